@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark of the FLAIR-1 segmentation hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or
 started plainly — then this process only SPAWNS the N ranks (one per GPU, RCCL over xGMI) and never touches a GPU
@@ -10,7 +10,12 @@ itself; it exits with the worst child exit code and rank 0's JSON line is the ou
 One "step" = one pass of the hot path over one batch of synthetic tiles already resident in HBM:
 U-Net/ResNet34 forward -> fused CE/argmax/confusion-matrix head -> backward -> (RCCL gradient all-reduce,
 N>1) -> SGD.  Workload = BASELINE.json configs[1]: 5-channel 512x512 tiles, 13 classes, bf16 compute,
-batch 32 per GPU (weak scaling).  Rank 0 prints ONE JSON line.  Extra objects on that line:
+batch 32 per GPU (weak scaling).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value` tiles/s, `ms_per_step`) with the figures
+derived from it.  --dump-outputs DIR then writes what the last timed step computed (see dump_outputs).  Everything else
+runs with --full only, after the timed steps: the inference leg (`inference_tiles_per_s`), the per-kernel tables and the
+extra objects below.  With --full the last timed step also carries the per-kernel HIP events behind `roofline`.
   roofline      dominant kernel, timed live with HIP events on its launch stream during the last timed step
   cpu_baseline  the oracle (torch-CPU fp32 restatement of the reference's CPU path) on a bounded sample
   surface       (N=1, outside the timed region) the same step driven through the reference's own surface:
@@ -233,6 +238,37 @@ def surface_throughput(args, dev, img, lab):
     return out
 
 
+DUMP_SAMPLE = 1 << 22     # elements kept of a larger output: 3 sampled arrays x 16 MiB stay under the 64 MB cap
+DUMP_CAP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, trainer):
+    """What the last timed step handed back to its caller, as DIR/<name>.npy (float32 / float64): the loss, the argmax
+    masks of the fused head, the confusion matrix it accumulated, and the model state after the SGD update (weights, BN
+    running statistics) with the gradient it was made from.  An array above DUMP_SAMPLE elements is a fixed sample
+    (seed 0, sorted flat indices, the same for the same shape), so two builds run with the same arguments compare
+    element for element."""
+    import numpy as np
+    m = trainer.model
+    arrays = {"loss": (trainer.loss.reshape(1), np.float32),
+              "preds": (trainer._preds, np.float32),
+              "confmat": (trainer.confmat, np.float64),
+              "params": (m.flat_parameters(), np.float32),
+              "grads": (trainer.grads, np.float32),
+              "buffers": (m.flat_buffers(), np.float32)}
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, (t, dt) in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy().astype(dt)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= DUMP_CAP_BYTES, total
+
+
 def spawn_ranks(n, cmd, env=None, timeout=None):
     """Start `cmd` n times as ranks 0..n-1 of one node (what torch.distributed.run / Lightning's DDP launcher does for the
     reference, src/flair/tasks.py:83-88) and wait.  Rank 0 inherits stdout; the other ranks' stdout goes to stderr.
@@ -285,11 +321,18 @@ def main():
     ap.add_argument("--no-overlap", action="store_true")
     ap.add_argument("--train-only", action="store_true",
                     help="skip the eval-mode inference leg (profiling runs: only train-step launches in the trace)")
-    ap.add_argument("--kernels", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--kernels", action="store_true", help="print the per-kernel table (and `roofline`) to stderr")
     ap.add_argument("--no-alone", action="store_true", help="skip the extra single-stream step behind `roofline_alone`")
     ap.add_argument("--force-exchange", action="store_true",
                     help="rehearse the RCCL gradient exchange (events, side stream, buckets) with a single rank")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel roofline, inference leg, fp32 parity mode, "
+                         "reference-surface throughput, CPU baseline, exposed communication (N>1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain start: become the launcher.  device_count() does not initialise the GPU on this image.
@@ -337,24 +380,27 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    profile = args.full or args.kernels   # per-kernel events in the last timed step
     for _ in range(args.warmup):
         trainer.train_step(img, lab)
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == args.steps - 1:
+        if profile and i == args.steps - 1:
             L.check(L.lib().flair_profile_start(4096))  # events around every kernel of the LAST timed step
         trainer.train_step(img, lab)
     sync()
     dt = time.perf_counter() - t0
-    prof = collect_profile(L)
+    prof = collect_profile(L) if profile else []
     loss = float(trainer.loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer)
 
     full_workload = args.dtype == "bf16" and args.batch == 32 and args.size == 512
 
     # the dominant kernel alone: one more step with the weight gradients on the caller's stream (outside the timed region)
     prof_alone = []
-    if world == 1 and not args.no_alone:   # (single rank only: a lone extra step would wait in the all-reduce for ever)
+    if args.full and world == 1 and not args.no_alone:   # (single rank only: a lone extra step would wait in the all-reduce for ever)
         L.lib().flair_tune_set(b"FLAIR_WGRAD_STREAM", 0)
         trainer.train_step(img, lab)
         L.check(L.lib().flair_profile_start(4096))
@@ -363,7 +409,7 @@ def main():
         L.lib().flair_tune_set(b"FLAIR_WGRAD_STREAM", 1)
 
     # inference tiles/s (eval-mode forward + argmax(softmax)), same tiles
-    inf_iters = 0 if args.train_only else max(3, args.steps // 2)
+    inf_iters = 0 if args.train_only or not args.full else max(3, args.steps // 2)
     for _ in range(2 if inf_iters else 0):
         trainer.predict(img)
     sync()
@@ -381,7 +427,7 @@ def main():
     # fp32 parity mode (exact v_mfma_f32_16x16x4_f32 arithmetic, the mode the mask / logit parity is asserted in): same
     # workload, a few steps, outside the timed region
     fp32 = None
-    if rank == 0 and world == 1 and args.dtype == "bf16" and not args.train_only:
+    if args.full and rank == 0 and world == 1 and args.dtype == "bf16" and not args.train_only:
         del trainer, model
         torch.cuda.empty_cache()
         m32 = flair_amd.create_model("unet", "resnet34", encoder_weights=None, in_channels=5, classes=args.classes,
@@ -404,36 +450,38 @@ def main():
 
     exchange = None
     if world > 1:
-        own_ms = 1e3 * dt / args.steps
-        # the same ranks without the gradient exchange (each rank's own compute; the replicas drift apart from here on, which
-        # no longer matters): what the exchange leaves exposed is the difference to the timed region
-        trainer.exchange = False
-        k2 = max(2, min(args.steps, 10))
-        trainer.train_step(img, lab)
-        sync()
-        t3 = time.perf_counter()
-        for _ in range(k2):
+        if args.full:
+            own_ms = 1e3 * dt / args.steps
+            # the same ranks without the gradient exchange (each rank's own compute; the replicas drift apart from here on,
+            # which no longer matters): what the exchange leaves exposed is the difference to the timed region
+            trainer.exchange = False
+            k2 = max(2, min(args.steps, 10))
             trainer.train_step(img, lab)
-        sync()
-        solo_ms = 1e3 * (time.perf_counter() - t3) / k2
-        ones = torch.ones(1, dtype=torch.float64, device=dev)
-        dist.all_reduce(ones)
-        per_rank = [torch.zeros(2, dtype=torch.float64, device=dev) for _ in range(world)]
-        dist.all_gather(per_rank, torch.tensor([own_ms, solo_ms], dtype=torch.float64, device=dev))
+            sync()
+            t3 = time.perf_counter()
+            for _ in range(k2):
+                trainer.train_step(img, lab)
+            sync()
+            solo_ms = 1e3 * (time.perf_counter() - t3) / k2
+            ones = torch.ones(1, dtype=torch.float64, device=dev)
+            dist.all_reduce(ones)
+            per_rank = [torch.zeros(2, dtype=torch.float64, device=dev) for _ in range(world)]
+            dist.all_gather(per_rank, torch.tensor([own_ms, solo_ms], dtype=torch.float64, device=dev))
         t = torch.tensor([dt, dti], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)   # the headline is the slowest rank's timed region
         dt, dti = float(t[0]), float(t[1])
-        solo_max = max(float(p[1]) for p in per_rank)
-        exchange = {"backend": "rccl" if backend == "nccl" else backend, "collective_ranks": int(round(float(ones[0]))),
-                    "per_rank_ms_per_step": [round(float(p[0]), 3) for p in per_rank],
-                    "ms_per_step_without_exchange": round(solo_max, 3),
-                    "exposed_comm_ms_per_step": round(1e3 * dt / args.steps - solo_max, 3),
-                    "overlap": not args.no_overlap, "buckets": len(trainer.buckets),
-                    "bucket_mbytes": [round(4e-6 * (e - b), 2) for b, e in trainer.buckets]}
+        if args.full:
+            solo_max = max(float(p[1]) for p in per_rank)
+            exchange = {"backend": "rccl" if backend == "nccl" else backend, "collective_ranks": int(round(float(ones[0]))),
+                        "per_rank_ms_per_step": [round(float(p[0]), 3) for p in per_rank],
+                        "ms_per_step_without_exchange": round(solo_max, 3),
+                        "exposed_comm_ms_per_step": round(1e3 * dt / args.steps - solo_max, 3),
+                        "overlap": not args.no_overlap, "buckets": len(trainer.buckets),
+                        "bucket_mbytes": [round(4e-6 * (e - b), 2) for b, e in trainer.buckets]}
 
     # the same step through the reference's own surface (LightningModule hooks, autograd, torch.optim.SGD)
     surface = None
-    if rank == 0 and world == 1 and not args.train_only:
+    if args.full and rank == 0 and world == 1 and not args.train_only:
         surface = surface_throughput(args, dev, img, lab)
 
     if rank == 0:
@@ -480,7 +528,7 @@ def main():
         if surface:
             surface["train_frac_of_value"] = round(surface["train_tiles_per_s"] / value, 4)
             res["surface"] = surface
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(2, args.size, args.classes, iters=24)
         print(json.dumps(res), flush=True)
     if dist.is_initialized():

@@ -2,7 +2,7 @@
 # Dynamic instruction mix per kernel (one PMC pass): VALU / SALU / LDS / VMEM instructions per wave.
 set -e
 REPO=$(pwd); export TMPDIR=/tmp; OUT=$REPO/gpurun_out/pmc_insts; rm -rf $OUT; mkdir -p $OUT; cd /tmp
-rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA --output-format csv -d $OUT/p -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> $OUT/log.txt
+rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_MFMA --output-format csv -d $OUT/p -- python3 $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> $OUT/log.txt
 cd $REPO
 F=$(find $OUT/p -name "*counter_collection.csv" | head -1)
 python3 - "$F" > $OUT/insts.txt <<'PY'

@@ -1,6 +1,6 @@
 set -e
 REPO=$(pwd); export TMPDIR=/tmp; OUT=$REPO/gpurun_out/pmc_step; rm -rf $OUT; mkdir -p $OUT; cd /tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/p -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> $OUT/log.txt
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/p -- python3 $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> $OUT/log.txt
 cd $REPO
 F=$(find $OUT/p -name "*counter_collection.csv" | head -1)
 python3 - "$F" > $OUT/lds.txt <<'PY'

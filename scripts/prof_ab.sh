@@ -10,7 +10,7 @@ cd /tmp
 for v in "$@"; do
   rm -rf "$OUT/t_$v"
   export $KEY=$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/t_$v" -- python3 "$REPO/bench.py" --steps 13 --warmup 3 --no-cpu-baseline --train-only --no-alone > "$OUT/${KEY}_${v}.json" 2> "$OUT/${KEY}_${v}.log" || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/t_$v" -- python3 "$REPO/bench.py" --full --steps 13 --warmup 3 --no-cpu-baseline --train-only --no-alone > "$OUT/${KEY}_${v}.json" 2> "$OUT/${KEY}_${v}.log" || exit 1
   S=$(find "$OUT/t_$v" -name "*kernel_stats.csv" | head -1)
   cp "$S" "$OUT/${KEY}_${v}_kernel_stats.csv"
   rm -rf "$OUT/t_$v"

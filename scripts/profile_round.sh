@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/prof_$R
 rm -rf "$OUT" && mkdir -p "$OUT"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$REPO/bench.py" --steps 13 --warmup 3 --no-cpu-baseline --train-only --no-alone > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> "$OUT/fetch.log"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- python3 "$REPO/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> "$OUT/write.log"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$REPO/bench.py" --full --steps 13 --warmup 3 --no-cpu-baseline --train-only --no-alone > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> "$OUT/fetch.log"
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- python3 "$REPO/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --train-only --no-alone > /dev/null 2> "$OUT/write.log"
 cd "$REPO"
 F=$(find "$OUT/fetch" -name "*counter_collection.csv" | head -1)
 W=$(find "$OUT/write" -name "*counter_collection.csv" | head -1)

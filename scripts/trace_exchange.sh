@@ -1,6 +1,6 @@
 set -e
 REPO=$(pwd); export TMPDIR=/tmp; OUT=$REPO/gpurun_out/exch; rm -rf $OUT; mkdir -p $OUT; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 $REPO/bench.py --steps 8 --warmup 3 --no-cpu-baseline --train-only --no-alone --force-exchange > $OUT/bench.json 2> $OUT/log.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 $REPO/bench.py --full --steps 8 --warmup 3 --no-cpu-baseline --train-only --no-alone --force-exchange > $OUT/bench.json 2> $OUT/log.txt
 cd $REPO
 S=$(find $OUT/t -name "*kernel_stats.csv" | head -1)
 python3 - "$S" <<'PY'

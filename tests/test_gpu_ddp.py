@@ -103,7 +103,7 @@ def test_bench_n_gt_1_branch_runs_end_to_end_on_gloo():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
-                        "--size", "64", "--dtype", "f32", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--size", "64", "--dtype", "f32", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["scaling"] == "weak"
