@@ -199,6 +199,29 @@ int flair_detect_stitch_preds(const uint8_t* preds_u8, const float* maxprob_f32,
   if (!preds_u8 || !maxprob_f32 || !raster_out || !tiles) return -1;
   return detect_stitch_preds(preds_u8, maxprob_f32, B, S, margin, tiles, raster_out, raster_h, raster_w, (hipStream_t)stream);
 }
+int flair_detect_blend_accum(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
+                             int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream) {
+  if (!logits_nchw || !tiles || !ring) return -1;
+  return detect_blend_accum(logits_nchw, B, C, S, margin, tiles, cheb_weights, x_lo, x_hi, y_lo, y_hi, ring, raster_h, raster_w,
+                            (hipStream_t)stream);
+}
+int flair_detect_blend_flush(float* ring, int C, int ring_cols, int x_lo, int x_hi, float* raster_out, int raster_h, int raster_w,
+                             void* stream) {
+  if (!ring || !raster_out) return -1;
+  return detect_blend_flush(ring, C, ring_cols, x_lo, x_hi, raster_out, raster_h, raster_w, (hipStream_t)stream);
+}
+int flair_detect_stitch_max(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
+                            int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream) {
+  if (!logits_nchw || !tiles || !raster_out) return -1;
+  return detect_stitch_max(logits_nchw, nullptr, nullptr, B, C, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
+                           raster_w, (hipStream_t)stream);
+}
+int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
+                                  int x_lo, int x_hi, int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream) {
+  if (!preds_u8 || !maxprob_f32 || !tiles || !raster_out) return -1;
+  return detect_stitch_max(nullptr, preds_u8, maxprob_f32, B, 0, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
+                           raster_w, (hipStream_t)stream);
+}
 int flair_gather_tiles(const uint8_t* raster_u8, int bands, int raster_h, int raster_w, const int32_t* tiles, int B, int S,
                        const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
                        float* img_out, void* stream) {

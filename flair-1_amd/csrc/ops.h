@@ -107,6 +107,12 @@ int detect_stitch_preds(const unsigned char* preds, const float* maxprob, int B,
                         int Hr, int Wr, hipStream_t s);
 int detect_convert(const float* logits, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,
                    hipStream_t s);
+// zone_detect overlap stitching (csrc/zone_stitch.hip); rectangles are [x_lo, x_hi) x [y_lo, y_hi) of the raster
+int detect_blend_accum(const float* logits, int B, int C, int S, int margin, const int* tiles, const float* wtab, int x_lo, int x_hi,
+                       int y_lo, int y_hi, float* ring, int Hr, int Wr, hipStream_t s);
+int detect_blend_flush(float* ring, int C, int K, int x_lo, int x_hi, float* out, int Hr, int Wr, hipStream_t s);
+int detect_stitch_max(const float* logits, const unsigned char* preds, const float* maxprob, int B, int C, int S, int margin,
+                      const int* tiles, int x_lo, int x_hi, int y_lo, int y_hi, float* out, int Hr, int Wr, hipStream_t s);
 int confmat_masks(const unsigned char* truth, const unsigned char* pred, long n, int C, int truth_offset, long long* confmat,
                   hipStream_t s);
 

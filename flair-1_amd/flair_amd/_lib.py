@@ -75,6 +75,10 @@ PROTOTYPES = {
     "flair_unet_reuse_constants": (i32, [vp, i32]),
     "flair_unet_want_preds": (i32, [vp, vp, vp]),
     "flair_detect_stitch_preds": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "flair_detect_blend_accum": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "flair_detect_blend_flush": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "flair_detect_stitch_max": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "flair_detect_stitch_max_preds": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_segformer_create": (i32, [C.POINTER(vp), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32]),
     "flair_segformer_destroy": (None, [vp]),
     "flair_segformer_param_count": (i64, [vp]),

@@ -1,12 +1,15 @@
-"""Device-side head of zone_detect's per-batch inference.
+"""Device-side zone_detect.
 
 The reference runs the model, takes ``softmax`` over classes, copies the FULL probability tensor to the host
 (19 MiB per 512x512 tile at 19 classes) and then, per tile on the CPU, crops the margin and calls ``convert``
 (src/zone_detect/compare.py:20-39,71-76; src/zone_detect/dataset.py:11-34).  ``inference`` below keeps the argument
 list of the reference function; with ``fused=True`` (default) it returns the cropped, converted tiles
 (2 x float32 per kept pixel for 'argmax', C bytes for 'class_prob') so that only those cross PCIe.
-Stitching modes that need the uncropped probabilities ('average', 'average_weights', 'max') and the raster
-windowing are outside this row.
+
+``ZoneDetector`` runs a whole raster resident in HBM: the default pipeline (exact clipping, main.py:386-428) and, for a
+config holding one combination of the comparison grid (``gen_param_combination``, main.py:275-372), the overlap stitching
+modes 'average', 'average_weights' and 'max' (compare.py:84-136 as DESIGN §8 states their intent), blended on the device
+by the gather-form kernels of csrc/zone_stitch.hip.  ``compare`` is the comparison loop without file I/O or metrics.
 """
 from __future__ import annotations
 
@@ -110,9 +113,134 @@ def tile_grid(img_size, patch_size: int, margin: int, stride: int | None = None)
     return np.asarray(rows, dtype=np.int32)
 
 
+STITCHING = ("exact-clipping", "average", "average_weights", "max")   # the methods of compare.py:67-136
+
+
+def gen_param_combination(config: dict) -> list:
+    """src/zone_detect/utils.py:110-166: every (padding, tile size, margin, stride, stitching) combination of the comparison
+    grid, quirks included: the stitching methods are read from ``strategies.stitching.methods`` (the shipped YAML writes
+    ``method``, which is ignored), a margin below 1 is a fraction of the tile size, combinations with size <= 2 * margin are
+    skipped and the strides come from ``get_stride`` (so from ``stride_range`` only when ``overlap_strat`` is set)."""
+    combi = []
+    padding_list = config.get("strategies", {}).get("padding_overall", [])
+    if not padding_list:
+        padding_list = ["no-padding"]
+    tiling_cfg = config.get("strategies", {}).get("tiling", {})
+    if tiling_cfg.get("enabled", False):
+        tile_size_list = tiling_cfg.get("size_range", [config["img_pixels_detection"]])
+    else:
+        tile_size_list = [config["img_pixels_detection"]]
+    stitching_cfg = config.get("strategies", {}).get("stitching", {})
+    if stitching_cfg.get("enabled", False):
+        margin_list = stitching_cfg.get("margin", [config["margin"]])
+        stitching_methods = stitching_cfg.get("methods", ["exact-clipping"])
+    else:
+        margin_list = [config["margin"]]
+        stitching_methods = ["exact-clipping"]
+    for padding in padding_list:
+        for img_pixels_detection in tile_size_list:
+            for margin in margin_list:
+                if margin < 1:
+                    margin = int(margin * img_pixels_detection)
+                if img_pixels_detection <= 2 * margin:
+                    continue
+                tmp_config = config.copy()
+                tmp_config["margin"] = margin
+                tmp_config["img_pixels_detection"] = img_pixels_detection
+                for stride in get_stride(tmp_config):
+                    for stitch in stitching_methods:
+                        combi.append({"img_pixels_detection": img_pixels_detection, "margin": margin, "padding": padding,
+                                      "stitching": stitch, "stride": stride})
+    return combi
+
+
+def method_name(combi: dict) -> str:
+    """main.py:302"""
+    return (f"size={combi['img_pixels_detection']}_stride={combi['stride']}_margin={combi['margin']}"
+            f"_padding={combi['padding']}_stitching={combi['stitching']}")
+
+
+def cheb_weight_table(patch_size: int):
+    """patch_weights(S, 0.5, 'exp') by Chebyshev distance d = 0 .. S // 2 to the patch centre, float32: the table
+    flair_detect_blend_accum reads for 'average_weights'."""
+    import numpy as np
+    w = patch_weights(patch_size, sigma=0.5, mode="exp")
+    c = patch_size // 2
+    return np.ascontiguousarray(w[c - np.arange(c + 1), c], dtype=np.float32)
+
+
+class OverlapStitch:
+    """Device state of one overlap-stitched job ('average', 'average_weights' or 'max') over the windows of ``grid``
+    (tile_grid rows, job order): ``add`` the model's output for job windows [b0, b0 + B) in order, then ``finish``.
+
+    'average' / 'average_weights' accumulate sum(w p) and sum(w) in a ring of K = S - 2m raster columns (x mod K): the job
+    runs columns outer, so once the windows of one column are in, every pixel left of the next column's core is final and
+    is flushed to the output before that column's first window.  A batch that straddles a column boundary is split into one
+    launch per column.  'max' keeps its running (class, probability) in the output itself."""
+
+    def __init__(self, method: str, grid, patch_size: int, margin: int, n_classes: int, raster_h: int, raster_w: int, device):
+        import numpy as np
+        if method not in STITCHING[1:]:
+            raise ValueError(f"no overlap stitching named {method!r}")
+        self.method, self.S, self.m, self.C = method, int(patch_size), int(margin), int(n_classes)
+        self.H, self.W, self.K = int(raster_h), int(raster_w), self.S - 2 * self.m
+        self.grid = np.asarray(grid)
+        self.out = torch.zeros(2, self.H, self.W, dtype=torch.float32, device=device)
+        self.ring = None if method == "max" else torch.zeros(self.C + 1, self.H, self.K, dtype=torch.float32, device=device)
+        self.wtab = (torch.from_numpy(cheb_weight_table(self.S)).to(device) if method == "average_weights" else None)
+        xs = self.grid[:, 0]
+        self._col_start = np.concatenate([[True], xs[1:] != xs[:-1]])
+        self._flushed = 0   # raster columns [0, _flushed) are final in self.out
+
+    def _flush(self, hi: int):
+        lo = self._flushed
+        if hi > lo:
+            # columns past lo + K lie between two columns' cores (stride > K): no window reached them, nothing to flush
+            L.check(L.lib().flair_detect_blend_flush(L.ptr(self.ring), self.C, self.K, lo, min(hi, lo + self.K), L.ptr(self.out),
+                                                     self.H, self.W, L.stream()), "flair_detect_blend_flush")
+            self._flushed = hi
+
+    def add(self, b0: int, tiles: torch.Tensor, logits: torch.Tensor = None, preds: torch.Tensor = None, prob: torch.Tensor = None):
+        """tiles: the device rows of job windows [b0, b0 + B); logits fp32 (B, C, S, S), or (preds u8, prob f32) (B, S, S)
+        from predict_classes (method 'max' only)."""
+        B = tiles.shape[0]
+        cuts = [b0] + [b for b in range(b0 + 1, b0 + B) if self._col_start[b]] + [b0 + B]
+        for s, e in zip(cuts[:-1], cuts[1:]):
+            x0 = int(self.grid[s, 0])
+            ys = self.grid[s:e, 1]
+            x_lo, x_hi = max(x0 + self.m, 0), min(x0 + self.S - self.m, self.W)
+            y_lo, y_hi = max(int(ys.min()) + self.m, 0), min(int(ys.max()) + self.S - self.m, self.H)
+            t = tiles[s - b0:e - b0]
+            if self.method == "max":
+                if preds is not None:
+                    rc = L.lib().flair_detect_stitch_max_preds(L.ptr(preds[s - b0:e - b0]), L.ptr(prob[s - b0:e - b0]), e - s, self.S,
+                                                               self.m, L.ptr(t), x_lo, x_hi, y_lo, y_hi, L.ptr(self.out), self.H, self.W,
+                                                               L.stream())
+                    L.check(rc, "flair_detect_stitch_max_preds")
+                else:
+                    rc = L.lib().flair_detect_stitch_max(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
+                                                         x_lo, x_hi, y_lo, y_hi, L.ptr(self.out), self.H, self.W, L.stream())
+                    L.check(rc, "flair_detect_stitch_max")
+                continue
+            if self._col_start[s]:
+                self._flush(min(x0 + self.m, self.W))
+            rc = L.lib().flair_detect_blend_accum(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
+                                                  L.ptr(self.wtab), x_lo, x_hi, y_lo, y_hi, L.ptr(self.ring), self.H, self.W,
+                                                  L.stream())
+            L.check(rc, "flair_detect_blend_accum")
+
+    def finish(self) -> torch.Tensor:
+        if self.ring is not None:
+            self._flush(self.W)
+        return self.out
+
+
 class ZoneDetector:
     """``model`` over a whole raster: windows are cut, normalised, inferred, converted and stitched on the device; the
-    raster goes up once as stored bytes and the result comes down once."""
+    raster goes up once as stored bytes and the result comes down once.
+
+    A config with a ``stitching`` key is one combination of the comparison grid (main.py:287-298, ``gen_param_combination``)
+    and must carry ``stride``; without one the pipeline is the default (exact clipping, stride ``get_stride``)."""
 
     def __init__(self, model, config: dict):
         import ctypes as C
@@ -122,9 +250,25 @@ class ZoneDetector:
         self.output_type = config["output_type"]
         if self.output_type not in OUTPUT_TYPES:
             raise ValueError("The output type has not been interpreted.")
-        if config.get("overlap_strat"):
-            raise NotImplementedError("overlap strategies ('average', 'average_weights', 'max') are not built yet")
-        self.stride = get_stride(config)[0]
+        self.stitching = config.get("stitching")
+        if self.stitching is None:
+            if config.get("overlap_strat"):
+                raise NotImplementedError("overlap_strat describes a comparison grid: expand it with gen_param_combination(config) "
+                                          "and run one ZoneDetector per combination (or compare())")
+            self.stitching = "exact-clipping"
+            self.stride = get_stride(config)[0]
+        else:
+            if self.stitching not in STITCHING:
+                raise ValueError(f"unknown stitching {self.stitching!r} (one of {', '.join(STITCHING)})")
+            if config.get("stride") is None:
+                raise ValueError("a stitching combination needs its 'stride' (gen_param_combination)")
+            if config.get("padding", "no-padding") != "no-padding":
+                raise ValueError(f"padding {config['padding']!r} is not implemented (only 'no-padding')")
+            self.stride = int(config["stride"])
+            if self.stride < 1:
+                raise ValueError("stride must be a positive number of pixels")
+        # class_prob output is stitched by exact clipping whatever the method (compare.py:67-68)
+        self.blend = None if self.stitching == "exact-clipping" or self.output_type == "class_prob" else self.stitching
         self.batch_size = int(config.get("batch_size", 4))
         self.channels = [int(c) for c in config["channels"]]
         norma = config["norma_task"][0]
@@ -138,6 +282,27 @@ class ZoneDetector:
         self._stds = (C.c_double * n)(*[float(s) for s in stds[:n]]) if self.norm_type == "custom" else None
         self.n_classes = int(config["n_classes"])
 
+    def _fast_preds(self, mode: int) -> bool:
+        """'argmax' output from a U-Net in eval mode: class and probability leave the head convolution's epilogue, the logits
+        are never written"""
+        if not (mode == 0 and hasattr(self.model, "predict_classes") and not self.model.training):
+            return False
+        if getattr(self.model, "classes", self.n_classes) != self.n_classes:
+            raise RuntimeError(f"model has {self.model.classes} classes, config says {self.n_classes}")
+        return True
+
+    def _logits(self, imgs: torch.Tensor) -> torch.Tensor:
+        if hasattr(self.model, "forward_full"):
+            # HuggingFace provider (SegFormer): `.logits` come at 1/4 of the tile size, which neither the margin crop nor
+            # convert (compare.py:69-82) rescale; the x4 bilinear upsample (align_corners=False) the library itself applies
+            # in front of its loss brings them to tile resolution first
+            logits = self.model.forward_full(imgs)
+        else:
+            logits = self.model(imgs).float().contiguous()
+        if logits.shape[1] != self.n_classes:
+            raise RuntimeError(f"model returned {logits.shape[1]} classes, config says {self.n_classes}")
+        return logits
+
     @torch.no_grad()
     def run(self, raster_u8: torch.Tensor) -> torch.Tensor:
         if not raster_u8.is_cuda or raster_u8.dtype != torch.uint8 or raster_u8.dim() != 3:
@@ -145,10 +310,15 @@ class ZoneDetector:
         raster_u8 = raster_u8.contiguous()
         bands, Hr, Wr = raster_u8.shape
         dev = raster_u8.device
-        grid = torch.from_numpy(tile_grid((Wr, Hr), self.S, self.margin, self.stride)).to(dev)
+        grid_np = tile_grid((Wr, Hr), self.S, self.margin, self.stride)
+        grid = torch.from_numpy(grid_np).to(dev)
         mode = OUTPUT_TYPES[self.output_type]
-        out = (torch.zeros(2, Hr, Wr, dtype=torch.float32, device=dev) if mode == 0
-               else torch.zeros(self.n_classes, Hr, Wr, dtype=torch.uint8, device=dev))
+        blend = (OverlapStitch(self.blend, grid_np, self.S, self.margin, self.n_classes, Hr, Wr, dev) if self.blend else None)
+        if blend is not None:
+            out = blend.out
+        else:
+            out = (torch.zeros(2, Hr, Wr, dtype=torch.float32, device=dev) if mode == 0
+                   else torch.zeros(self.n_classes, Hr, Wr, dtype=torch.uint8, device=dev))
         from .data_feed import NORM_CODES
         for b0 in range(0, grid.shape[0], self.batch_size):
             tiles = grid[b0:b0 + self.batch_size].contiguous()
@@ -157,26 +327,39 @@ class ZoneDetector:
             L.check(L.lib().flair_gather_tiles(L.ptr(raster_u8), bands, Hr, Wr, L.ptr(tiles), B, self.S, self._ch,
                                                len(self.channels), NORM_CODES[self.norm_type], self._means, self._stds,
                                                L.ptr(imgs), L.stream()), "flair_gather_tiles")
-            if mode == 0 and hasattr(self.model, "predict_classes") and not self.model.training:
-                # 'argmax' output: class and probability leave the head convolution's epilogue, the logits are never written
-                if getattr(self.model, "classes", self.n_classes) != self.n_classes:
-                    raise RuntimeError(f"model has {self.model.classes} classes, config says {self.n_classes}")
+            if blend is not None:
+                if self.blend == "max" and self._fast_preds(mode):
+                    preds, prob = self.model.predict_classes(imgs, want_prob=True)
+                    blend.add(b0, tiles, preds=preds, prob=prob)
+                else:
+                    blend.add(b0, tiles, logits=self._logits(imgs))
+                continue
+            if self._fast_preds(mode):
                 preds, prob = self.model.predict_classes(imgs, want_prob=True)
                 L.check(L.lib().flair_detect_stitch_preds(L.ptr(preds), L.ptr(prob), B, self.S, self.margin, L.ptr(tiles), L.ptr(out),
                                                           Hr, Wr, L.stream()), "flair_detect_stitch_preds")
                 continue
-            if hasattr(self.model, "forward_full"):
-                # HuggingFace provider (SegFormer): `.logits` come at 1/4 of the tile size, which neither the margin crop nor
-                # convert (compare.py:69-82) rescale; the x4 bilinear upsample (align_corners=False) the library itself applies
-                # in front of its loss brings them to tile resolution first
-                logits = self.model.forward_full(imgs)
-            else:
-                logits = self.model(imgs).float().contiguous()
-            if logits.shape[1] != self.n_classes:
-                raise RuntimeError(f"model returned {logits.shape[1]} classes, config says {self.n_classes}")
+            logits = self._logits(imgs)
             L.check(L.lib().flair_detect_stitch(L.ptr(logits), B, self.n_classes, self.S, self.margin, mode, L.ptr(tiles),
                                                 L.ptr(out), Hr, Wr, L.stream()), "flair_detect_stitch")
-        return out
+        return blend.finish() if blend is not None else out
+
+
+def compare(model, config: dict, raster_u8: torch.Tensor) -> dict:
+    """The comparison loop of main.py:275-372 without raster files or metrics: one ZoneDetector per combination of
+    ``gen_param_combination(config)``.  Returns {method name (main.py:302): (output raster, wall ms of the synchronised run)}."""
+    import time
+    results = {}
+    for combi in gen_param_combination(config):
+        cfg = dict(config)
+        cfg.update(combi)
+        det = ZoneDetector(model, cfg)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = det.run(raster_u8)
+        torch.cuda.synchronize()
+        results[method_name(combi)] = (out, (time.perf_counter() - t0) * 1e3)
+    return results
 
 
 # ------------------------------------------------------------------------------------------------------------------

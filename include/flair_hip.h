@@ -169,6 +169,27 @@ int flair_detect_stitch_preds(const uint8_t* preds_u8, const float* maxprob_f32,
                               float* raster_out, int raster_h, int raster_w, void* stream);
 int flair_detect_stitch(const float* logits_nchw, int B, int C, int S, int margin, int output_type, const int32_t* tiles,
                         void* raster_out, int raster_h, int raster_w, void* stream);
+/* Overlap stitching of zone_detect ('average', 'average_weights', 'max'; src/zone_detect/compare.py:84-136, intent as DESIGN §8
+ * states it): windows of the slicing job overlap (stride < S - 2m) and every window contributes its margin-cropped centre
+ * [x0+m, x0+S-m) x [y0+m, y0+S-m) clipped to the raster.  Each call touches the raster rectangle [x_lo, x_hi) x [y_lo, y_hi)
+ * only, one thread per pixel walking the call's B windows (tiles as above; only x0, y0 are read) in job order: no atomics,
+ * the result does not depend on how the job is cut into calls.
+ * flair_detect_blend_accum: ring (C+1, raster_h, S-2m) fp32, raster column x at ring column x mod (S-2m), += w * softmax(logits)
+ *   per class and += w in plane C; w = 1 when cheb_weights is null, else cheb_weights[max(|i - S/2|, |j - S/2|)] at patch pixel
+ *   (i, j) (S/2 + 1 fp32 entries: patch_weights(S, 0.5, 'exp') by Chebyshev distance).  x_hi - x_lo <= S - 2m.
+ * flair_detect_blend_flush: ring columns of raster columns [x_lo, x_hi) (x_hi - x_lo <= ring_cols), every row: where plane C
+ *   is > 0, raster_out (2, raster_h, raster_w) fp32 = [first argmax, max] of sum(w p) / sum(w); those ring entries are zeroed.
+ * flair_detect_stitch_max(_preds): raster_out (2, raster_h, raster_w) fp32 holds a running [class, probability]; a window's
+ *   (first argmax, its probability) — of softmax(logits), or the maps flair_unet_want_preds leaves — replaces it unless the
+ *   held probability is strictly greater. */
+int flair_detect_blend_accum(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
+                             int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream);
+int flair_detect_blend_flush(float* ring, int C, int ring_cols, int x_lo, int x_hi, float* raster_out, int raster_h, int raster_w,
+                             void* stream);
+int flair_detect_stitch_max(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
+                            int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
+int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
+                                  int x_lo, int x_hi, int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
 
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */

@@ -3,7 +3,9 @@
 pipeline (512-pixel windows, margin 128 -> 1600 windows), plus the per-batch cost of the device data feed.
 Prints one JSON line.  MODEL=segformer runs the same raster through SegFormer-MiT-B2 (5 channels, 19 labels: BASELINE
 config 5 as named), BATCH windows per forward (default 32 for the U-Net, 16 for SegFormer); KERNELS=1 adds the per-kernel table
-of one SegFormer batch (HIP events inside the library)."""
+of one SegFormer batch (HIP events inside the library).  STITCH=average|average_weights|max|exact-clipping and STRIDE=<pixels>
+run one combination of the comparison grid (zone_detect.gen_param_combination) instead of the default exact clipping at
+stride 256."""
 import json
 import os
 import sys
@@ -33,9 +35,12 @@ def main():
            "channels": [1, 2, 3, 4, 5],
            "norma_task": [{"norm_type": "custom", "norm_means": [105.08, 110.87, 101.82, 106.38, 53.26],
                            "norm_stds": [52.17, 45.38, 44, 39.69, 79.3]}]}
+    stitch, stride = os.environ.get("STITCH"), os.environ.get("STRIDE")
+    if stitch or stride:
+        cfg.update(stitching=stitch or "exact-clipping", stride=int(stride or 256), padding="no-padding")
     raster = torch.randint(0, 256, (5, side, side), dtype=torch.uint8, device=dev)
     det = ZoneDetector(model, cfg)
-    n = len(tile_grid((side, side), 512, 128))
+    n = len(tile_grid((side, side), 512, 128, det.stride))
     det.run(raster[:, :2048, :2048].contiguous())  # warm-up
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -78,7 +83,8 @@ def main():
                             "tflops": round(fl.value / max(ms.value, 1e-9) / 1e9, 1), "gbps": round(by.value / max(ms.value, 1e-9) / 1e6, 1)})
         kernels.sort(key=lambda r: -r["ms"])
     label = "SegFormer-MiT-B2" if which == "segformer" else "U-Net/ResNet34"
-    print(json.dumps({"workload": f"zone_detect {side}x{side}x5 uint8, {label} {dt_name}, 19 classes, argmax, 512/128, batch {batch}",
+    print(json.dumps({"workload": f"zone_detect {side}x{side}x5 uint8, {label} {dt_name}, 19 classes, argmax, 512/128, "
+                                  + (f"{det.stitching} stride {det.stride}, " if stitch or stride else "") + f"batch {batch}",
                       "kernels_one_batch": kernels,
                       "windows": n, "seconds": round(dt, 3), "windows_per_s": round(n / dt, 1),
                       "megapixels_per_s": round(side * side / dt / 1e6, 1), "result_d2h_s": round(d2h, 3),
