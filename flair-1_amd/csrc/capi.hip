@@ -222,6 +222,34 @@ int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_
   return detect_stitch_max(nullptr, preds_u8, maxprob_f32, B, 0, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
                            raster_w, (hipStream_t)stream);
 }
+int flair_zone_window_confmat_preds(const uint8_t* preds_u8, int B, int C, int S, int margin, const int32_t* tiles,
+                                    const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream) {
+  if (!preds_u8 || !tiles || !truth_u8 || !confmats) return -1;
+  return zone_window_confmat(0, preds_u8, B, C, S, margin, tiles, truth_u8, raster_h, raster_w, (long long*)confmats, (hipStream_t)stream);
+}
+int flair_zone_window_confmat_logits(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles,
+                                     const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream) {
+  if (!logits_nchw || !tiles || !truth_u8 || !confmats) return -1;
+  return zone_window_confmat(1, logits_nchw, B, C, S, margin, tiles, truth_u8, raster_h, raster_w, (long long*)confmats,
+                             (hipStream_t)stream);
+}
+int flair_zone_window_confmat_raster(const float* raster, int B, int C, int S, int margin, const int32_t* tiles, const uint8_t* truth_u8,
+                                     int raster_h, int raster_w, int64_t* confmats, void* stream) {
+  if (!raster || !tiles || !truth_u8 || !confmats) return -1;
+  return zone_window_confmat(2, raster, B, C, S, margin, tiles, truth_u8, raster_h, raster_w, (long long*)confmats, (hipStream_t)stream);
+}
+int flair_zone_raster_confmat(const float* raster, const uint8_t* truth_u8, int raster_h, int raster_w, int C, int64_t* confmat,
+                              void* stream) {
+  if (!raster || !truth_u8 || !confmat) return -1;
+  return zone_raster_confmat(raster, truth_u8, raster_h, raster_w, C, (long long*)confmat, (hipStream_t)stream);
+}
+int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raster_h, int raster_w, int K, const int32_t* row_origins,
+                         int n_rows, const int32_t* col_origins, int n_cols, double sigma, int radius, uint8_t* mask_ws,
+                         int32_t* colsum_ws, int32_t* counts_ws, double* tmp_ws, double* error_map, void* stream) {
+  if (!raster || !truth_u8 || !row_origins || !col_origins || !mask_ws || !colsum_ws || !counts_ws || !tmp_ws || !error_map) return -1;
+  return zone_error_map(raster, truth_u8, raster_h, raster_w, K, row_origins, n_rows, col_origins, n_cols, sigma, radius, mask_ws,
+                        colsum_ws, counts_ws, tmp_ws, error_map, (hipStream_t)stream);
+}
 int flair_gather_tiles(const uint8_t* raster_u8, int bands, int raster_h, int raster_w, const int32_t* tiles, int B, int S,
                        const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
                        float* img_out, void* stream) {

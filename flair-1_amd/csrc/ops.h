@@ -115,5 +115,11 @@ int detect_stitch_max(const float* logits, const unsigned char* preds, const flo
                       const int* tiles, int x_lo, int x_hi, int y_lo, int y_hi, float* out, int Hr, int Wr, hipStream_t s);
 int confmat_masks(const unsigned char* truth, const unsigned char* pred, long n, int C, int truth_offset, long long* confmat,
                   hipStream_t s);
+// zone_detect metrics (csrc/zone_metrics.hip); source 0: u8 class tiles (B, S, S), 1: fp32 logits (B, C, S, S), 2: fp32 raster
+int zone_window_confmat(int source, const void* pred, int B, int C, int S, int margin, const int* tiles, const unsigned char* truth,
+                        int Hr, int Wr, long long* confmats, hipStream_t s);
+int zone_raster_confmat(const float* band, const unsigned char* truth, int Hr, int Wr, int C, long long* confmat, hipStream_t s);
+int zone_error_map(const float* band, const unsigned char* truth, int Hr, int Wr, int K, const int* ys, int ny, const int* xs, int nx,
+                   double sigma, int radius, unsigned char* mask, int* colsum, int* counts, double* tmp, double* out, hipStream_t s);
 
 }  // namespace flair

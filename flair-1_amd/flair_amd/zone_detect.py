@@ -9,16 +9,20 @@ list of the reference function; with ``fused=True`` (default) it returns the cro
 ``ZoneDetector`` runs a whole raster resident in HBM: the default pipeline (exact clipping, main.py:386-428) and, for a
 config holding one combination of the comparison grid (``gen_param_combination``, main.py:275-372), the overlap stitching
 modes 'average', 'average_weights' and 'max' (compare.py:84-136 as DESIGN §8 states their intent), blended on the device
-by the gather-form kernels of csrc/zone_stitch.hip.  ``compare`` is the comparison loop without file I/O or metrics.
+by the gather-form kernels of csrc/zone_stitch.hip.  ``compare`` is the comparison loop without file I/O or metrics;
+``run(raster, truth)`` also counts every window's confusion matrix on the device, and ``zone_metrics.evaluate`` is the
+comparison loop with metrics (main.py:255-372 with --metrics).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib as L
 
 OUTPUT_TYPES = {"argmax": 0, "class_prob": 1}   # the values config["output_type"] may take (compare.py:69-82)
 _MODE_PROBS = 2                                   # private: every fp32 softmax probability, no convert (compare.py:35)
+_MAX_GRID_Y = 65535                               # windows per launch of the per-window confusion matrices (grid.y)
 
 
 def detect_convert(logits: torch.Tensor, margin: int, output_type: str, _probs: bool = False) -> torch.Tensor:
@@ -281,6 +285,22 @@ class ZoneDetector:
         self._means = (C.c_double * n)(*[float(m) for m in means[:n]]) if self.norm_type == "custom" else None
         self._stds = (C.c_double * n)(*[float(s) for s in stds[:n]]) if self.norm_type == "custom" else None
         self.n_classes = int(config["n_classes"])
+        self.classes = config.get("classes")
+        self.window_confmats = None   # run(raster, truth): (n, C, C) int64 on the device, one per window in job order
+        self.window_rects = None      # and their (col_off, row_off, width, height) core rectangles, numpy int32 (n, 4)
+
+    def _check_truth(self, truth_u8: torch.Tensor, Hr: int, Wr: int):
+        if not truth_u8.is_cuda or truth_u8.dtype != torch.uint8 or tuple(truth_u8.shape) != (Hr, Wr):
+            raise ValueError(f"truth must be a ({Hr}, {Wr}) uint8 tensor on the HIP device, the raster's extent "
+                             f"(got {tuple(truth_u8.shape)} {truth_u8.dtype} on {truth_u8.device})")
+        if self.output_type != "argmax":
+            raise ValueError("metrics need the 'argmax' output: band 0 of 'class_prob' is a probability, not a class")
+        if not self.classes:
+            raise ValueError("metrics need config['classes'] (the class weights and names of the confusion matrix)")
+        model_c = getattr(self.model, "classes", None) or getattr(self.model, "num_labels", None) or self.n_classes
+        if int(model_c) != len(self.classes) or self.n_classes != len(self.classes):
+            raise ValueError(f"the model has {model_c} classes (config n_classes {self.n_classes}), config['classes'] lists "
+                             f"{len(self.classes)}")
 
     def _fast_preds(self, mode: int) -> bool:
         """'argmax' output from a U-Net in eval mode: class and probability leave the head convolution's epilogue, the logits
@@ -304,7 +324,10 @@ class ZoneDetector:
         return logits
 
     @torch.no_grad()
-    def run(self, raster_u8: torch.Tensor) -> torch.Tensor:
+    def run(self, raster_u8: torch.Tensor, truth_u8: torch.Tensor = None) -> torch.Tensor:
+        """The output raster.  With ``truth_u8`` ((H, W) uint8 label raster on the device) the run also leaves
+        ``window_confmats`` / ``window_rects``: each window's confusion matrix over its margin-cropped core against
+        truth - 1, from the window's own prediction (exact clipping) or from the finished raster (overlap methods)."""
         if not raster_u8.is_cuda or raster_u8.dtype != torch.uint8 or raster_u8.dim() != 3:
             raise RuntimeError("raster must be a (bands, H, W) uint8 tensor on the HIP device")
         raster_u8 = raster_u8.contiguous()
@@ -312,6 +335,15 @@ class ZoneDetector:
         dev = raster_u8.device
         grid_np = tile_grid((Wr, Hr), self.S, self.margin, self.stride)
         grid = torch.from_numpy(grid_np).to(dev)
+        confmats, self.window_confmats, self.window_rects = None, None, None
+        if truth_u8 is not None:
+            self._check_truth(truth_u8, Hr, Wr)
+            truth_u8 = truth_u8.contiguous()
+            C = self.n_classes
+            confmats = torch.zeros(len(grid_np), C, C, dtype=torch.int64, device=dev)
+            K = self.S - 2 * self.margin
+            self.window_rects = np.stack([grid_np[:, 0] + self.margin, grid_np[:, 1] + self.margin, np.full(len(grid_np), K),
+                                          np.full(len(grid_np), K)], axis=1).astype(np.int32)
         mode = OUTPUT_TYPES[self.output_type]
         blend = (OverlapStitch(self.blend, grid_np, self.S, self.margin, self.n_classes, Hr, Wr, dev) if self.blend else None)
         if blend is not None:
@@ -338,11 +370,29 @@ class ZoneDetector:
                 preds, prob = self.model.predict_classes(imgs, want_prob=True)
                 L.check(L.lib().flair_detect_stitch_preds(L.ptr(preds), L.ptr(prob), B, self.S, self.margin, L.ptr(tiles), L.ptr(out),
                                                           Hr, Wr, L.stream()), "flair_detect_stitch_preds")
+                if confmats is not None:
+                    L.check(L.lib().flair_zone_window_confmat_preds(L.ptr(preds), B, self.n_classes, self.S, self.margin, L.ptr(tiles),
+                                                                    L.ptr(truth_u8), Hr, Wr, L.ptr(confmats[b0:b0 + B]), L.stream()),
+                            "flair_zone_window_confmat_preds")
                 continue
             logits = self._logits(imgs)
             L.check(L.lib().flair_detect_stitch(L.ptr(logits), B, self.n_classes, self.S, self.margin, mode, L.ptr(tiles),
                                                 L.ptr(out), Hr, Wr, L.stream()), "flair_detect_stitch")
-        return blend.finish() if blend is not None else out
+            if confmats is not None:
+                L.check(L.lib().flair_zone_window_confmat_logits(L.ptr(logits), B, self.n_classes, self.S, self.margin, L.ptr(tiles),
+                                                                 L.ptr(truth_u8), Hr, Wr, L.ptr(confmats[b0:b0 + B]), L.stream()),
+                        "flair_zone_window_confmat_logits")
+        if blend is not None:
+            out = blend.finish()
+            if confmats is not None:   # an overlap method's window is scored on the finished raster
+                for b0 in range(0, len(grid_np), _MAX_GRID_Y):
+                    B = min(_MAX_GRID_Y, len(grid_np) - b0)
+                    L.check(L.lib().flair_zone_window_confmat_raster(L.ptr(out), B, self.n_classes, self.S, self.margin,
+                                                                     L.ptr(grid[b0:b0 + B]), L.ptr(truth_u8), Hr, Wr,
+                                                                     L.ptr(confmats[b0:b0 + B]), L.stream()),
+                            "flair_zone_window_confmat_raster")
+        self.window_confmats = confmats
+        return out
 
 
 def compare(model, config: dict, raster_u8: torch.Tensor) -> dict:

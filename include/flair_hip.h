@@ -191,6 +191,32 @@ int flair_detect_stitch_max(const float* logits_nchw, int B, int C, int S, int m
 int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
                                   int x_lo, int x_hi, int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
 
+/* zone_detect's comparison metrics against a ground-truth raster (src/zone_detect/test/metrics.py; csrc/zone_metrics.hip).
+ * truth_u8 (raster_h, raster_w): the stored label raster; its class is (truth - 1) in uint8 arithmetic, so a 0 becomes 255.
+ * Every count is sklearn's confusion_matrix(truth - 1, pred, labels=range(C)): rows truth, columns prediction, pairs with a
+ * member outside range(C) dropped.  Matrices are int64 and ADDED to (callers zero them); C <= 32.
+ * flair_zone_window_confmat_*: confmats (B, C, C), one per window b over its margin-cropped core
+ *   [x0+m, x0+S-m) x [y0+m, y0+S-m) clipped to the raster (tiles as flair_detect_stitch; only x0, y0 are read), the prediction
+ *   being the window's own u8 class tile (B, S, S) (_preds), the class flair_detect_stitch writes from its fp32 logits
+ *   (B, C, S, S) (_logits), or band 0 of the finished fp32 raster (2, raster_h, raster_w) (_raster).
+ * flair_zone_raster_confmat: confmat (C, C) of band 0 of the fp32 raster (2, raster_h, raster_w) over the whole raster.
+ * flair_zone_error_map: error_rate_patch (metrics.py:350-442) of band 0: for the n_rows x n_cols patches at
+ *   (row_origins[a], col_origins[b]) (device int32; each patch K x K inside the raster), the mean over patches of the K x K map
+ *   [truth - 1 != class] (no-data counts as an error), then scipy.ndimage.gaussian_filter(., sigma, mode='reflect') with
+ *   truncate radius `radius` (<= 32), in fp64 -> error_map (K, K).  Workspaces: mask_ws raster_h * raster_w bytes,
+ *   colsum_ws raster_h * K int32, counts_ws K * K int32, tmp_ws K * K fp64. */
+int flair_zone_window_confmat_preds(const uint8_t* preds_u8, int B, int C, int S, int margin, const int32_t* tiles,
+                                    const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream);
+int flair_zone_window_confmat_logits(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles,
+                                     const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream);
+int flair_zone_window_confmat_raster(const float* raster, int B, int C, int S, int margin, const int32_t* tiles, const uint8_t* truth_u8,
+                                     int raster_h, int raster_w, int64_t* confmats, void* stream);
+int flair_zone_raster_confmat(const float* raster, const uint8_t* truth_u8, int raster_h, int raster_w, int C, int64_t* confmat,
+                              void* stream);
+int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raster_h, int raster_w, int K, const int32_t* row_origins,
+                         int n_rows, const int32_t* col_origins, int n_cols, double sigma, int radius, uint8_t* mask_ws,
+                         int32_t* colsum_ws, int32_t* counts_ws, double* tmp_ws, double* error_map, void* stream);
+
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream);
