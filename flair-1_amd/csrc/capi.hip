@@ -5,6 +5,7 @@
 #include "../../include/flair_hip.h"
 #include "unet.h"
 #include "segformer.h"
+#include "upernet.h"
 
 using namespace flair;
 
@@ -14,6 +15,12 @@ struct flair_unet { UNet net; flair_unet(int a, int b, int c) : net(a, b, c) {} 
 struct flair_segformer {
   SegFormer net;
   flair_segformer(int a, int b, const int* d, const int* h, const int* hd, const int* sr, int dh, int dt) : net(a, b, d, h, hd, sr, dh, dt) {}
+};
+
+struct flair_upernet {
+  UperNet net;
+  flair_upernet(int a, int b, int e, const int* d, const int* h, int hid, const int* ps, int ai, int ac, int dt)
+      : net(a, b, e, d, h, hid, ps, ai, ac, dt) {}
 };
 
 extern "C" {
@@ -33,6 +40,7 @@ const char* flair_strerror(int code) {
     case -11: return "call order: backward / stage call without the matching forward on this workspace";
     case -12: return "gradient buffer already initialised";
     case -13: return "internal side stream: event record / wait failed";
+    case -14: return "UperNet-Swin tile size: height and width must be multiples of 32 from 64 to 2048";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -472,6 +480,51 @@ int flair_segformer_forward(flair_segformer_t* h, const float* params, const flo
                             float* logits_full_nchw, int B, int H, int W, void* ws, size_t wsb, void* stream) {
   if (!h) return -1;
   return h->net.forward(params, x_nchw, logits_quarter_nchw, logits_full_nchw, B, H, W, ws, wsb, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------ UperNet-Swin (HuggingFace provider)
+int flair_upernet_create(flair_upernet_t** out, int in_channels, int num_labels, int embed_dim, const int depths[4], const int num_heads[4],
+                         int window_size, int hidden_size, const int pool_scales[4], int auxiliary_in_channels, int auxiliary_channels,
+                         int dtype) {
+  if (!out || !depths || !num_heads || !pool_scales || in_channels < 1 || num_labels < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  if (window_size != 7) return -2;   // the attention kernel's 7 x 7 windows (swin-tiny / -small)
+  if (embed_dim < 32 || (embed_dim % 32)) return -2;
+  for (int i = 0; i < 4; ++i)
+    if (depths[i] < 1 || num_heads[i] * 32 != (embed_dim << i) || pool_scales[i] < 1 || pool_scales[i] > 64) return -2;   // heads of 32
+  if (hidden_size < 64 || (hidden_size % 64) || auxiliary_in_channels < 1 || auxiliary_channels < 1) return -2;
+  flair_upernet* h = new (std::nothrow) flair_upernet(in_channels, num_labels, embed_dim, depths, num_heads, hidden_size, pool_scales,
+                                                      auxiliary_in_channels, auxiliary_channels, dtype);
+  if (!h) return -100;
+  *out = h;
+  return 0;
+}
+void flair_upernet_destroy(flair_upernet_t* h) { delete h; }
+int64_t flair_upernet_param_count(const flair_upernet_t* h) { return h ? h->net.n_params : -1; }
+int flair_upernet_num_tensors(const flair_upernet_t* h) { return h ? (int)h->net.tensors.size() : -1; }
+int flair_upernet_tensor_info(const flair_upernet_t* h, int i, char* name, int name_cap, int64_t shape[4], int* ndim, int64_t* offset,
+                              int* kind) {
+  if (!h || i < 0 || i >= (int)h->net.tensors.size() || !name || name_cap < 2) return -1;
+  const SfTensor& t = h->net.tensors[i];
+  strncpy(name, t.name.c_str(), name_cap - 1);
+  name[name_cap - 1] = 0;
+  for (int d = 0; d < 4; ++d) shape[d] = t.shape[d];
+  *ndim = t.ndim; *offset = t.offset; *kind = t.kind;
+  return 0;
+}
+int64_t flair_upernet_workspace_bytes(flair_upernet_t* h, int B, int H, int W) {
+  if (!h || B < 1) return -1;
+  if (!UperNet::shape_ok(H, W)) return -14;
+  return (int64_t)h->net.workspace_bytes(B, H, W);
+}
+void flair_upernet_weights_changed(flair_upernet_t* h) {
+  if (h) h->net.weights_changed();
+}
+int flair_upernet_forward(flair_upernet_t* h, const float* params, const float* x_nchw, float* logits_nchw, int B, int H, int W, void* ws,
+                          size_t wsb, void* stream) {
+  if (!h) return -1;
+  if (!UperNet::shape_ok(H, W)) return -14;
+  return h->net.forward(params, x_nchw, logits_nchw, B, H, W, ws, wsb, (hipStream_t)stream);
 }
 
 }  // extern "C"

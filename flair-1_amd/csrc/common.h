@@ -161,7 +161,8 @@ struct ConvArgs {
   const void* acc_src;
   // with bnr_partial: store dz * m (m = the ReLU mask the fused reduction computes anyway) instead of dz, so that the consumers
   // of this gradient need no mask source (halo-GEMM epilogue only)
-  int bnr_mask;
+  int bnr_mask;  // optional exact (erf) GELU on the output, after the bias: the fc1 of a Swin MLP (gather-form kernel only, NHWC output)
+  int ogelu;
 };
 bool conv_bnapply_fusable(int dtype, const ConvArgs& a);   // a.ap_y set: will launch_conv run the halo-GEMM kernel that applies it?
 bool conv_acc_src_ok(int dtype, const ConvArgs& a);        // a.acc_src set: does the kernel launch_conv picks honour it?

@@ -264,9 +264,13 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
           mo = ((long)img * 2 * a.Hout + 2 * ho + c_oy) * (2 * a.Wout) + 2 * wo + c_ox;
         }
         T* dst = out + mo * a.out_ld + n;
-        if (a.ores || a.orelu) {
+        if (a.ores || a.orelu || a.ogelu) {
           float fa[CH];
           chunk_to_f<T>(v, fa);
+          if (a.ogelu) {
+#pragma unroll
+            for (int e = 0; e < CH; ++e) fa[e] = 0.5f * fa[e] * (1.f + erff(fa[e] * 0.70710678118654752f));
+          }
           if (a.ores) {
             float fb[CH];
             chunk_to_f<T>(*reinterpret_cast<const uint4*>((const T*)a.ores + mo * a.out_ld + n), fb);
@@ -418,6 +422,9 @@ int launch_conv(int dtype, const ConvArgs& a, hipStream_t s) {
   if ((a.ap_y || a.acc_src || a.bnr_mask) && !conv_hg_applicable(dtype, a)) return -6;
   if (a.acc_src && !conv_acc_src_ok(dtype, a)) return -6;
   if (a.bnr_mask && !a.bnr_partial) return -6;
+  // the GELU epilogue exists in the gather-form kernel only
+  if (a.ogelu && (!a.out || a.out_nchw || a.in_scale || conv_stem_applicable(dtype, a) || conv_hg_applicable(dtype, a) || conv_halo_applicable(a)))
+    return -6;
   if (a.in_scale) {   // lazy BN + ReLU on the input: the halo-GEMM (>= 64 channels) and the small-channel halo kernel apply it
     if (conv_hg_applicable(dtype, a)) return (a.pool_c0 > 0 || a.bnr_partial) ? -6 : launch_conv_hg(dtype, a, s);
     if (!conv_halo_applicable(a) || (a.pool_c0 > 0 && !conv_tile_epilogue_ok(dtype, a))) return -6;

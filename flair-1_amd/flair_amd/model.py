@@ -7,7 +7,8 @@ Same constructor argument (the YAML config dict), same attributes (``seg_model``
   * the metadata broadcast ``x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16)`` + ``torch.add``
     (model.py:59-60; element [b,c,h,w] += x_enc[b,h]) runs as one in-place HIP kernel on a copy of feats[-1]
     instead of materialising the (B,512,16,16) repeat;
-  * the HuggingFace provider branch (model.py:43-50,66-68) is outside the hot path and raises.
+  * the HuggingFace provider branch (model.py:43-50,66-68) builds SegFormer-MiT and 3-channel UperNet-Swin natively
+    (inference only); other names raise.
 """
 from __future__ import annotations
 
@@ -121,14 +122,26 @@ class FLAIR_ModelFactory(nn.Module):
                                           in_channels=n_channels, **kw)
         elif self.model_provider == "HuggingFace":
             # model.py:43-50: AutoModelForSemanticSegmentation.from_pretrained(org_model, num_labels=...).  No hub here: the
-            # SegFormer family (BASELINE config 5) is built natively from its published geometry, weights arrive through
-            # load_state_dict; anything else raises.  Inference only.
+            # SegFormer family (BASELINE config 5) and UperNet-Swin-tiny / -small are built natively from their published
+            # geometry, weights arrive through load_state_dict; anything else raises.  Inference only.
             from .segformer import SegformerForSemanticSegmentation, config_for
+            from .upernet import UperNetForSemanticSegmentation, config_for_upernet
             hf = config["model_framework"]["HuggingFace"]
-            kw = config_for(hf["org_model"])
-            kw.update({k: hf[k] for k in ("depths", "decoder_hidden_size") if k in hf})
-            self.seg_model = SegformerForSemanticSegmentation(num_channels=n_channels, num_labels=n_classes,
-                                                              compute_dtype=compute_dtype, **kw)
+            if "upernet" in hf["org_model"].lower():
+                # UperNet-Swin (the provider's default, openmmlab/upernet-swin-small): the reference builds it from the hub config,
+                # whose backbone takes 3 input channels, and never passes num_channels (quirk Q11) — any other band count fails in
+                # its first forward.  Built here for exactly that case.
+                kw = config_for_upernet(hf["org_model"])
+                if n_channels != 3:
+                    raise NotImplementedError(
+                        f"{hf['org_model']!r} with {n_channels} channels: the reference builds this model with the hub config's 3 "
+                        "input channels; build flair_amd.UperNetForSemanticSegmentation(num_channels=...) directly for other band counts")
+                self.seg_model = UperNetForSemanticSegmentation(num_channels=3, num_labels=n_classes, compute_dtype=compute_dtype, **kw)
+            else:
+                kw = config_for(hf["org_model"])
+                kw.update({k: hf[k] for k in ("depths", "decoder_hidden_size") if k in hf})
+                self.seg_model = SegformerForSemanticSegmentation(num_channels=n_channels, num_labels=n_classes,
+                                                                  compute_dtype=compute_dtype, **kw)
 
     def forward(self, x, met=None):
         if self.use_metadata == True and self.model_provider == "SegmentationModelsPytorch":  # noqa: E712

@@ -301,6 +301,30 @@ int flair_segformer_forward(flair_segformer_t* h, const float* params, const flo
                             float* logits_full_nchw, int B, int H, int W, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * UperNet with a Swin backbone (upernet-swin-tiny / -small), inference only: the HuggingFace provider's default model
+ * (`openmmlab/upernet-swin-small` in the reference's configs).  Replaces transformers' UperNetForSemanticSegmentation.forward
+ * in eval mode; the auxiliary head's tensors are in the table and are never computed.  Tensor names / shapes
+ * (flair_upernet_tensor_info) are that library's state_dict keys (transformers 5.x names); every tensor, BatchNorm running
+ * statistics included (kind 1), lives in ONE flat fp32 buffer.  Geometry: window 7, heads of 32 channels; H, W multiples of
+ * 32 from 64 to 2048 (other sizes: -14). */
+typedef struct flair_upernet flair_upernet_t;
+int flair_upernet_create(flair_upernet_t** out, int in_channels, int num_labels, int embed_dim, const int depths[4],
+                         const int num_heads[4], int window_size, int hidden_size, const int pool_scales[4],
+                         int auxiliary_in_channels, int auxiliary_channels, int dtype);
+void flair_upernet_destroy(flair_upernet_t* h);
+int64_t flair_upernet_param_count(const flair_upernet_t* h);
+int flair_upernet_num_tensors(const flair_upernet_t* h);
+int flair_upernet_tensor_info(const flair_upernet_t* h, int i, char* name, int name_cap, int64_t shape[4], int* ndim,
+                              int64_t* offset, int* kind);
+int64_t flair_upernet_workspace_bytes(flair_upernet_t* h, int B, int H, int W);
+/* as flair_segformer_weights_changed: the packed weights and folded BatchNorm at the front of the workspace are reused
+ * while `params` and `workspace` are the same pointers; call this after changing the parameter buffer's contents in place */
+void flair_upernet_weights_changed(flair_upernet_t* h);
+/* logits_nchw: fp32 (B, labels, H, W) = the library's `.logits` (already resized to the input size) */
+int flair_upernet_forward(flair_upernet_t* h, const float* params, const float* x_nchw, float* logits_nchw, int B, int H, int W,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostic tuning switch (kernel-variant A/B timing inside one process; keys are the FLAIR_* environment
  * variables DESIGN.md lists, the environment supplies the default).  Returns 0. */
 int flair_tune_set(const char* key, int value);
