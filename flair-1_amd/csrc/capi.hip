@@ -343,6 +343,9 @@ int flair_conv2d_forward(int dtype, const void* x0, const void* x1, int N, int H
   a.Hout = (a.Hin + 2 * pad - R) / stride + 1; a.Wout = (a.Win + 2 * pad - R) / stride + 1;
   a.R = R; a.S = R; a.out_mul = stride; a.pad = pad; a.in_div = 1; a.Cout = Cout; a.Kg = Kg; a.Kpad = Kpad; a.w = wp;
   a.bias = bias; a.out = y_nhwc; a.out_ld = Cout; a.out_nchw = y_nchw;
+  // the row count must be that of the kernel launch_conv picks WITH statistics on (bf16 32 -> 128: the multi-block persistent
+  // kernel writes none and has a capped grid; the per-tile kernel that runs instead has one row per tile)
+  a.stats = stats;
   const int nblk = conv_grid_rows(dtype, a);
   float* partial = stats ? (float*)ar.get((size_t)nblk * 2 * Cout * 4) : nullptr;
   a.stats = partial;
@@ -387,6 +390,110 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
     rc = launch_wgrad(dtype, w, s);
   }
   return rc;
+}
+
+// ---- the fused forms of the same launchers (plain structs in, ConvArgs / WgradArgs out; no kernel differs)
+static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a, int& Cin, int& rows_f) {
+  if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
+  if (p->mode != 0 && p->mode != 1) return -2;
+  if (p->mode == 1 && p->stride != 1) return -6;   // the parity-class stride-2 data gradient packs its weights in unet.hip
+  memset(&a, 0, sizeof(a));
+  int Kg, Kpad;
+  conv_geom(p->dtype, p->C0, p->x1 ? p->C1 : 0, p->Cout, p->R, Cin, Kg, Kpad, rows_f);
+  a.src0 = p->x0; a.src1 = p->x1; a.C0 = p->C0; a.C1 = p->x1 ? p->C1 : 0; a.up0 = p->up0; a.N = p->N;
+  a.Hin = p->up0 ? 2 * p->H : p->H; a.Win = p->up0 ? 2 * p->W : p->W;
+  const int pad = p->mode == 1 ? p->R - 1 - p->pad : p->pad;
+  a.Hout = (a.Hin + 2 * pad - p->R) / p->stride + 1; a.Wout = (a.Win + 2 * pad - p->R) / p->stride + 1;
+  a.R = p->R; a.S = p->R; a.out_mul = p->stride; a.pad = pad; a.in_div = 1; a.Cout = p->Cout; a.Kg = Kg; a.Kpad = Kpad;
+  a.bias = p->bias; a.out = p->y_nhwc; a.out_ld = p->out_ld > 0 ? p->out_ld : p->Cout; a.out_nchw = p->y_nchw;
+  a.in_scale = p->in_scale; a.in_shift = p->in_shift;
+  a.oscale = p->oscale; a.oshift = p->oshift; a.ores = p->ores; a.orelu = p->orelu;
+  a.accumulate = p->accumulate; a.acc_src = p->acc_src;
+  a.pool_c0 = p->pool_c0; a.out_skip = p->out_skip; a.out_skip_ld = p->out_skip_ld; a.skip_accumulate = p->skip_accumulate;
+  a.preds_u8 = p->preds_u8; a.maxprob_f32 = p->maxprob_f32;
+  return 0;
+}
+
+size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p) {
+  ConvArgs a;
+  int Cin, rows_f;
+  if (!p || conv_ex_fill(p, a, Cin, rows_f)) return 0;
+  a.w = p;  // (non-null: the dispatch predicates only look at which pointers are set)
+  a.stats = p->stats;
+  size_t b = (size_t)round_up((long)((size_t)rows_f * a.Kpad * dtype_size(p->dtype)), 256);
+  if (p->stats) b += (size_t)round_up((long)conv_grid_rows(p->dtype, a) * 2 * p->Cout * 4, 256);
+  return b + 256;
+}
+
+int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void* stream) {
+  if (!p || !p->x0 || !p->w_oihw || !workspace) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  ConvArgs a;
+  int Cin, rows_f;
+  int rc = conv_ex_fill(p, a, Cin, rows_f);
+  if (rc) return rc;
+  OpArena ar(workspace, wsb);
+  void* wp = ar.get((size_t)rows_f * a.Kpad * dtype_size(p->dtype));
+  a.w = wp;
+  float* partial = nullptr;
+  int nblk = 0;
+  if (p->stats) {
+    a.stats = p->stats;   // (so that the row count is that of the kernel launch_conv picks with statistics on)
+    nblk = conv_grid_rows(p->dtype, a);
+    partial = (float*)ar.get((size_t)nblk * 2 * p->Cout * 4);
+    a.stats = partial;
+  }
+  if (ar.bad) return -100;
+  // mode 1: w_oihw is the forward layer's [C0][Cout][R][R]; the data gradient multiplies by its transposed, flipped pack
+  rc = p->mode == 1 ? pack_weight(p->dtype, p->w_oihw, wp, Cin, p->Cout, p->R, p->R, Cin, rows_f, a.Kpad, 1, s)
+                    : pack_weight(p->dtype, p->w_oihw, wp, p->Cout, Cin, p->R, p->R, Cin, rows_f, a.Kpad, 0, s);
+  if (rc) return rc;
+  rc = launch_conv(p->dtype, a, s);
+  if (rc) return rc;
+  if (p->stats) rc = partial_rows_sum(partial, nblk, 2 * p->Cout, p->stats, s);
+  return rc;
+}
+
+static int wgrad_ex_fill(const flair_wgrad_ex_t* p, WgradArgs& w) {
+  if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
+  memset(&w, 0, sizeof(w));
+  w.x0 = p->x0; w.x1 = p->x1; w.C0 = p->C0; w.C1 = p->x1 ? p->C1 : 0; w.up0 = p->up0; w.N = p->N;
+  w.Hin = p->up0 ? 2 * p->H : p->H; w.Win = p->up0 ? 2 * p->W : p->W;
+  w.Hout = (w.Hin + 2 * p->pad - p->R) / p->stride + 1; w.Wout = (w.Win + 2 * p->pad - p->R) / p->stride + 1;
+  w.R = p->R; w.S = p->R; w.stride = p->stride; w.pad = p->pad;
+  w.dy = p->dy; w.dy_ld = p->dy_ld > 0 ? p->dy_ld : p->Cout; w.Cout = p->Cout; w.dw = p->dw;
+  w.Cin_real = p->Cin_real > 0 ? p->Cin_real : w.C0 + w.C1;
+  w.accumulate = p->accumulate; w.in_scale = p->in_scale; w.in_shift = p->in_shift; w.cus = p->cus; w.dbias = p->dbias;
+  return 0;
+}
+
+size_t flair_conv2d_wgrad_ex_workspace_bytes(const flair_wgrad_ex_t* p) {
+  WgradArgs w;
+  if (!p || wgrad_ex_fill(p, w)) return 0;
+  size_t b = (size_t)round_up((long)wgrad_workspace_bytes(p->dtype, w), 256);
+  if (p->dbias && wgrad_dbias_fusable(p->dtype, w)) b += (size_t)round_up((long)WGRAD_DBIAS_ROWS * w.dy_ld * 4, 256);
+  return b + 256;
+}
+
+int flair_conv2d_wgrad_ex(const flair_wgrad_ex_t* p, void* workspace, size_t wsb, void* stream) {
+  if (!p || !p->x0 || !p->dy || !p->dw || !workspace) return -1;
+  WgradArgs w;
+  int rc = wgrad_ex_fill(p, w);
+  if (rc) return rc;
+  OpArena ar(workspace, wsb);
+  w.partial = (float*)ar.get(wgrad_workspace_bytes(p->dtype, w));
+  if (p->dbias && wgrad_dbias_fusable(p->dtype, w)) w.dbias_partial = (float*)ar.get((size_t)WGRAD_DBIAS_ROWS * w.dy_ld * 4);
+  if (ar.bad) return -100;
+  return launch_wgrad(p->dtype, w, (hipStream_t)stream);
+}
+
+// partial block sums + the per-channel coefficient rows of either direction (what the two calls below carve out of `workspace`)
+size_t flair_bn_workspace_bytes(int64_t rows, int C) {
+  if (rows < 1 || C < 1) return 0;
+  const size_t partial = (size_t)round_up((long)bn_bwd_blocks(rows) * 2 * C * 4, 256);
+  const size_t fwd = 2 * (size_t)round_up((long)C * 4, 256) + partial + (size_t)round_up(2L * C * 4, 256);
+  const size_t bwd = partial + (size_t)round_up(3L * C * 4, 256);
+  return (fwd > bwd ? fwd : bwd) + 256;
 }
 
 int flair_bn_relu_forward(int dtype, const void* y, int64_t rows, int C, const float* gamma, const float* beta,

@@ -60,6 +60,11 @@ PROTOTYPES = {
     "flair_conv2d_forward": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp,
                                    vp, sz, vp]),
     "flair_conv2d_backward": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "flair_conv2d_ex_workspace_bytes": (sz, [vp]),
+    "flair_conv2d_ex": (i32, [vp, vp, sz, vp]),
+    "flair_conv2d_wgrad_ex_workspace_bytes": (sz, [vp]),
+    "flair_conv2d_wgrad_ex": (i32, [vp, vp, sz, vp]),
+    "flair_bn_workspace_bytes": (sz, [i64, i32]),
     "flair_bn_relu_forward": (i32, [i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "flair_bn_relu_backward": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "flair_maxpool_forward": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -103,6 +108,27 @@ PROTOTYPES = {
     "flair_tune_set": (i32, [C.c_char_p, i32]),
     "flair_debug_buffer": (i32, [vp]),
 }
+
+
+class ConvEx(C.Structure):
+    """flair_conv_ex_t"""
+    _fields_ = [("dtype", i32), ("mode", i32), ("x0", vp), ("x1", vp),
+                ("N", i32), ("H", i32), ("W", i32), ("C0", i32), ("C1", i32), ("up0", i32),
+                ("w_oihw", vp), ("bias", vp), ("Cout", i32), ("R", i32), ("stride", i32), ("pad", i32),
+                ("y_nhwc", vp), ("out_ld", i32), ("y_nchw", vp), ("stats", vp),
+                ("in_scale", vp), ("in_shift", vp), ("oscale", vp), ("oshift", vp), ("ores", vp), ("orelu", i32),
+                ("accumulate", i32), ("acc_src", vp),
+                ("pool_c0", i32), ("out_skip", vp), ("out_skip_ld", i32), ("skip_accumulate", i32),
+                ("preds_u8", vp), ("maxprob_f32", vp)]
+
+
+class WgradEx(C.Structure):
+    """flair_wgrad_ex_t"""
+    _fields_ = [("dtype", i32), ("x0", vp), ("x1", vp),
+                ("N", i32), ("H", i32), ("W", i32), ("C0", i32), ("C1", i32), ("up0", i32),
+                ("dy", vp), ("dy_ld", i32), ("Cout", i32), ("R", i32), ("stride", i32), ("pad", i32),
+                ("dw", vp), ("Cin_real", i32), ("accumulate", i32), ("in_scale", vp), ("in_shift", vp),
+                ("dbias", vp), ("cus", i32)]
 
 
 class FlairHipError(RuntimeError):

@@ -68,13 +68,76 @@ def conv2d_backward(x, w, dy, stride=1, pad=1, need_dx=True, need_dw=True):
     return dx, dw
 
 
+def conv2d_ex(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, want_nhwc=True, want_nchw=False, want_stats=False,
+              in_scale=None, in_shift=None, oscale=None, oshift=None, ores=None, orelu=False, out=None, accumulate=False,
+              acc_src=None, pool_c0=0, out_skip=None, skip_accumulate=False, want_preds=False, want_maxprob=False):
+    """flair_conv2d_ex: the fused forms of the convolution launcher.  mode 0: forward, w = [Cout][C0 + C1][R][R]; mode 1: stride-1
+    data gradient, x0 = dy, w = the forward layer's [C0][Cout][R][R].  `out` (NHWC, optional) is the tensor accumulated into / written;
+    with pool_c0 it is [N][H/2][W/2][pool_c0] and out_skip [N][H][W][Cout - pool_c0].
+    Returns a dict: y, out_skip, y_nchw, stats, preds, maxprob (absent outputs None)."""
+    import ctypes as C
+    N, H, W, C0 = x0.shape
+    C1 = x1.shape[3] if x1 is not None else 0
+    R = w.shape[2]
+    Cout = w.shape[1] if mode == 1 else w.shape[0]
+    assert (w.shape[0] if mode == 1 else w.shape[1]) == C0 + C1
+    dt = _dt(x0)
+    Hin, Win = (2 * H, 2 * W) if up0 else (H, W)
+    p_eff = R - 1 - pad if mode == 1 else pad
+    Ho, Wo = (Hin + 2 * p_eff - R) // stride + 1, (Win + 2 * p_eff - R) // stride + 1
+    dev = x0.device
+    if out is None and want_nhwc:
+        assert not accumulate or acc_src is not None, "accumulate needs the tensor to add to"
+        out = (torch.empty(N, Ho // 2, Wo // 2, pool_c0, dtype=x0.dtype, device=dev) if pool_c0 else
+               torch.empty(N, Ho, Wo, Cout, dtype=x0.dtype, device=dev))
+    if pool_c0 and pool_c0 < Cout and out_skip is None:
+        assert not skip_accumulate
+        out_skip = torch.empty(N, Ho, Wo, Cout - pool_c0, dtype=x0.dtype, device=dev)
+    yn = torch.empty(N, Cout, Ho, Wo, dtype=torch.float32, device=dev) if want_nchw else None
+    st = torch.empty(2, Cout, dtype=torch.float32, device=dev) if want_stats else None
+    pr = torch.empty(N, Ho, Wo, dtype=torch.uint8, device=dev) if want_preds else None
+    mp = torch.empty(N, Ho, Wo, dtype=torch.float32, device=dev) if want_maxprob else None
+    a = L.ConvEx(dtype=dt, mode=mode, x0=L.ptr(x0), x1=L.ptr(x1), N=N, H=H, W=W, C0=C0, C1=C1, up0=int(up0), w_oihw=L.ptr(w),
+                 bias=L.ptr(bias), Cout=Cout, R=R, stride=stride, pad=pad, y_nhwc=L.ptr(out),
+                 out_ld=out.shape[3] if out is not None else 0, y_nchw=L.ptr(yn), stats=L.ptr(st), in_scale=L.ptr(in_scale),
+                 in_shift=L.ptr(in_shift), oscale=L.ptr(oscale), oshift=L.ptr(oshift), ores=L.ptr(ores), orelu=int(orelu),
+                 accumulate=int(accumulate), acc_src=L.ptr(acc_src), pool_c0=pool_c0, out_skip=L.ptr(out_skip),
+                 out_skip_ld=out_skip.shape[3] if out_skip is not None else 0, skip_accumulate=int(skip_accumulate),
+                 preds_u8=L.ptr(pr), maxprob_f32=L.ptr(mp))
+    l = L.lib()
+    ws = _ws(l.flair_conv2d_ex_workspace_bytes(C.addressof(a)), dev)
+    L.check(l.flair_conv2d_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream()), "conv2d_ex")
+    return {"y": out, "out_skip": out_skip, "y_nchw": yn, "stats": st, "preds": pr, "maxprob": mp}
+
+
+def conv2d_wgrad_ex(x0, dy, Cout, R=3, stride=1, pad=1, x1=None, up0=False, in_scale=None, in_shift=None, dw=None, accumulate=False,
+                    want_dbias=False, cus=0, cin_real=0):
+    """flair_conv2d_wgrad_ex: dw (and the fused dbias) of conv(cat([up2(x0)?, x1])) against dy [N][Ho][Wo][dy_ld >= Cout]."""
+    import ctypes as C
+    N, H, W, C0 = x0.shape
+    C1 = x1.shape[3] if x1 is not None else 0
+    dt = _dt(x0)
+    dev = x0.device
+    if dw is None:
+        assert not accumulate
+        dw = torch.empty(Cout, cin_real or (C0 + C1), R, R, dtype=torch.float32, device=dev)
+    db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dbias else None
+    a = L.WgradEx(dtype=dt, x0=L.ptr(x0), x1=L.ptr(x1), N=N, H=H, W=W, C0=C0, C1=C1, up0=int(up0), dy=L.ptr(dy), dy_ld=dy.shape[3],
+                  Cout=Cout, R=R, stride=stride, pad=pad, dw=L.ptr(dw), Cin_real=cin_real, accumulate=int(accumulate),
+                  in_scale=L.ptr(in_scale), in_shift=L.ptr(in_shift), dbias=L.ptr(db), cus=cus)
+    l = L.lib()
+    ws = _ws(l.flair_conv2d_wgrad_ex_workspace_bytes(C.addressof(a)), dev)
+    L.check(l.flair_conv2d_wgrad_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream()), "conv2d_wgrad_ex")
+    return dw, db
+
+
 def bn_relu_forward(y, gamma, beta, running_mean, running_var, training=True, residual=None, relu=True):
     C = y.shape[-1]
     rows = y.numel() // C
     out = torch.empty_like(y)
     mean = torch.empty(C, dtype=torch.float32, device=y.device)
     invstd = torch.empty(C, dtype=torch.float32, device=y.device)
-    ws = _ws(1024 * 2 * C * 4 + 16 * C * 4 + 8192, y.device)
+    ws = _ws(L.lib().flair_bn_workspace_bytes(rows, C), y.device)
     L.check(L.lib().flair_bn_relu_forward(_dt(y), L.ptr(y), rows, C, L.ptr(gamma), L.ptr(beta), L.ptr(running_mean),
                                           L.ptr(running_var), int(training), L.ptr(residual), int(relu), L.ptr(out),
                                           L.ptr(mean), L.ptr(invstd), L.ptr(ws), ws.numel(), L.stream()), "bn_relu_forward")
@@ -88,7 +151,7 @@ def bn_relu_backward(dout, out, y, gamma, mean, invstd, relu=True, want_dres=Fal
     dres = torch.empty_like(y) if want_dres else None
     dgamma = torch.empty(C, dtype=torch.float32, device=y.device)
     dbeta = torch.empty(C, dtype=torch.float32, device=y.device)
-    ws = _ws(1024 * 2 * C * 4 + 16 * C * 4 + 8192, y.device)
+    ws = _ws(L.lib().flair_bn_workspace_bytes(rows, C), y.device)
     L.check(L.lib().flair_bn_relu_backward(_dt(y), L.ptr(dout), L.ptr(out), L.ptr(y), rows, C, L.ptr(gamma), L.ptr(mean),
                                            L.ptr(invstd), int(relu), L.ptr(dy), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta),
                                            L.ptr(ws), ws.numel(), L.stream()), "bn_relu_backward")

@@ -235,6 +235,54 @@ int flair_conv2d_forward(int dtype, const void* x0, const void* x1, int N, int H
 int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Cin, const float* w_oihw, int Cout, int R,
                           int stride, int pad, const void* dy_nhwc, void* dx_nhwc, float* dw_oihw, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* The fused forms of the two launchers above, as the network launches them: every option is a field of a plain struct
+ * (zero / NULL = off) that is copied into the launcher's arguments; no kernel differs.  The return value is the launcher's own:
+ * -6 where the kernel chosen for the shape does not implement a requested option.
+ * flair_conv2d_ex, mode 0: the forward of flair_conv2d_forward.  mode 1: the stride-1 data gradient — x0 is dy with C0 channels,
+ *   w_oihw the FORWARD layer's weights [C0][Cout][R][R], `pad` the forward padding, the output has Cout channels.
+ *   in_scale / in_shift [C0 + C1]: the input is relu(x * in_scale[c] + in_shift[c]) inside the image, zero in the padding.
+ *   oscale / oshift [Cout], ores (NHWC, as y_nhwc), orelu: y = [relu](acc * oscale + oshift (+ bias) (+ ores)).
+ *   accumulate: y_nhwc += result; with acc_src the addend is read from acc_src (NHWC, as y_nhwc) instead of y_nhwc.
+ *   pool_c0 > 0: output columns [0, pool_c0) are 2x2 sum-pooled into y_nhwc ([N][Ho/2][Wo/2][out_ld]), columns [pool_c0, Cout)
+ *     go to out_skip ([N][Ho][Wo][out_skip_ld]; += with skip_accumulate) — the backward of "nearest x2 upsample ++ skip".
+ *   out_ld: row stride of y_nhwc in elements (0 = Cout).  preds_u8 [N][Ho][Wo]: first argmax over the Cout outputs of a pixel,
+ *     maxprob_f32 its softmax probability; y_nhwc may then be NULL.
+ *   stats [2][Cout] as in flair_conv2d_forward.
+ * flair_conv2d_wgrad_ex: dw[Cout][Cin_real][R][R] (+= with accumulate) of the convolution over cat([up2(x0)?, x1]) (H, W: extent
+ *   of x0 as stored), lazy input as above, dy rows of dy_ld elements (0 = Cout), Cin_real = 0: C0 + C1.  dbias [Cout]: the column
+ *   sums of dy from the same kernel (16 -> <= 16 channel layers with dy_ld == 16; -6 elsewhere).  cus: workgroup budget of the
+ *   register-resident kernel (0 = default).
+ * Workspace: the _workspace_bytes call on the same struct (under the same flair_tune_set settings). */
+typedef struct flair_conv_ex {
+  int dtype, mode;
+  const void* x0; const void* x1;
+  int N, H, W, C0, C1, up0;
+  const float* w_oihw; const float* bias;
+  int Cout, R, stride, pad;
+  void* y_nhwc; int out_ld;
+  float* y_nchw; float* stats;
+  const float* in_scale; const float* in_shift;
+  const float* oscale; const float* oshift; const void* ores; int orelu;
+  int accumulate; const void* acc_src;
+  int pool_c0; void* out_skip; int out_skip_ld; int skip_accumulate;
+  uint8_t* preds_u8; float* maxprob_f32;
+} flair_conv_ex_t;
+typedef struct flair_wgrad_ex {
+  int dtype;
+  const void* x0; const void* x1;
+  int N, H, W, C0, C1, up0;
+  const void* dy; int dy_ld;
+  int Cout, R, stride, pad;
+  float* dw; int Cin_real; int accumulate;
+  const float* in_scale; const float* in_shift;
+  float* dbias; int cus;
+} flair_wgrad_ex_t;
+size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p);
+int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
+size_t flair_conv2d_wgrad_ex_workspace_bytes(const flair_wgrad_ex_t* p);
+int flair_conv2d_wgrad_ex(const flair_wgrad_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
+/* workspace of flair_bn_relu_forward / _backward for `rows` rows of C channels */
+size_t flair_bn_workspace_bytes(int64_t rows, int C);
 int flair_bn_relu_forward(int dtype, const void* y, int64_t rows, int C, const float* gamma, const float* beta,
                           float* running_mean, float* running_var, int training, const void* residual, int relu,
                           void* out, float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes,
