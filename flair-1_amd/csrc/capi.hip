@@ -6,6 +6,8 @@
 #include "unet.h"
 #include "segformer.h"
 #include "upernet.h"
+#include "segformer_ops.h"
+#include "swin_ops.h"
 
 using namespace flair;
 
@@ -410,7 +412,7 @@ static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a, int& Cin, int& ro
   a.oscale = p->oscale; a.oshift = p->oshift; a.ores = p->ores; a.orelu = p->orelu;
   a.accumulate = p->accumulate; a.acc_src = p->acc_src;
   a.pool_c0 = p->pool_c0; a.out_skip = p->out_skip; a.out_skip_ld = p->out_skip_ld; a.skip_accumulate = p->skip_accumulate;
-  a.preds_u8 = p->preds_u8; a.maxprob_f32 = p->maxprob_f32;
+  a.preds_u8 = p->preds_u8; a.maxprob_f32 = p->maxprob_f32; a.ogelu = p->ogelu;
   return 0;
 }
 
@@ -546,6 +548,100 @@ int flair_nchw_to_nhwc(int dtype, const float* x, void* y, int N, int C, int H, 
 int flair_nhwc_to_nchw(int dtype, const void* x, float* y, int N, int C, int H, int W, int Cpad, void* stream) {
   return nhwc_to_nchw_f32(dtype, x, y, N, C, H, W, Cpad, nullptr, (hipStream_t)stream);
 }
+
+// ---- the SegFormer / UperNet-Swin kernels one at a time: each forwards to the launcher the executors call
+#define FLAIR_DT_OK(dt) ((dt) == DT_F32 || (dt) == DT_BF16)
+int flair_sf_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, float eps, void* stream) {
+  if (!x || !gamma || !beta || !y || rows < 1 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_layernorm(dtype, x, gamma, beta, y, (long)rows, C, eps, (hipStream_t)stream);
+}
+int flair_sf_dwconv3x3_gelu(int dtype, const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, void* stream) {
+  if (!x || !w || !bias || !y || B < 1 || H < 1 || W < 1 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_dwconv3x3_gelu(dtype, x, w, bias, y, B, H, W, C, (hipStream_t)stream);
+}
+int flair_sf_bilinear_nhwc(int dtype, const void* x, void* y, int B, int h, int w, int C, int H, int W, int ld, void* stream) {
+  if (!x || !y || B < 1 || h < 1 || w < 1 || H < 1 || W < 1 || C < 1 || ld < C) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_bilinear_nhwc(dtype, x, y, B, h, w, C, H, W, ld, (hipStream_t)stream);
+}
+int flair_sf_bilinear_nchw_f32(const float* x, float* y, int64_t planes, int h, int w, int H, int W, void* stream) {
+  if (!x || !y || planes < 1 || h < 1 || w < 1 || H < 1 || W < 1) return -1;
+  return sf_bilinear_nchw_f32(x, y, (long)planes, h, w, H, W, (hipStream_t)stream);
+}
+int flair_sf_slice_cols(int dtype, const float* src, int ld, int col0, int ncols, int64_t rows, void* dst, void* stream) {
+  if (!src || !dst || rows < 1 || col0 < 0 || ncols < 1 || col0 + ncols > ld) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_slice_cols(dtype, src, ld, col0, ncols, (long)rows, dst, (hipStream_t)stream);
+}
+int flair_sf_fuse_bias(const float* wf, int D, const float* b3, const float* b2, const float* b1, const float* b0, const float* scale,
+                       const float* shift, float* shift2, void* stream) {
+  if (!wf || !b3 || !b2 || !b1 || !b0 || !scale || !shift || !shift2 || D < 1) return -1;
+  return sf_fuse_bias(wf, D, b3, b2, b1, b0, scale, shift, shift2, (hipStream_t)stream);
+}
+int flair_sf_upsample_sum_bn_relu(int dtype, const void* g0, const void* g1, const void* g2, const void* g3, const float* scale,
+                                  const float* shift2, void* z, int B, int H, int W, int D, void* stream) {
+  if (!g0 || !g1 || !g2 || !g3 || !scale || !shift2 || !z || B < 1 || H < 1 || W < 1 || D < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_upsample_sum_bn_relu(dtype, g0, g1, g2, g3, scale, shift2, z, B, H, W, D, (hipStream_t)stream);
+}
+int flair_sf_ffn_fused_ok(int dtype, int C, int H, int W) { return sf_ffn_fused_ok(dtype, C, H, W) ? 1 : 0; }
+int flair_sf_ffn_dw_pack(const float* w, const float* b, float* out, int nch, void* stream) {
+  if (!w || !b || !out || nch < 1) return -1;
+  return sf_ffn_dw_pack(w, b, out, nch, (hipStream_t)stream);
+}
+int flair_sf_ffn_fused(const void* x, const float* ln_g, const float* ln_b, const void* w1, const float* b1, const float* dwp, const void* w2,
+                       const float* b2, void* out, int B, int H, int W, int C, float eps, const float* ln2_g, const float* ln2_b, void* out_ln,
+                       void* stream) {
+  if (!x || !ln_g || !ln_b || !w1 || !b1 || !dwp || !w2 || !b2 || !out || B < 1) return -1;
+  return sf_ffn_fused(x, ln_g, ln_b, w1, b1, dwp, w2, b2, out, B, H, W, C, eps, ln2_g, ln2_b, out_ln, (hipStream_t)stream);
+}
+int flair_sf_head_fused_ok(int dtype, int H, int W, int C0, int D, int labels) { return sf_head_fused_ok(dtype, H, W, C0, D, labels) ? 1 : 0; }
+int flair_sf_head_wint(void* wint, void* stream) {
+  if (!wint) return -1;
+  return sf_head_wint(wint, (hipStream_t)stream);
+}
+int flair_sf_head_fused(const void* f0, const void* w0, const void* g1, const void* g2, const void* g3, const void* wint, const float* scale,
+                        const float* shift2, const void* wc, const float* bc, float* out, int B, int H, int W, int D, int labels, void* stream) {
+  if (!f0 || !w0 || !g1 || !g2 || !g3 || !wint || !scale || !shift2 || !wc || !out || B < 1 || labels < 1) return -1;
+  return sf_head_fused(f0, w0, g1, g2, g3, wint, scale, shift2, wc, bc, out, B, H, W, D, labels, (hipStream_t)stream);
+}
+int flair_sf_attention(int dtype, const void* q, const void* k, const void* v, void* out, int B, int N, int Nk, int hidden, int kv_ld,
+                       void* stream) {
+  if (!q || !k || !v || !out || B < 1 || N < 1 || hidden < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return sf_attention(dtype, q, k, v, out, B, N, Nk, hidden, kv_ld, (hipStream_t)stream);
+}
+int flair_swin_window_attention(int dtype, const void* qkv, const float* qkv_bias, const float* table, void* out, int B, int H, int W, int C,
+                                int heads, int shift, void* stream) {
+  if (!qkv || !qkv_bias || !table || !out) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return swin_window_attention(dtype, qkv, qkv_bias, table, out, B, H, W, C, heads, shift, (hipStream_t)stream);
+}
+int flair_swin_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, int ld, float eps,
+                         void* stream) {
+  if (!x || !gamma || !beta || !y || rows < 1 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return swin_layernorm(dtype, x, gamma, beta, y, (long)rows, C, ld, eps, (hipStream_t)stream);
+}
+int flair_swin_patch_merge_ln(int dtype, const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C, float eps,
+                              void* stream) {
+  if (!x || !gamma || !beta || !y || B < 1 || H < 2 || W < 2 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return swin_patch_merge_ln(dtype, x, gamma, beta, y, B, H, W, C, eps, (hipStream_t)stream);
+}
+int flair_swin_adaptive_avgpool(int dtype, const void* x, int ld, void* y, int B, int h, int w, int C, int S, void* stream) {
+  if (!x || !y || B < 1 || h < 1 || w < 1 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return swin_adaptive_avgpool(dtype, x, ld, y, B, h, w, C, S, (hipStream_t)stream);
+}
+int flair_swin_bilinear_add(int dtype, const void* x, void* y, int B, int h, int w, int C, int H, int W, void* stream) {
+  if (!x || !y || B < 1 || h < 1 || w < 1 || H < 1 || W < 1 || C < 1) return -1;
+  if (!FLAIR_DT_OK(dtype)) return -2;
+  return swin_bilinear_add(dtype, x, y, B, h, w, C, H, W, (hipStream_t)stream);
+}
+#undef FLAIR_DT_OK
 
 // ------------------------------------------------------------------------------------------ SegFormer (zone_detect, HuggingFace provider)
 int flair_segformer_create(flair_segformer_t** out, int in_channels, int num_labels, const int depths[4], const int hidden_sizes[4],

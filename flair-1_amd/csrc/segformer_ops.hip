@@ -1272,7 +1272,10 @@ int sf_dwconv3x3_gelu(int dtype, const void* x, const float* w, const float* bia
   while (cg * 2 <= 256 && ng % (cg * 2) == 0) cg *= 2;    // groups per workgroup: the largest power of two dividing both 256 and
                                                           // the group count (4 x 320 channels = 320 groups -> 64 per workgroup, 5 in y)
   int L = W % 16 == 0 ? 16 : W % 8 == 0 ? 8 : W % 4 == 0 ? 4 : W % 2 == 0 ? 2 : 1;   // pixels per segment
-  const int lmax = tune("FLAIR_SF_DW_L", dtype == DT_F32 ? 16 : 4);   // (bf16: 16 and 8 spill at four waves per SIMD)
+  // 0 = the dtype's own default, looked up at every call (tune() keeps the first default it is given for a key, so a
+  // dtype-dependent default there would be fixed by whichever dtype ran first).  bf16: 16 and 8 spill at four waves per SIMD
+  int lmax = tune("FLAIR_SF_DW_L", 0);
+  if (lmax <= 0) lmax = dtype == DT_F32 ? 16 : 4;
   while (L > lmax && L > 1) L >>= 1;
   const long items = (long)B * H * (W / L);
   if (items > (1L << 30)) return -2;

@@ -71,6 +71,25 @@ PROTOTYPES = {
     "flair_maxpool_backward": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "flair_nchw_to_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "flair_nhwc_to_nchw": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "flair_sf_layernorm": (i32, [i32, vp, vp, vp, vp, i64, i32, f32, vp]),
+    "flair_sf_dwconv3x3_gelu": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "flair_sf_bilinear_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "flair_sf_bilinear_nchw_f32": (i32, [vp, vp, i64, i32, i32, i32, i32, vp]),
+    "flair_sf_slice_cols": (i32, [i32, vp, i32, i32, i32, i64, vp, vp]),
+    "flair_sf_fuse_bias": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "flair_sf_upsample_sum_bn_relu": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "flair_sf_ffn_fused_ok": (i32, [i32, i32, i32, i32]),
+    "flair_sf_ffn_dw_pack": (i32, [vp, vp, vp, i32, vp]),
+    "flair_sf_ffn_fused": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "flair_sf_head_fused_ok": (i32, [i32, i32, i32, i32, i32, i32]),
+    "flair_sf_head_wint": (i32, [vp, vp]),
+    "flair_sf_head_fused": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "flair_sf_attention": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "flair_swin_window_attention": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "flair_swin_layernorm": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, f32, vp]),
+    "flair_swin_patch_merge_ln": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
+    "flair_swin_adaptive_avgpool": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "flair_swin_bilinear_add": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "flair_profile_start": (i32, [i32]),
     "flair_profile_stop": (i32, []),
     "flair_profile_kernel": (i32, [i32, C.c_char_p, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double),
@@ -119,7 +138,7 @@ class ConvEx(C.Structure):
                 ("in_scale", vp), ("in_shift", vp), ("oscale", vp), ("oshift", vp), ("ores", vp), ("orelu", i32),
                 ("accumulate", i32), ("acc_src", vp),
                 ("pool_c0", i32), ("out_skip", vp), ("out_skip_ld", i32), ("skip_accumulate", i32),
-                ("preds_u8", vp), ("maxprob_f32", vp)]
+                ("preds_u8", vp), ("maxprob_f32", vp), ("ogelu", i32)]
 
 
 class WgradEx(C.Structure):

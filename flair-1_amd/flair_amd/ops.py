@@ -70,10 +70,11 @@ def conv2d_backward(x, w, dy, stride=1, pad=1, need_dx=True, need_dw=True):
 
 def conv2d_ex(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, want_nhwc=True, want_nchw=False, want_stats=False,
               in_scale=None, in_shift=None, oscale=None, oshift=None, ores=None, orelu=False, out=None, accumulate=False,
-              acc_src=None, pool_c0=0, out_skip=None, skip_accumulate=False, want_preds=False, want_maxprob=False):
+              acc_src=None, pool_c0=0, out_skip=None, skip_accumulate=False, want_preds=False, want_maxprob=False, ogelu=False):
     """flair_conv2d_ex: the fused forms of the convolution launcher.  mode 0: forward, w = [Cout][C0 + C1][R][R]; mode 1: stride-1
     data gradient, x0 = dy, w = the forward layer's [C0][Cout][R][R].  `out` (NHWC, optional) is the tensor accumulated into / written;
-    with pool_c0 it is [N][H/2][W/2][pool_c0] and out_skip [N][H][W][Cout - pool_c0].
+    with pool_c0 it is [N][H/2][W/2][pool_c0] and out_skip [N][H][W][Cout - pool_c0].  ogelu: erf-GELU of the
+    accumulator (+ bias) before ores / orelu (gather-form GEMM only).
     Returns a dict: y, out_skip, y_nchw, stats, preds, maxprob (absent outputs None)."""
     import ctypes as C
     N, H, W, C0 = x0.shape
@@ -103,7 +104,7 @@ def conv2d_ex(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, wan
                  in_shift=L.ptr(in_shift), oscale=L.ptr(oscale), oshift=L.ptr(oshift), ores=L.ptr(ores), orelu=int(orelu),
                  accumulate=int(accumulate), acc_src=L.ptr(acc_src), pool_c0=pool_c0, out_skip=L.ptr(out_skip),
                  out_skip_ld=out_skip.shape[3] if out_skip is not None else 0, skip_accumulate=int(skip_accumulate),
-                 preds_u8=L.ptr(pr), maxprob_f32=L.ptr(mp))
+                 preds_u8=L.ptr(pr), maxprob_f32=L.ptr(mp), ogelu=int(ogelu))
     l = L.lib()
     ws = _ws(l.flair_conv2d_ex_workspace_bytes(C.addressof(a)), dev)
     L.check(l.flair_conv2d_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream()), "conv2d_ex")
@@ -225,3 +226,168 @@ def jaccard(confmat):
 
 def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
+
+
+# ---- the SegFormer / UperNet-Swin kernels one at a time (the launchers the two executors call).  `rc=True` returns the
+# launcher's return code instead of raising, so that a refusal (-2) can be asserted.
+def _ret(rc, what, out, want_rc):
+    if want_rc:
+        return rc
+    L.check(rc, what)
+    return out
+
+
+def _bf16(t):
+    return t.to(torch.bfloat16).contiguous()
+
+
+def sf_layernorm(x, gamma, beta, eps, rc=False):
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    return _ret(L.lib().flair_sf_layernorm(_dt(x), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), x.numel() // C, C, float(eps),
+                                           L.stream()), "sf_layernorm", y, rc)
+
+
+def swin_layernorm(x, gamma, beta, eps, out=None, rc=False):
+    """out (optional): rows of ld = out.shape[-1] >= C elements, columns [0, C) written."""
+    C = x.shape[-1]
+    y = torch.empty_like(x) if out is None else out
+    return _ret(L.lib().flair_swin_layernorm(_dt(x), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), x.numel() // C, C, y.shape[-1],
+                                             float(eps), L.stream()), "swin_layernorm", y, rc)
+
+
+def swin_patch_merge_ln(x, gamma, beta, eps, rc=False):
+    B, H, W, C = x.shape
+    y = torch.empty(B, H // 2, W // 2, 4 * C, dtype=x.dtype, device=x.device)
+    return _ret(L.lib().flair_swin_patch_merge_ln(_dt(x), L.ptr(x), L.ptr(gamma), L.ptr(beta), L.ptr(y), B, H, W, C, float(eps),
+                                                  L.stream()), "swin_patch_merge_ln", y, rc)
+
+
+def sf_dwconv3x3_gelu(x, w, bias, rc=False):
+    """x [B][H][W][C], w [C][3][3] (or [C][1][3][3]) fp32, bias [C] fp32"""
+    B, H, W, C = x.shape
+    y = torch.empty_like(x)
+    return _ret(L.lib().flair_sf_dwconv3x3_gelu(_dt(x), L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), B, H, W, C, L.stream()),
+                "sf_dwconv3x3_gelu", y, rc)
+
+
+def sf_bilinear_nhwc(x, H, W, out=None, rc=False):
+    """out (optional) [B][H][W][ld >= C]: channels [0, C) written"""
+    B, h, w, C = x.shape
+    y = torch.empty(B, H, W, C, dtype=x.dtype, device=x.device) if out is None else out
+    return _ret(L.lib().flair_sf_bilinear_nhwc(_dt(x), L.ptr(x), L.ptr(y), B, h, w, C, H, W, y.shape[-1], L.stream()),
+                "sf_bilinear_nhwc", y, rc)
+
+
+def sf_bilinear_nchw_f32(x, H, W, rc=False):
+    B, Cc, h, w = x.shape
+    y = torch.empty(B, Cc, H, W, dtype=torch.float32, device=x.device)
+    return _ret(L.lib().flair_sf_bilinear_nchw_f32(L.ptr(x), L.ptr(y), B * Cc, h, w, H, W, L.stream()), "sf_bilinear_nchw_f32", y, rc)
+
+
+def sf_slice_cols(src, col0, ncols, dtype, rc=False):
+    """fp32 [rows][ld] columns [col0, col0 + ncols) -> dtype [rows][ncols]"""
+    rows, ld = src.shape
+    dt = L.dtype_code(dtype)
+    y = torch.empty(rows, ncols, dtype=L.torch_dtype(dt), device=src.device)
+    return _ret(L.lib().flair_sf_slice_cols(dt, L.ptr(src), ld, col0, ncols, rows, L.ptr(y), L.stream()), "sf_slice_cols", y, rc)
+
+
+def sf_fuse_bias(wf, b3, b2, b1, b0, scale, shift, rc=False):
+    D = wf.shape[0]
+    y = torch.empty(D, dtype=torch.float32, device=wf.device)
+    return _ret(L.lib().flair_sf_fuse_bias(L.ptr(wf), D, L.ptr(b3), L.ptr(b2), L.ptr(b1), L.ptr(b0), L.ptr(scale), L.ptr(shift),
+                                           L.ptr(y), L.stream()), "sf_fuse_bias", y, rc)
+
+
+def sf_upsample_sum_bn_relu(g0, g1, g2, g3, scale, shift2, rc=False):
+    B, H, W, D = g0.shape
+    z = torch.empty_like(g0)
+    return _ret(L.lib().flair_sf_upsample_sum_bn_relu(_dt(g0), L.ptr(g0), L.ptr(g1), L.ptr(g2), L.ptr(g3), L.ptr(scale), L.ptr(shift2),
+                                                      L.ptr(z), B, H, W, D, L.stream()), "sf_upsample_sum_bn_relu", z, rc)
+
+
+def sf_ffn_fused_ok(dtype, C, H, W):
+    return bool(L.lib().flair_sf_ffn_fused_ok(L.dtype_code(dtype), C, H, W))
+
+
+def sf_ffn_fused(x, ln_g, ln_b, w1, b1, dw_w, dw_b, w2, b2, eps, ln2_g=None, ln2_b=None, want_ln=False, out=None, out_ln=None,
+                 rc=False):
+    """x bf16 [B][H][W][C]; w1 [4C][C], w2 [C][4C], dw_w [4C][3][3] fp32 (the two matrices are packed to bf16 row-major here).
+    Returns (out, out_ln)."""
+    B, H, W, C = x.shape
+    l = L.lib()
+    dwp = sf_ffn_dw_pack(dw_w, dw_b)
+    w1p, w2p = _bf16(w1), _bf16(w2)
+    out = torch.empty_like(x) if out is None else out
+    if want_ln and out_ln is None:
+        out_ln = torch.empty_like(x)
+    r = l.flair_sf_ffn_fused(L.ptr(x), L.ptr(ln_g), L.ptr(ln_b), L.ptr(w1p), L.ptr(b1), L.ptr(dwp), L.ptr(w2p), L.ptr(b2), L.ptr(out),
+                             B, H, W, C, float(eps), L.ptr(ln2_g), L.ptr(ln2_b), L.ptr(out_ln), L.stream())
+    return _ret(r, "sf_ffn_fused", (out, out_ln), rc)
+
+
+def sf_ffn_dw_pack(dw_w, dw_b):
+    nch = dw_b.numel()
+    dwp = torch.empty(nch // 4, 10, 4, dtype=torch.float32, device=dw_w.device)
+    dw_w = dw_w.contiguous()
+    L.check(L.lib().flair_sf_ffn_dw_pack(L.ptr(dw_w), L.ptr(dw_b), L.ptr(dwp), nch, L.stream()), "sf_ffn_dw_pack")
+    return dwp
+
+
+def sf_head_fused_ok(dtype, H, W, C0, D, labels):
+    return bool(L.lib().flair_sf_head_fused_ok(L.dtype_code(dtype), H, W, C0, D, labels))
+
+
+def sf_head_wint(device):
+    w = torch.empty(128, 96, dtype=torch.bfloat16, device=device)
+    L.check(L.lib().flair_sf_head_wint(L.ptr(w), L.stream()), "sf_head_wint")
+    return w
+
+
+def sf_head_fused(f0, w0, g1, g2, g3, scale, shift2, wc, bc, rc=False):
+    """f0 bf16 [B][H][W][64], g_i bf16 [B][H >> i][W >> i][D]; w0 [D][64], wc [labels][D] fp32 (packed to bf16 here, wc padded to
+    32 rows of zeros); logits fp32 NCHW"""
+    B, H, W, _ = f0.shape
+    D, labels = w0.shape[0], wc.shape[0]
+    wcp = torch.zeros(32, D, dtype=torch.bfloat16, device=f0.device)
+    wcp[:min(labels, 32)] = wc[:32].to(torch.bfloat16)
+    out = torch.empty(B, labels, H, W, dtype=torch.float32, device=f0.device)
+    w0p, wint = _bf16(w0), sf_head_wint(f0.device)   # named: a temporary's block would be handed to the next allocation
+    r = L.lib().flair_sf_head_fused(L.ptr(f0), L.ptr(w0p), L.ptr(g1), L.ptr(g2), L.ptr(g3), L.ptr(wint),
+                                    L.ptr(scale), L.ptr(shift2), L.ptr(wcp), L.ptr(bc), L.ptr(out), B, H, W, D, labels, L.stream())
+    return _ret(r, "sf_head_fused", out, rc)
+
+
+def sf_attention(q, k, v, kv_ld=None, rc=False):
+    """q [B][N][hidden]; k, v [B][Nk] rows of kv_ld elements (views into one [B][Nk][2 * hidden] buffer allowed: pass kv_ld)"""
+    B, N, hidden = q.shape
+    Nk = k.shape[1]
+    kv_ld = kv_ld or k.shape[2]
+    out = torch.empty_like(q)
+    r = L.lib().flair_sf_attention(_dt(q), L.ptr(q), k.data_ptr(), v.data_ptr(), L.ptr(out), B, N, Nk, hidden, kv_ld, L.stream())
+    return _ret(r, "sf_attention", out, rc)
+
+
+def swin_window_attention(qkv, qkv_bias, table, heads, shift, rc=False):
+    """qkv [B][H][W][3C] (biases included), qkv_bias [3C], table [169][heads] fp32 -> [B][H][W][C]"""
+    B, H, W, C3 = qkv.shape
+    out = torch.empty(B, H, W, C3 // 3, dtype=qkv.dtype, device=qkv.device)
+    r = L.lib().flair_swin_window_attention(_dt(qkv), L.ptr(qkv), L.ptr(qkv_bias), L.ptr(table), L.ptr(out), B, H, W, C3 // 3, heads,
+                                            shift, L.stream())
+    return _ret(r, "swin_window_attention", out, rc)
+
+
+def swin_adaptive_avgpool(x, C, S, rc=False):
+    """x [B][h][w][ld >= C] -> [B][S][S][C]"""
+    B, h, w, ld = x.shape
+    y = torch.empty(B, S, S, C, dtype=x.dtype, device=x.device)
+    return _ret(L.lib().flair_swin_adaptive_avgpool(_dt(x), L.ptr(x), ld, L.ptr(y), B, h, w, C, S, L.stream()), "swin_adaptive_avgpool",
+                y, rc)
+
+
+def swin_bilinear_add_(y, x, rc=False):
+    """y [B][H][W][C] += bilinear(x [B][h][w][C]) in place"""
+    B, H, W, C = y.shape
+    _, h, w, _ = x.shape
+    return _ret(L.lib().flair_swin_bilinear_add(_dt(x), L.ptr(x), L.ptr(y), B, h, w, C, H, W, L.stream()), "swin_bilinear_add", y, rc)

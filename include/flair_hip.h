@@ -266,6 +266,7 @@ typedef struct flair_conv_ex {
   int accumulate; const void* acc_src;
   int pool_c0; void* out_skip; int out_skip_ld; int skip_accumulate;
   uint8_t* preds_u8; float* maxprob_f32;
+  int ogelu;   /* y = gelu_erf(acc (+ bias)) before ores / orelu: the gather-form GEMM only (-6 elsewhere) */
 } flair_conv_ex_t;
 typedef struct flair_wgrad_ex {
   int dtype;
@@ -296,6 +297,43 @@ int flair_maxpool_backward(int dtype, const void* dy, const uint8_t* idx, void* 
                            void* stream);
 int flair_nchw_to_nhwc(int dtype, const float* x_nchw, void* y_nhwc, int N, int C, int H, int W, int Cpad, void* stream);
 int flair_nhwc_to_nchw(int dtype, const void* x_nhwc, float* y_nchw, int N, int C, int H, int W, int Cpad, void* stream);
+
+/* The SegFormer / UperNet-Swin kernels one at a time, as the two executors launch them (csrc/segformer_ops.h, csrc/swin_ops.h
+ * say what each computes).  All pointers are device pointers; activations token-major NHWC in `dtype`, parameters fp32 unless
+ * noted; the return value is the launcher's own (-2: a shape the kernel does not take).  The _ok predicates return 0 / 1. */
+int flair_sf_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, float eps,
+                       void* stream);
+int flair_sf_dwconv3x3_gelu(int dtype, const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C,
+                            void* stream);
+int flair_sf_bilinear_nhwc(int dtype, const void* x, void* y, int B, int h, int w, int C, int H, int W, int ld, void* stream);
+int flair_sf_bilinear_nchw_f32(const float* x, float* y, int64_t planes, int h, int w, int H, int W, void* stream);
+int flair_sf_slice_cols(int dtype, const float* src, int ld, int col0, int ncols, int64_t rows, void* dst, void* stream);
+int flair_sf_fuse_bias(const float* wf, int D, const float* b3, const float* b2, const float* b1, const float* b0,
+                       const float* scale, const float* shift, float* shift2, void* stream);
+int flair_sf_upsample_sum_bn_relu(int dtype, const void* g0, const void* g1, const void* g2, const void* g3, const float* scale,
+                                  const float* shift2, void* z, int B, int H, int W, int D, void* stream);
+int flair_sf_ffn_fused_ok(int dtype, int C, int H, int W);
+int flair_sf_ffn_dw_pack(const float* w, const float* b, float* out, int nch, void* stream);
+/* x / out / out_ln bf16 [B][H][W][C]; w1 [4C][C], w2 [C][4C] bf16 row-major; dwp from flair_sf_ffn_dw_pack */
+int flair_sf_ffn_fused(const void* x, const float* ln_g, const float* ln_b, const void* w1, const float* b1, const float* dwp,
+                       const void* w2, const float* b2, void* out, int B, int H, int W, int C, float eps, const float* ln2_g,
+                       const float* ln2_b, void* out_ln, void* stream);
+int flair_sf_head_fused_ok(int dtype, int H, int W, int C0, int D, int labels);
+int flair_sf_head_wint(void* wint_bf16_128x96, void* stream);
+/* f0 [B][H][W][64], w0 [D][64], g1..g3 [B][H >> i][W >> i][D], wint, wc [32][D] (rows >= labels zero): bf16; out fp32 NCHW */
+int flair_sf_head_fused(const void* f0, const void* w0, const void* g1, const void* g2, const void* g3, const void* wint,
+                        const float* scale, const float* shift2, const void* wc, const float* bc, float* out, int B, int H, int W,
+                        int D, int labels, void* stream);
+int flair_sf_attention(int dtype, const void* q, const void* k, const void* v, void* out, int B, int N, int Nk, int hidden,
+                       int kv_ld, void* stream);
+int flair_swin_window_attention(int dtype, const void* qkv, const float* qkv_bias, const float* table, void* out, int B, int H,
+                                int W, int C, int heads, int shift, void* stream);
+int flair_swin_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* y, int64_t rows, int C, int ld,
+                         float eps, void* stream);
+int flair_swin_patch_merge_ln(int dtype, const void* x, const float* gamma, const float* beta, void* y, int B, int H, int W, int C,
+                              float eps, void* stream);
+int flair_swin_adaptive_avgpool(int dtype, const void* x, int ld, void* y, int B, int h, int w, int C, int S, void* stream);
+int flair_swin_bilinear_add(int dtype, const void* x, void* y, int B, int h, int w, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MetadataMLP (replaces /root/reference/src/flair/model.py:74-96, called at model.py:58): Linear(45,64) -> Dropout(0.4) ->
