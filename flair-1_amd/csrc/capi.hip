@@ -11,8 +11,6 @@
 
 using namespace flair;
 
-namespace flair { int conv_weight_rows_pad(int cout); }
-
 struct flair_unet { UNet net; flair_unet(int a, int b, int c) : net(a, b, c) {} };
 struct flair_segformer {
   SegFormer net;
@@ -24,6 +22,18 @@ struct flair_upernet {
   flair_upernet(int a, int b, int e, const int* d, const int* h, int hid, const int* ps, int ai, int ac, int dt)
       : net(a, b, e, d, h, hid, ps, ai, ac, dt) {}
 };
+
+// one entry of a transformer executor's tensor table (flair_segformer_tensor_info, flair_upernet_tensor_info)
+static int tf_tensor_info(const std::vector<SfTensor>& tensors, int i, char* name, int name_cap, int64_t shape[4], int* ndim,
+                          int64_t* offset, int* kind) {
+  if (i < 0 || i >= (int)tensors.size() || !name || name_cap < 2) return -1;
+  const SfTensor& t = tensors[i];
+  strncpy(name, t.name.c_str(), name_cap - 1);
+  name[name_cap - 1] = 0;
+  for (int d = 0; d < 4; ++d) shape[d] = t.shape[d];
+  *ndim = t.ndim; *offset = t.offset; *kind = t.kind;
+  return 0;
+}
 
 extern "C" {
 
@@ -664,13 +674,7 @@ int64_t flair_segformer_param_count(const flair_segformer_t* h) { return h ? h->
 int flair_segformer_num_tensors(const flair_segformer_t* h) { return h ? (int)h->net.tensors.size() : -1; }
 int flair_segformer_tensor_info(const flair_segformer_t* h, int i, char* name, int name_cap, int64_t shape[4], int* ndim, int64_t* offset,
                                 int* kind) {
-  if (!h || i < 0 || i >= (int)h->net.tensors.size() || !name || name_cap < 2) return -1;
-  const SfTensor& t = h->net.tensors[i];
-  strncpy(name, t.name.c_str(), name_cap - 1);
-  name[name_cap - 1] = 0;
-  for (int d = 0; d < 4; ++d) shape[d] = t.shape[d];
-  *ndim = t.ndim; *offset = t.offset; *kind = t.kind;
-  return 0;
+  return h ? tf_tensor_info(h->net.tensors, i, name, name_cap, shape, ndim, offset, kind) : -1;
 }
 int64_t flair_segformer_workspace_bytes(flair_segformer_t* h, int B, int H, int W) {
   if (!h || B < 1 || !h->net.shape_ok(H, W)) return -1;
@@ -707,13 +711,7 @@ int64_t flair_upernet_param_count(const flair_upernet_t* h) { return h ? h->net.
 int flair_upernet_num_tensors(const flair_upernet_t* h) { return h ? (int)h->net.tensors.size() : -1; }
 int flair_upernet_tensor_info(const flair_upernet_t* h, int i, char* name, int name_cap, int64_t shape[4], int* ndim, int64_t* offset,
                               int* kind) {
-  if (!h || i < 0 || i >= (int)h->net.tensors.size() || !name || name_cap < 2) return -1;
-  const SfTensor& t = h->net.tensors[i];
-  strncpy(name, t.name.c_str(), name_cap - 1);
-  name[name_cap - 1] = 0;
-  for (int d = 0; d < 4; ++d) shape[d] = t.shape[d];
-  *ndim = t.ndim; *offset = t.offset; *kind = t.kind;
-  return 0;
+  return h ? tf_tensor_info(h->net.tensors, i, name, name_cap, shape, ndim, offset, kind) : -1;
 }
 int64_t flair_upernet_workspace_bytes(flair_upernet_t* h, int B, int H, int W) {
   if (!h || B < 1) return -1;

@@ -52,6 +52,7 @@ struct PackTable {
   PackDesc d[MAX];
 };
 int pack_weights_all(int dtype, const float* params, void* base, const PackTable& tb, hipStream_t s);
+int conv_weight_rows_pad(int cout);   // conv_igemm.hip: rows of a packed weight (Cout up to whole column tiles)
 int sgd_step(float* params, const float* grads, long n, float lr, hipStream_t s);
 int add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, hipStream_t s);
 int ew_add(int dtype, void* dst, const void* src, long n, hipStream_t s);

@@ -14,63 +14,10 @@
 // fused epilogues (bias, residual, erf-GELU, folded BatchNorm + ReLU, fp32 NCHW logits); the rest is swin_ops.hip.
 #include "upernet.h"
 
-#include <string.h>
-
 #include "segformer_ops.h"
 #include "swin_ops.h"
 
 namespace flair {
-
-int conv_weight_rows_pad(int cout);   // conv_igemm.hip
-
-#define UP_RUN(expr)                     \
-  do {                                   \
-    if (!dry_ && !err_) {                \
-      int rc__ = (expr);                 \
-      if (rc__) err_ = rc__;             \
-    }                                    \
-  } while (0)
-
-long UperNet::add_tensor(const std::string& name, int ndim, long d0, long d1, long d2, long d3, int kind) {
-  SfTensor t;
-  t.name = name; t.ndim = ndim; t.shape[0] = d0; t.shape[1] = d1; t.shape[2] = d2; t.shape[3] = d3; t.kind = kind;
-  long n = 1;
-  for (int i = 0; i < ndim; ++i) n *= t.shape[i];
-  t.offset = n_params;
-  n_params = round_up(n_params + n, 4);   // every tensor 16-byte aligned in the flat buffer
-  tensors.push_back(t);
-  return t.offset;
-}
-
-SfLin UperNet::make_lin(int cin, int cout, int k, int stride, int pad) const {
-  SfLin L;
-  L.cin = cin; L.cout = cout; L.k = k; L.stride = stride; L.pad = pad;
-  L.cin_p = (int)round_up(cin, 8);
-  L.w_off = -1; L.b_off = -1;
-  L.Kg = k * k * L.cin_p;
-  L.Kpad = (int)round_up(L.Kg, dtype == DT_F32 ? 32 : 64);
-  L.rows = conv_weight_rows_pad(cout);
-  return L;
-}
-
-int UperNet::add_lin(const std::string& name, int cin, int cout, int k, int stride, int pad, bool bias) {
-  SfLin L = make_lin(cin, cout, k, stride, pad);
-  const bool conv = name.find("#conv") != std::string::npos;
-  const std::string base = name.substr(0, name.find('#'));
-  L.w_off = conv ? add_tensor(base + ".weight", 4, cout, cin, k, k, 0) : add_tensor(base + ".weight", 2, cout, cin, 1, 1, 0);
-  L.b_off = bias ? add_tensor(base + ".bias", 1, cout, 1, 1, 1, 0) : -1;
-  lins.push_back(L);
-  return (int)lins.size() - 1;
-}
-
-int UperNet::add_ln(const std::string& name, int C) {
-  SfNorm n;
-  n.C = C;
-  n.g_off = add_tensor(name + ".weight", 1, C, 1, 1, 1, 0);
-  n.b_off = add_tensor(name + ".bias", 1, C, 1, 1, 1, 0);
-  norms.push_back(n);
-  return (int)norms.size() - 1;
-}
 
 int UperNet::add_cbn(const std::string& name, int cin, int cout, int k) {
   UpConvBn c;
@@ -85,7 +32,7 @@ int UperNet::add_cbn(const std::string& name, int cin, int cout, int k) {
 
 UperNet::UperNet(int in_ch, int labels, int embed, const int* depths_, const int* heads_, int hidden_, const int* pool_scales_, int aux_in,
                  int aux_channels, int dt)
-    : in_channels(in_ch), num_labels(labels), embed_dim(embed), hidden(hidden_), dtype(dt) {
+    : TfExec(dt), in_channels(in_ch), num_labels(labels), embed_dim(embed), hidden(hidden_) {
   for (int i = 0; i < 4; ++i) {
     depths[i] = depths_[i]; heads[i] = heads_[i]; pool_scales[i] = pool_scales_[i]; dims[i] = embed << i;
   }
@@ -146,104 +93,44 @@ int UperNet::max_batch(int H, int W) const {
   return (int)(n < 1 ? 1 : n > 1024 ? 1024 : n);
 }
 
-void* UperNet::alloc(size_t bytes) {
-  const size_t off = top_;
-  top_ = (size_t)round_up((long)(top_ + bytes), 256);
-  if (top_ > peak_) peak_ = top_;
-  if (!dry_ && top_ > cap_) { if (!err_) err_ = -100; return base_; }
-  return base_ + off;
-}
-
-void UperNet::gemm(const SfLin& L, const void* in, int B, int Hin, int Win, void* out, int out_ld, const void* res, const float* oscale,
-                   const float* oshift, int relu, float* out_nchw, int gelu, const void* wpacked, const float* bias) {
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src0 = in; a.C0 = L.cin_p; a.N = B; a.Hin = Hin; a.Win = Win;
-  a.Hout = (Hin + 2 * L.pad - L.k) / L.stride + 1; a.Wout = (Win + 2 * L.pad - L.k) / L.stride + 1;
-  a.R = L.k; a.S = L.k; a.out_mul = L.stride; a.pad = L.pad; a.in_div = 1;
-  a.Cout = L.cout; a.Kg = L.Kg; a.Kpad = L.Kpad; a.w = wpacked ? wpacked : base_ + L.packed;
-  a.bias = bias ? bias : L.b_off >= 0 ? params_ + L.b_off : nullptr;
-  a.out = out; a.out_ld = out_ld; a.out_nchw = out_nchw;
-  a.ores = res; a.oscale = oscale; a.oshift = oshift; a.orelu = relu; a.ogelu = gelu;
-  UP_RUN(launch_conv(dtype, a, s_));
-}
-
 void UperNet::conv_bn_relu(int i, const void* in, int B, int Hin, int Win, void* out, int out_ld) {
   gemm(lins[cbs[i].conv], in, B, Hin, Win, out, out_ld, nullptr, bn_sc_[i], bn_sh_[i], 1, nullptr);
 }
 
 void UperNet::layernorm(const SfNorm& n, const void* x, void* y, long rows, int ld) {
-  UP_RUN(swin_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, ld, 1e-5f, s_));
+  TF_RUN(swin_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, ld, 1e-5f, s_));
 }
 
 int UperNet::run(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s,
                  bool dry) {
   if (!shape_ok(H, W)) return -10;
-  base_ = dry ? (unsigned char*)0x100000 : (unsigned char*)ws;
-  cap_ = ws_bytes; top_ = 0; peak_ = 0; dry_ = dry; err_ = 0; s_ = s; params_ = params;
   const size_t es = dtype_size(dtype);
   // ---- what depends on the weights alone (packed operands, fused q / k / v, folded BatchNorm) sits at the front of the arena
   // at shape-independent offsets and is rebuilt only when the parameter buffer or the workspace changes, or after weights_changed()
-  const bool fresh = !dry && cache_ok_ && cache_params_ == params && cache_ws_ == ws;
-  for (auto& L : lins) { L.packed = top_; alloc((size_t)L.rows * L.Kpad * es); }
-  if (!fresh) {
-    PackTable tb;
-    tb.n = 0;
-    for (size_t i = 0; i < lins.size(); ++i) {
-      const SfLin& L = lins[i];
-      PackDesc& d = tb.d[tb.n++];
-      memset(&d, 0, sizeof(d));
-      d.w_off = L.w_off; d.dst_off = L.packed; d.Cout = L.cout; d.Cin = L.cin; d.R = L.k; d.S = L.k;
-      d.Cin_p = L.cin_p; d.rows_pad = L.rows; d.Kpad = L.Kpad; d.tf = 0;
-      if (tb.n == PackTable::MAX || i + 1 == lins.size()) {
-        UP_RUN(pack_weights_all(dtype, params_, base_, tb, s_));
-        tb.n = 0;
-      }
-    }
-  }
+  const bool fresh = begin(params, ws, ws_bytes, s, dry, 0);
+  pack_lins(fresh);
   // q, k and v of a block as ONE product over [q_proj.weight; k_proj.weight; v_proj.weight] (3C rows) with the concatenated bias
   qkv_w_.clear(); qkv_b_.clear();
-  {
-    PackTable tb;
-    tb.n = 0;
-    for (int si = 0; si < 4; ++si)
-      for (const SwBlock& K : stages[si].blocks) {
-        const int C = dims[si];
-        const SfLin Lq = make_lin(C, 3 * C, 1, 1, 0);
-        const size_t off = top_;
-        alloc((size_t)Lq.rows * Lq.Kpad * es);
-        float* bias = (float*)alloc((size_t)3 * C * 4);
-        qkv_w_.push_back(off); qkv_b_.push_back(bias);
-        if (fresh || dry_) continue;
-        const long w_off[3] = {K.qw, K.kw, K.vw}, b_off[3] = {K.qb, K.kb, K.vb};
-        for (int part = 0; part < 3; ++part) {
-          PackDesc& d = tb.d[tb.n++];
-          memset(&d, 0, sizeof(d));
-          d.w_off = w_off[part]; d.dst_off = off + (size_t)part * C * Lq.Kpad * es; d.Cout = C; d.Cin = C; d.R = 1; d.S = 1;
-          d.Cin_p = Lq.cin_p; d.rows_pad = part < 2 ? C : Lq.rows - 2 * C; d.Kpad = Lq.Kpad; d.tf = 0;
-          if (!err_ && hipMemcpyAsync(bias + part * C, params_ + b_off[part], (size_t)C * 4, hipMemcpyDeviceToDevice, s_) != hipSuccess)
-            err_ = -101;
-        }
-        if (tb.n + 3 > PackTable::MAX) {
-          UP_RUN(pack_weights_all(dtype, params_, base_, tb, s_));
-          tb.n = 0;
-        }
-      }
-    if (tb.n) UP_RUN(pack_weights_all(dtype, params_, base_, tb, s_));
-  }
+  for (int si = 0; si < 4; ++si)
+    for (const SwBlock& K : stages[si].blocks) {
+      const SfPart qkv[3] = {{K.qw, K.qb}, {K.kw, K.kb}, {K.vw, K.vb}};
+      float* bias;
+      qkv_w_.push_back(fuse_rows(make_lin(dims[si], 3 * dims[si], 1, 1, 0), qkv, 3, fresh, &bias));
+      qkv_b_.push_back(bias);
+    }
+  flush_packs();
   bn_sc_.clear(); bn_sh_.clear();
   for (const UpConvBn& c : cbs) {
     const int n = lins[c.conv].cout;
     float* sc = (float*)alloc((size_t)n * 4);
     float* sh = (float*)alloc((size_t)n * 4);
     bn_sc_.push_back(sc); bn_sh_.push_back(sh);
-    if (!fresh) UP_RUN(bn_eval_coeffs(n, params_ + c.g, params_ + c.b, params_ + c.rm, params_ + c.rv, 1e-5f, sc, sh, s_));
+    if (!fresh) TF_RUN(bn_eval_coeffs(n, params_ + c.g, params_ + c.b, params_ + c.rm, params_ + c.rv, 1e-5f, sc, sh, s_));
   }
-  if (!dry) { cache_ok_ = err_ == 0; cache_params_ = params; cache_ws_ = ws; }
   // ---- input, the backbone's outputs, the pyramid-pooling concatenation (stage 4's output is its first dims[3] channels)
   const int Cin_p = lins[patch].cin_p;
   void* xin = alloc((size_t)B * H * W * Cin_p * es);
-  UP_RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
+  TF_RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
   int fh[4], fw[4];
   for (int i = 0; i < 4; ++i) { fh[i] = H >> (i + 2); fw[i] = W >> (i + 2); }
   void* feat[3];
@@ -275,7 +162,7 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
       const SwBlock& K = S.blocks[bi];
       layernorm(norms[K.ln1], x, ln, tokens, C);
       gemm(Lq, ln, B, h, w, qkv, 3 * C, nullptr, nullptr, nullptr, 0, nullptr, 0, base_ + qkv_w_[blk], qkv_b_[blk]);
-      UP_RUN(swin_window_attention(dtype, qkv, qkv_b_[blk], params_ + K.table, ctx, B, h, w, C, heads[i], (bi & 1) ? 3 : 0, s_));
+      TF_RUN(swin_window_attention(dtype, qkv, qkv_b_[blk], params_ + K.table, ctx, B, h, w, C, heads[i], (bi & 1) ? 3 : 0, s_));
       gemm(lins[K.o], ctx, B, h, w, x, C, /*residual*/ x, nullptr, nullptr, 0, nullptr);   // x = o_proj(ctx) + x in place
       layernorm(norms[K.ln2], x, ln, tokens, C);
       gemm(lins[K.fc1], ln, B, h, w, f1, 4 * C, nullptr, nullptr, nullptr, 0, nullptr, /*gelu*/ 1);
@@ -284,7 +171,7 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     if (i < 3) layernorm(norms[hs_norm[i]], x, feat[i], tokens, C);
     else layernorm(norms[hs_norm[3]], x, ppm_cat, tokens, pc_ld);
     if (i < 3) {   // patch merging: gather + LayerNorm(4C) into `ln` (tokens / 4 rows of 4C), reduction 4C -> 2C
-      UP_RUN(swin_patch_merge_ln(dtype, x, params_ + norms[S.merge_ln].g_off, params_ + norms[S.merge_ln].b_off, ln, B, h, w, C, 1e-5f, s_));
+      TF_RUN(swin_patch_merge_ln(dtype, x, params_ + norms[S.merge_ln].g_off, params_ + norms[S.merge_ln].b_off, ln, B, h, w, C, 1e-5f, s_));
       gemm(lins[S.reduction], ln, B, h / 2, w / 2, xn, 2 * C, nullptr, nullptr, nullptr, 0, nullptr);
     }
     top_ = mark;   // the stage's scratch is free again (one stream: later launches are ordered behind its readers)
@@ -300,15 +187,15 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
       const int Sc = pool_scales[j];
       void* pooled = alloc((size_t)B * Sc * Sc * dims[3] * es);
       void* pp = alloc((size_t)B * Sc * Sc * D * es);
-      UP_RUN(swin_adaptive_avgpool(dtype, ppm_cat, pc_ld, pooled, B, fh[3], fw[3], dims[3], Sc, s_));
+      TF_RUN(swin_adaptive_avgpool(dtype, ppm_cat, pc_ld, pooled, B, fh[3], fw[3], dims[3], Sc, s_));
       conv_bn_relu(psp[j], pooled, B, Sc, Sc, pp, D);
-      UP_RUN(sf_bilinear_nhwc(dtype, pp, ppm_cat + (size_t)(dims[3] + j * D) * es, B, Sc, Sc, D, fh[3], fw[3], pc_ld, s_));
+      TF_RUN(sf_bilinear_nhwc(dtype, pp, ppm_cat + (size_t)(dims[3] + j * D) * es, B, Sc, Sc, D, fh[3], fw[3], pc_ld, s_));
     }
     conv_bn_relu(bottleneck, ppm_cat, B, fh[3], fw[3], lat[3], D);
     top_ = mark;
   }
   // ---- top-down path: each step reads the level the previous step updated
-  for (int i = 3; i > 0; --i) UP_RUN(swin_bilinear_add(dtype, lat[i], lat[i - 1], B, fh[i], fw[i], D, fh[i - 1], fw[i - 1], s_));
+  for (int i = 3; i > 0; --i) TF_RUN(swin_bilinear_add(dtype, lat[i], lat[i - 1], B, fh[i], fw[i], D, fh[i - 1], fw[i - 1], s_));
   // ---- FPN convs, every level at level 0's size in its channel slice of the concatenation, fpn_bottleneck, classifier
   unsigned char* fcat = (unsigned char*)alloc((size_t)B * fh[0] * fw[0] * 4 * D * es);
   conv_bn_relu(fpn[0], lat[0], B, fh[0], fw[0], fcat, 4 * D);
@@ -316,24 +203,21 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     const size_t mark = top_;
     void* t = alloc((size_t)B * fh[i] * fw[i] * D * es);
     conv_bn_relu(fpn[i], lat[i], B, fh[i], fw[i], t, D);
-    UP_RUN(sf_bilinear_nhwc(dtype, t, fcat + (size_t)i * D * es, B, fh[i], fw[i], D, fh[0], fw[0], 4 * D, s_));
+    TF_RUN(sf_bilinear_nhwc(dtype, t, fcat + (size_t)i * D * es, B, fh[i], fw[i], D, fh[0], fw[0], 4 * D, s_));
     top_ = mark;
   }
-  UP_RUN(sf_bilinear_nhwc(dtype, lat[3], fcat + (size_t)3 * D * es, B, fh[3], fw[3], D, fh[0], fw[0], 4 * D, s_));
+  TF_RUN(sf_bilinear_nhwc(dtype, lat[3], fcat + (size_t)3 * D * es, B, fh[3], fw[3], D, fh[0], fw[0], 4 * D, s_));
   void* z = alloc((size_t)B * fh[0] * fw[0] * D * es);
   conv_bn_relu(fpn_bottleneck, fcat, B, fh[0], fw[0], z, D);
   float* lq = (float*)alloc((size_t)B * num_labels * fh[0] * fw[0] * 4);
   gemm(lins[cls], z, B, fh[0], fw[0], nullptr, 0, nullptr, nullptr, nullptr, 0, lq);   // 1x1 conv + bias: fp32 NCHW at 1/4
-  UP_RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
-  need_ = peak_ + (1 << 20);
-  if (err_) cache_ok_ = false;
-  return err_;
+  TF_RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
+  return end();
 }
 
 size_t UperNet::workspace_bytes(int B, int H, int W) {
   const int bc = max_batch(H, W);
-  if (run(nullptr, nullptr, reinterpret_cast<float*>(16), B < bc ? B : bc, H, W, nullptr, 0, nullptr, true)) return 0;
-  return need_;
+  return planned(run(nullptr, nullptr, reinterpret_cast<float*>(16), B < bc ? B : bc, H, W, nullptr, 0, nullptr, true));
 }
 
 int UperNet::forward(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s) {

@@ -14,16 +14,14 @@ are refused.  Every tensor is a view of one flat fp32 device buffer laid out by 
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 import re
 from types import SimpleNamespace
 
 import torch
-import torch.nn as nn
 
 from . import _lib as L
-from .segformer import SegformerForSemanticSegmentation
+from ._native_model import NativeModel
 
 # published geometries: embed_dim 96, heads 3 / 6 / 12 / 24, window 7 for both; only the depth of stage 3 differs
 UPERNET_SWIN_DEPTHS = {"tiny": (2, 2, 6, 2), "small": (2, 2, 18, 2)}
@@ -65,7 +63,11 @@ def config_for_upernet(org_model: str) -> dict:
     return {"depths": UPERNET_SWIN_DEPTHS[m.group(1)]}
 
 
-class UperNetForSemanticSegmentation(nn.Module):
+class UperNetForSemanticSegmentation(NativeModel):
+    _PREFIX = "upernet"
+    _ZERO_LEAVES = ("bias", "relative_position_bias_table")
+    _BAD_TILE = "unsupported tile size {H}x{W}: H and W must be multiples of 32 from 64 to 2048"
+
     def __init__(self, num_channels=3, num_labels=150, embed_dim=96, depths=(2, 2, 18, 2), num_heads=(3, 6, 12, 24), window_size=7,
                  hidden_size=512, pool_scales=(1, 2, 3, 6), auxiliary_in_channels=384, auxiliary_channels=256, compute_dtype=None,
                  initializer_range=0.02):
@@ -85,46 +87,8 @@ class UperNetForSemanticSegmentation(nn.Module):
         L.check(L.lib().flair_upernet_create(C.byref(h), self.num_channels, self.num_labels, int(embed_dim), arr(depths), arr(num_heads),
                                              int(window_size), int(hidden_size), arr(pool_scales), int(auxiliary_in_channels),
                                              int(auxiliary_channels), self._dt), "flair_upernet_create")
-        object.__setattr__(self, "_h", h)
-        self._layout = self._query_layout()
-        self._n = L.lib().flair_upernet_param_count(h)
-        g = torch.Generator().manual_seed(torch.initial_seed() & 0x7FFFFFFF)
-        for name, (shape, off, kind) in self._layout.items():
-            leaf = name.rsplit(".", 1)[1]
-            if kind == 1:
-                t = torch.zeros(shape) if leaf == "running_mean" else torch.ones(shape)
-            elif leaf == "bias" or leaf == "relative_position_bias_table":
-                t = torch.zeros(shape)
-            elif len(shape) == 1:            # LayerNorm / BatchNorm weight
-                t = torch.ones(shape)
-            else:                             # Linear / Conv2d weight
-                t = torch.empty(shape).normal_(0.0, initializer_range, generator=g)
-            self._attach(name, t, kind)
-            if leaf == "running_var":        # BatchNorm2d's counter follows its running statistics in the library's order
-                self._attach(name[:-len("running_var")] + "num_batches_tracked", torch.zeros((), dtype=torch.int64), 1)
-        self._flat = None
-        self._version = -1
-        self._ws = None
+        self._init_tensors(h, initializer_range)
         self.eval()
-
-    _attach = SegformerForSemanticSegmentation._attach
-    _tensor = SegformerForSemanticSegmentation._tensor
-
-    def _query_layout(self):
-        l = L.lib()
-        out = {}
-        name = C.create_string_buffer(160)
-        shape = (C.c_int64 * 4)()
-        nd, kind, off = C.c_int(), C.c_int(), C.c_int64()
-        for i in range(l.flair_upernet_num_tensors(self._h)):
-            L.check(l.flair_upernet_tensor_info(self._h, i, name, 160, shape, C.byref(nd), C.byref(off), C.byref(kind)))
-            out[name.value.decode()] = (tuple(shape[d] for d in range(nd.value)), off.value, kind.value)
-        return out
-
-    def train(self, mode=True):
-        if mode:
-            raise RuntimeError("flair_amd.UperNetForSemanticSegmentation is inference-only (zone_detect never trains)")
-        return super().train(False)
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
         """The library's 5.x keys, or the 4.x keys of the reference's checkpoints (``rename_legacy_keys``).  A 4.x SwinBackbone has
@@ -138,43 +102,6 @@ class UperNetForSemanticSegmentation(nn.Module):
                     sd[k] = own[k].detach().clone()
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
-    def _flatten(self):
-        dev = next(self.parameters()).device
-        if dev.type != "cuda":
-            raise L.FlairHipError("flair_amd.UperNetForSemanticSegmentation runs on a HIP device only: call .cuda() first")
-        ok = self._flat is not None and self._flat.device == dev
-        if ok:
-            base = self._flat.data_ptr()
-            version = 0
-            for name, (shape, off, _) in self._layout.items():
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
-                if t.data_ptr() != base + 4 * off or t.dtype != torch.float32:
-                    ok = False
-                    break
-                version += t._version
-        if ok:
-            if version != self._version:      # an in-place update since the last forward: re-pack the cached layouts
-                self.weights_changed()
-                self._version = version
-            return self._flat
-        flat = torch.zeros(self._n, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for name, (shape, off, _) in self._layout.items():
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
-                view = flat[off:off + math.prod(shape)].view(shape)
-                view.copy_(t.detach().to(device=dev, dtype=torch.float32))
-                t.data = view
-        self._flat = flat
-        self._version = sum(getattr(*self._tensor(name))._version for name in self._layout)
-        self.weights_changed()
-        return flat
-
-    def weights_changed(self):
-        """See SegformerForSemanticSegmentation.weights_changed: call after updating the weights through ``.data`` or raw pointers."""
-        L.lib().flair_upernet_weights_changed(self._h)
-
     @torch.no_grad()
     def forward(self, pixel_values, labels=None, **_):
         if labels is not None:
@@ -184,32 +111,10 @@ class UperNetForSemanticSegmentation(nn.Module):
     @torch.no_grad()
     def forward_full(self, pixel_values):
         """the logits at the input size, (B, labels, H, W) — the same tensor as ``forward(x).logits``"""
-        x = pixel_values
-        if not x.is_cuda:
-            raise L.FlairHipError("flair_amd.UperNetForSemanticSegmentation needs HIP tensors (no CPU fallback)")
-        flat = self._flatten()
-        if x.device != flat.device:
-            raise L.FlairHipError(f"tensor on {x.device} passed to a model on {flat.device}")
-        x = x.detach().to(torch.float32).contiguous()
-        if x.dim() != 4 or x.shape[1] != self.num_channels:
-            raise RuntimeError(f"expected input (B,{self.num_channels},H,W), got {tuple(x.shape)}")
+        flat, x = self._prepare(pixel_values)
         B, _, H, W = x.shape
-        l = L.lib()
         with torch.cuda.device(flat.device):
-            need = l.flair_upernet_workspace_bytes(self._h, B, H, W)
-            if need <= 0:
-                raise RuntimeError(f"unsupported tile size {H}x{W}: H and W must be multiples of 32 from 64 to 2048")
-            if self._ws is None or self._ws.numel() < need or self._ws.device != flat.device:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=flat.device)
             out = torch.empty(B, self.num_labels, H, W, dtype=torch.float32, device=x.device)
-            L.check(l.flair_upernet_forward(self._h, L.ptr(flat), L.ptr(x), L.ptr(out), B, H, W, L.ptr(self._ws), self._ws.numel(),
-                                            L.stream()), "flair_upernet_forward")
+            L.check(L.lib().flair_upernet_forward(self._h, L.ptr(flat), L.ptr(x), L.ptr(out), B, H, W, L.ptr(self._ws), self._ws.numel(),
+                                                  L.stream()), "flair_upernet_forward")
         return out
-
-    def __del__(self):
-        try:
-            h = self.__dict__.get("_h")
-            if h:
-                L.lib().flair_upernet_destroy(h)
-        except Exception:  # noqa: BLE001
-            pass
