@@ -207,12 +207,21 @@ int flair_feed_tiles(const uint8_t* img_u8, const uint8_t* msk_raw, const uint8_
 }
 int flair_detect_convert(const float* logits_nchw, int B, int C, int S, int margin, int output_type, void* out, void* stream) {
   if (!logits_nchw || !out) return -1;
-  return detect_convert(logits_nchw, B, C, S, margin, output_type, out, nullptr, 0, 0, (hipStream_t)stream);
+  return detect_convert(logits_nchw, 1, B, C, S, margin, output_type, out, nullptr, 0, 0, (hipStream_t)stream);
+}
+int flair_detect_convert_q4(const float* logits_nchw, int B, int C, int S, int margin, int output_type, void* out, void* stream) {
+  if (!logits_nchw || !out) return -1;
+  return detect_convert(logits_nchw, 4, B, C, S, margin, output_type, out, nullptr, 0, 0, (hipStream_t)stream);
 }
 int flair_detect_stitch(const float* logits_nchw, int B, int C, int S, int margin, int output_type, const int32_t* tiles,
                         void* raster_out, int raster_h, int raster_w, void* stream) {
   if (!logits_nchw || !raster_out || !tiles) return -1;
-  return detect_convert(logits_nchw, B, C, S, margin, output_type, raster_out, tiles, raster_h, raster_w, (hipStream_t)stream);
+  return detect_convert(logits_nchw, 1, B, C, S, margin, output_type, raster_out, tiles, raster_h, raster_w, (hipStream_t)stream);
+}
+int flair_detect_stitch_q4(const float* logits_nchw, int B, int C, int S, int margin, int output_type, const int32_t* tiles,
+                           void* raster_out, int raster_h, int raster_w, void* stream) {
+  if (!logits_nchw || !raster_out || !tiles) return -1;
+  return detect_convert(logits_nchw, 4, B, C, S, margin, output_type, raster_out, tiles, raster_h, raster_w, (hipStream_t)stream);
 }
 int flair_detect_stitch_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
                               float* raster_out, int raster_h, int raster_w, void* stream) {
@@ -222,7 +231,13 @@ int flair_detect_stitch_preds(const uint8_t* preds_u8, const float* maxprob_f32,
 int flair_detect_blend_accum(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
                              int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream) {
   if (!logits_nchw || !tiles || !ring) return -1;
-  return detect_blend_accum(logits_nchw, B, C, S, margin, tiles, cheb_weights, x_lo, x_hi, y_lo, y_hi, ring, raster_h, raster_w,
+  return detect_blend_accum(logits_nchw, 1, B, C, S, margin, tiles, cheb_weights, x_lo, x_hi, y_lo, y_hi, ring, raster_h, raster_w,
+                            (hipStream_t)stream);
+}
+int flair_detect_blend_accum_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
+                                int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream) {
+  if (!logits_nchw || !tiles || !ring) return -1;
+  return detect_blend_accum(logits_nchw, 4, B, C, S, margin, tiles, cheb_weights, x_lo, x_hi, y_lo, y_hi, ring, raster_h, raster_w,
                             (hipStream_t)stream);
 }
 int flair_detect_blend_flush(float* ring, int C, int ring_cols, int x_lo, int x_hi, float* raster_out, int raster_h, int raster_w,
@@ -233,13 +248,19 @@ int flair_detect_blend_flush(float* ring, int C, int ring_cols, int x_lo, int x_
 int flair_detect_stitch_max(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
                             int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream) {
   if (!logits_nchw || !tiles || !raster_out) return -1;
-  return detect_stitch_max(logits_nchw, nullptr, nullptr, B, C, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
+  return detect_stitch_max(logits_nchw, 1, nullptr, nullptr, B, C, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
+                           raster_w, (hipStream_t)stream);
+}
+int flair_detect_stitch_max_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
+                               int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream) {
+  if (!logits_nchw || !tiles || !raster_out) return -1;
+  return detect_stitch_max(logits_nchw, 4, nullptr, nullptr, B, C, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
                            raster_w, (hipStream_t)stream);
 }
 int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
                                   int x_lo, int x_hi, int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream) {
   if (!preds_u8 || !maxprob_f32 || !tiles || !raster_out) return -1;
-  return detect_stitch_max(nullptr, preds_u8, maxprob_f32, B, 0, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
+  return detect_stitch_max(nullptr, 1, preds_u8, maxprob_f32, B, 0, S, margin, tiles, x_lo, x_hi, y_lo, y_hi, raster_out, raster_h,
                            raster_w, (hipStream_t)stream);
 }
 int flair_zone_window_confmat_preds(const uint8_t* preds_u8, int B, int C, int S, int margin, const int32_t* tiles,
@@ -251,6 +272,12 @@ int flair_zone_window_confmat_logits(const float* logits_nchw, int B, int C, int
                                      const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream) {
   if (!logits_nchw || !tiles || !truth_u8 || !confmats) return -1;
   return zone_window_confmat(1, logits_nchw, B, C, S, margin, tiles, truth_u8, raster_h, raster_w, (long long*)confmats,
+                             (hipStream_t)stream);
+}
+int flair_zone_window_confmat_logits_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles,
+                                        const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream) {
+  if (!logits_nchw || !tiles || !truth_u8 || !confmats) return -1;
+  return zone_window_confmat(3, logits_nchw, B, C, S, margin, tiles, truth_u8, raster_h, raster_w, (long long*)confmats,
                              (hipStream_t)stream);
 }
 int flair_zone_window_confmat_raster(const float* raster, int B, int C, int S, int margin, const int32_t* tiles, const uint8_t* truth_u8,
@@ -725,7 +752,14 @@ int flair_upernet_forward(flair_upernet_t* h, const float* params, const float* 
                           size_t wsb, void* stream) {
   if (!h) return -1;
   if (!UperNet::shape_ok(H, W)) return -14;
-  return h->net.forward(params, x_nchw, logits_nchw, B, H, W, ws, wsb, (hipStream_t)stream);
+  return h->net.forward(params, x_nchw, logits_nchw, B, H, W, ws, wsb, (hipStream_t)stream, false);
+}
+int flair_upernet_forward_quarter(flair_upernet_t* h, const float* params, const float* x_nchw, float* logits_quarter_nchw, int B, int H,
+                                  int W, void* ws, size_t wsb, void* stream) {
+  if (!h) return -1;
+  if (!UperNet::shape_ok(H, W)) return -14;
+  if ((H % 4) || (W % 4)) return -2;
+  return h->net.forward(params, x_nchw, logits_quarter_nchw, B, H, W, ws, wsb, (hipStream_t)stream, true);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 //                   src/zone_detect/compare.py:35,71-76; src/zone_detect/dataset.py:11-34.
 //   confmat_masks   offline evaluation: confusion matrix of (truth raster - 1) against a prediction raster.
 //                   src/flair/metrics.py:60-75.
+#include "logit_source.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -105,10 +106,12 @@ __global__ __launch_bounds__(256) void gather_tiles_kernel(FeedArgs a, const int
   }
 }
 
-// one thread per kept pixel; logits NCHW fp32, so a wave reads 256 contiguous bytes per class plane
+// one thread per kept pixel; SRC = FullLogits: logits NCHW fp32, so a wave reads 256 contiguous bytes per class plane;
+// SRC = QuarterLogits: logits (B, C, S/4, S/4), interpolated x4 in registers (logit_source.h)
 // tiles == null: out is the per-tile (B, 2 | C, K, K) result.  Otherwise out is the whole (2 | C, Hr, Wr) output raster
 // and tile b = {x0, y0, wx0, wx1, wy0, wy1}: its pixel (i, j) lands at (y0 + i, x0 + j) if inside the write window
 // (the part of its margin-cropped centre that no later tile of the slicing job overwrites).
+template <class SRC>
 __global__ __launch_bounds__(256) void detect_convert_kernel(const float* __restrict__ logits, int B, int C, int S, int margin,
                                                              int mode, void* __restrict__ out, const int* __restrict__ tiles,
                                                              int Hr, int Wr) {
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(256) void detect_convert_kernel(const float* __rest
     const int b = (int)(t / KK);
     const long r = t - (long)b * KK;
     const int i = (int)(r / K), j = (int)(r - (long)i * K);
-    const float* p = logits + (long)b * C * SS + (long)(i + margin) * S + (j + margin);
+    const SRC src(logits, b, C, S, SS, i + margin, j + margin);
     long obase = (long)b * (mode == 0 ? 2 : C) * KK + r, ostride = KK;   // mode 2 ('probs'): C fp32 planes
     if (tiles) {
       const int* tb = tiles + b * 6;
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(256) void detect_convert_kernel(const float* __rest
     float m = -INFINITY;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c)
-      if (c < C) { x[c] = p[(long)c * SS]; m = fmaxf(m, x[c]); }
+      if (c < C) { x[c] = src(c); m = fmaxf(m, x[c]); }
     float ssum = 0.f;
 #pragma unroll
     for (int c = 0; c < MAXC; ++c)
@@ -236,14 +239,22 @@ int feed_tiles(const FeedArgs& a, hipStream_t s) {
   return 0;
 }
 
-int detect_convert(const float* logits, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,
+int detect_convert(const float* logits, int up, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,
                    hipStream_t s) {
   if (C < 1 || C > MAXC || B < 1 || margin < 0 || S - 2 * margin < 1 || mode < 0 || mode > 2 || (tiles && mode == 2)) return -2;
   if (tiles && (Hr < 1 || Wr < 1)) return -2;
+  if ((up != 1 && up != 4) || S % up) return -2;
   const long K = S - 2 * margin;
-  ProfScope ps(tiles ? "detect_stitch" : "detect_convert", 0.0, (double)B * K * K * (4.0 * C + (mode == 2 ? 4.0 * C : mode ? C : 8.0)), s);
-  hipLaunchKernelGGL(detect_convert_kernel, dim3(stream_blocks((long)B * K * K)), dim3(256), 0, s, logits, B, C, S, margin, mode, out,
-                     tiles, Hr, Wr);
+  const double bytes = (double)B * K * K * (4.0 * C / (up * up) + (mode == 2 ? 4.0 * C : mode ? C : 8.0));
+  const dim3 grid(stream_blocks((long)B * K * K));
+  if (up == 4) {
+    ProfScope ps(tiles ? "detect_stitch_q4" : "detect_convert_q4", 0.0, bytes, s);
+    hipLaunchKernelGGL(detect_convert_kernel<QuarterLogits>, grid, dim3(256), 0, s, logits, B, C, S, margin, mode, out, tiles, Hr, Wr);
+    FLAIR_CHECK_LAUNCH();
+    return 0;
+  }
+  ProfScope ps(tiles ? "detect_stitch" : "detect_convert", 0.0, bytes, s);
+  hipLaunchKernelGGL(detect_convert_kernel<FullLogits>, grid, dim3(256), 0, s, logits, B, C, S, margin, mode, out, tiles, Hr, Wr);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }

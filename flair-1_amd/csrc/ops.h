@@ -106,17 +106,19 @@ int feed_tiles(const FeedArgs& a, hipStream_t s);
 int gather_tiles(const FeedArgs& a, const int* tiles, int Hr, int Wr, hipStream_t s);  // a.img: one (Cb, Hr, Wr) raster
 int detect_stitch_preds(const unsigned char* preds, const float* maxprob, int B, int S, int margin, const int* tiles, float* out,
                         int Hr, int Wr, hipStream_t s);
-int detect_convert(const float* logits, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,
+// `up` of the logits consumers: 1 = logits (B, C, S, S); 4 = (B, C, S/4, S/4), interpolated x4 per pixel (csrc/logit_source.h)
+int detect_convert(const float* logits, int up, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,
                    hipStream_t s);
 // zone_detect overlap stitching (csrc/zone_stitch.hip); rectangles are [x_lo, x_hi) x [y_lo, y_hi) of the raster
-int detect_blend_accum(const float* logits, int B, int C, int S, int margin, const int* tiles, const float* wtab, int x_lo, int x_hi,
+int detect_blend_accum(const float* logits, int up, int B, int C, int S, int margin, const int* tiles, const float* wtab, int x_lo, int x_hi,
                        int y_lo, int y_hi, float* ring, int Hr, int Wr, hipStream_t s);
 int detect_blend_flush(float* ring, int C, int K, int x_lo, int x_hi, float* out, int Hr, int Wr, hipStream_t s);
-int detect_stitch_max(const float* logits, const unsigned char* preds, const float* maxprob, int B, int C, int S, int margin,
+int detect_stitch_max(const float* logits, int up, const unsigned char* preds, const float* maxprob, int B, int C, int S, int margin,
                       const int* tiles, int x_lo, int x_hi, int y_lo, int y_hi, float* out, int Hr, int Wr, hipStream_t s);
 int confmat_masks(const unsigned char* truth, const unsigned char* pred, long n, int C, int truth_offset, long long* confmat,
                   hipStream_t s);
-// zone_detect metrics (csrc/zone_metrics.hip); source 0: u8 class tiles (B, S, S), 1: fp32 logits (B, C, S, S), 2: fp32 raster
+// zone_detect metrics (csrc/zone_metrics.hip); source 0: u8 class tiles (B, S, S), 1: fp32 logits (B, C, S, S), 2: fp32 raster,
+// 3: fp32 quarter-resolution logits (B, C, S/4, S/4)
 int zone_window_confmat(int source, const void* pred, int B, int C, int S, int margin, const int* tiles, const unsigned char* truth,
                         int Hr, int Wr, long long* confmats, hipStream_t s);
 int zone_raster_confmat(const float* band, const unsigned char* truth, int Hr, int Wr, int C, long long* confmat, hipStream_t s);

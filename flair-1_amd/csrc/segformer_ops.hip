@@ -8,6 +8,7 @@
 
 #include <type_traits>
 
+#include "bilinear_src.h"
 #include "prof.h"
 #include "tune.h"
 
@@ -184,15 +185,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 }
 
 // ------------------------------------------------------------------------------------------------------ bilinear resize
-// nn.functional.interpolate(mode='bilinear', align_corners=False): src = max(0, (dst + 0.5) * in / out - 0.5)
-__device__ __forceinline__ void bilinear_src(int dst, int in, int out, int& i0, int& i1, float& l1) {
-  float s = ((float)dst + 0.5f) * ((float)in / (float)out) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
+// bilinear_src (bilinear_src.h): nn.functional.interpolate(mode='bilinear', align_corners=False)
 
 // NHWC [B][h][w][C] -> a channel slice of NHWC [B][H][W][ld] (the decode head's concatenation buffer)
 template <typename T>

@@ -4,6 +4,7 @@
 // conv_hg.hip.  Activations are token-major [B * H * W][C] = NHWC, T = float (parity mode, exact-fp32 MFMA) or bf16.
 #include "swin_ops.h"
 
+#include "bilinear_src.h"
 #include "prof.h"
 
 namespace flair {
@@ -307,15 +308,6 @@ __global__ __launch_bounds__(256) void swin_avgpool_kernel(const T* __restrict__
   }
 }
 
-// nn.functional.interpolate(mode='bilinear', align_corners=False): src = max(0, (dst + 0.5) * in / out - 0.5)
-__device__ __forceinline__ void bilinear_src(int dst, int in, int out, int& i0, int& i1, float& l1) {
-  float s = ((float)dst + 0.5f) * ((float)in / (float)out) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in - 1) i0 = in - 1;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
 
 // y += bilinear(x), both dense NHWC; the sum in fp32, rounded once
 template <typename T>

@@ -20,8 +20,10 @@ class UperNet : public TfExec {
   static bool shape_ok(int H, int W);
   int max_batch(int H, int W) const;   // images per internal pass (every tensor below 2^31 elements)
   size_t workspace_bytes(int B, int H, int W);
-  // logits: fp32 NCHW (B, labels, H, W) = the library's `.logits` (decode head at 1/4 resolution, then bilinear to the input size)
-  int forward(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s);
+  // logits: fp32 NCHW (B, labels, H, W) = the library's `.logits` (decode head at 1/4 resolution, then bilinear to the input size);
+  // quarter: (B, labels, H/4, W/4), the classifier's own output, and no x4 pass
+  int forward(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s,
+              bool quarter);
 
  private:
   std::vector<SwStage> stages;
@@ -34,7 +36,8 @@ class UperNet : public TfExec {
   int add_cbn(const std::string& name, int cin, int cout, int k);
   void conv_bn_relu(int i, const void* in, int B, int Hin, int Win, void* out, int out_ld);
   void layernorm(const SfNorm& n, const void* x, void* y, long rows, int ld);
-  int run(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s, bool dry);
+  int run(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s, bool dry,
+          bool quarter);
 };
 
 }  // namespace flair

@@ -102,7 +102,7 @@ void UperNet::layernorm(const SfNorm& n, const void* x, void* y, long rows, int 
 }
 
 int UperNet::run(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s,
-                 bool dry) {
+                 bool dry, bool quarter) {
   if (!shape_ok(H, W)) return -10;
   const size_t es = dtype_size(dtype);
   // ---- what depends on the weights alone (packed operands, fused q / k / v, folded BatchNorm) sits at the front of the arena
@@ -210,23 +210,26 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
   void* z = alloc((size_t)B * fh[0] * fw[0] * D * es);
   conv_bn_relu(fpn_bottleneck, fcat, B, fh[0], fw[0], z, D);
   float* lq = (float*)alloc((size_t)B * num_labels * fh[0] * fw[0] * 4);
-  gemm(lins[cls], z, B, fh[0], fw[0], nullptr, 0, nullptr, nullptr, nullptr, 0, lq);   // 1x1 conv + bias: fp32 NCHW at 1/4
-  TF_RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
+  // 1x1 conv + bias: fp32 NCHW at 1/4, for a quarter-resolution caller straight into its tensor (the workspace plan is the same)
+  gemm(lins[cls], z, B, fh[0], fw[0], nullptr, 0, nullptr, nullptr, nullptr, 0, quarter ? logits : lq);
+  if (!quarter) TF_RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
   return end();
 }
 
 size_t UperNet::workspace_bytes(int B, int H, int W) {
   const int bc = max_batch(H, W);
-  return planned(run(nullptr, nullptr, reinterpret_cast<float*>(16), B < bc ? B : bc, H, W, nullptr, 0, nullptr, true));
+  return planned(run(nullptr, nullptr, reinterpret_cast<float*>(16), B < bc ? B : bc, H, W, nullptr, 0, nullptr, true, false));
 }
 
-int UperNet::forward(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s) {
+int UperNet::forward(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s,
+                     bool quarter) {
   if (!params || !x_nchw || !logits || !ws || B < 1) return -1;
   const int bc = max_batch(H, W);
   for (int b0 = 0; b0 < B; b0 += bc) {   // passes of at most bc images through the same workspace
     const int nb = B - b0 < bc ? B - b0 : bc;
-    const int rc = run(params, x_nchw + (size_t)b0 * in_channels * H * W, logits + (size_t)b0 * num_labels * H * W, nb, H, W, ws, ws_bytes,
-                       s, false);
+    const size_t out_px = quarter ? (size_t)(H / 4) * (W / 4) : (size_t)H * W;
+    const int rc = run(params, x_nchw + (size_t)b0 * in_channels * H * W, logits + (size_t)b0 * num_labels * out_px, nb, H, W, ws, ws_bytes,
+                       s, false, quarter);
     if (rc) return rc;
   }
   return 0;

@@ -9,6 +9,7 @@
 //                    / P, then scipy.ndimage.gaussian_filter (mode 'reflect') in fp64
 // Every count is an integer: LDS-privatised u32 histograms flushed with integer atomics, so the matrices do not depend on the
 // launch shape or the batch split.  No float atomics.
+#include "logit_source.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -19,7 +20,7 @@ namespace {
 constexpr int MAXC = 32;
 constexpr int CHUNKS_PER_BLOCK = 2048;   // 4-pixel chunks of one window per block (8 per thread)
 
-enum { SRC_PREDS = 0, SRC_LOGITS = 1, SRC_RASTER = 2 };
+enum { SRC_PREDS = 0, SRC_LOGITS = 1, SRC_RASTER = 2, SRC_LOGITS_Q4 = 3 };
 
 // numpy: uint8 raster - 1 wraps 0 -> 255; sklearn drops a pair whose truth or prediction lies outside range(C)
 __device__ __forceinline__ unsigned truth_class(unsigned raw) { return (raw + 255u) & 0xffu; }
@@ -27,12 +28,13 @@ __device__ __forceinline__ unsigned truth_class(unsigned raw) { return (raw + 25
 __device__ __forceinline__ unsigned float_class(float v) { return (v >= 0.f && v < 256.f) ? (unsigned)(int)v : 0xffu; }
 
 // the class detect_convert_kernel writes for 'argmax': softmax in fp32, first index of the largest probability
-__device__ __forceinline__ unsigned logits_class(const float* __restrict__ p, long plane, int C) {
+template <class LSRC>
+__device__ __forceinline__ unsigned logits_class(const LSRC& src, int C) {
   float x[MAXC];
   float m = -INFINITY;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c)
-    if (c < C) { x[c] = p[(long)c * plane]; m = fmaxf(m, x[c]); }
+    if (c < C) { x[c] = src(c); m = fmaxf(m, x[c]); }
   float ssum = 0.f;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c)
@@ -61,6 +63,7 @@ __device__ __forceinline__ void flush_hist(const unsigned* hist, int C, long lon
 
 // grid (blocks per window, B); a block walks 4-pixel chunks (row i, columns 4q .. 4q+3) of window b's K x K core.
 // A chunk reads its truth (and u8 / fp32 class) bytes with one vector load when the addresses allow it, else byte by byte.
+// SRC_LOGITS_Q4: pred is the quarter-resolution (B, C, S/4, S/4) logits, interpolated per pixel (logit_source.h).
 template <int SRC>
 __global__ __launch_bounds__(256) void window_confmat_kernel(const void* __restrict__ pred, int C, int S, int margin,
                                                              const int* __restrict__ tiles, const unsigned char* __restrict__ truth,
@@ -84,7 +87,8 @@ __global__ __launch_bounds__(256) void window_confmat_kernel(const void* __restr
         const unsigned tc = truth_class(truth[(long)gy * Wr + x]);
         unsigned pc;
         if (SRC == SRC_PREDS) pc = reinterpret_cast<const unsigned char*>(pred)[b * SS + (long)(i + margin) * S + j + e + margin];
-        else if (SRC == SRC_LOGITS) pc = logits_class(reinterpret_cast<const float*>(pred) + b * C * SS + (long)(i + margin) * S + j + e + margin, SS, C);
+        else if (SRC == SRC_LOGITS) pc = logits_class(FullLogits(reinterpret_cast<const float*>(pred) + b * C * SS + (long)(i + margin) * S + j + e + margin, SS), C);
+        else if (SRC == SRC_LOGITS_Q4) pc = logits_class(QuarterLogits(reinterpret_cast<const float*>(pred), b, C, S, SS, i + margin, j + e + margin), C);
         else pc = float_class(reinterpret_cast<const float*>(pred)[(long)gy * Wr + x]);
         count(hist, tc, pc, C);
       }
@@ -113,7 +117,11 @@ __global__ __launch_bounds__(256) void window_confmat_kernel(const void* __restr
     } else if (SRC == SRC_LOGITS) {
       const float* pp = reinterpret_cast<const float*>(pred) + b * C * SS + (long)(i + margin) * S + j + margin;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) pc[e] = e < n ? logits_class(pp + e, SS, C) : 0xffu;
+      for (int e = 0; e < 4; ++e) pc[e] = e < n ? logits_class(FullLogits(pp + e, SS), C) : 0xffu;
+    } else if (SRC == SRC_LOGITS_Q4) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        pc[e] = e < n ? logits_class(QuarterLogits(reinterpret_cast<const float*>(pred), b, C, S, SS, i + margin, j + e + margin), C) : 0xffu;
     } else {
       const float* pp = reinterpret_cast<const float*>(pred) + (long)gy * Wr + gx;   // band 0 of (2, H, W)
       if (n == 4 && !((uintptr_t)pp & 15)) {
@@ -244,19 +252,22 @@ inline int blocks_for(long items) {
 
 int zone_window_confmat(int source, const void* pred, int B, int C, int S, int margin, const int* tiles, const unsigned char* truth,
                         int Hr, int Wr, long long* confmats, hipStream_t s) {
-  if (source < SRC_PREDS || source > SRC_RASTER || C < 1 || C > MAXC || B < 0 || margin < 0 || S - 2 * margin < 1 || Hr < 1 || Wr < 1)
+  if (source < SRC_PREDS || source > SRC_LOGITS_Q4 || C < 1 || C > MAXC || B < 0 || margin < 0 || S - 2 * margin < 1 || Hr < 1 || Wr < 1)
     return -2;
+  if (source == SRC_LOGITS_Q4 && S % 4) return -2;
   if (B == 0) return 0;
   const long K = S - 2 * margin, nchunk = K * ((K + 3) / 4);
   const long nblk = (nchunk + CHUNKS_PER_BLOCK - 1) / CHUNKS_PER_BLOCK;
   const int per_window = (int)(nblk < 256 ? nblk : 256);
-  const double bytes = (double)B * K * K * (1.0 + (source == SRC_PREDS ? 1.0 : source == SRC_LOGITS ? 4.0 * C : 4.0));
-  ProfScope ps("zone_window_confmat", 0.0, bytes, s);
+  const double bytes = (double)B * K * K * (1.0 + (source == SRC_PREDS ? 1.0 : source == SRC_LOGITS ? 4.0 * C : source == SRC_LOGITS_Q4 ? 0.25 * C : 4.0));
+  ProfScope ps(source == SRC_LOGITS_Q4 ? "zone_window_confmat_q4" : "zone_window_confmat", 0.0, bytes, s);
   const dim3 grid(per_window, B);
   if (source == SRC_PREDS)
     hipLaunchKernelGGL(window_confmat_kernel<SRC_PREDS>, grid, dim3(256), 0, s, pred, C, S, margin, tiles, truth, Hr, Wr, confmats);
   else if (source == SRC_LOGITS)
     hipLaunchKernelGGL(window_confmat_kernel<SRC_LOGITS>, grid, dim3(256), 0, s, pred, C, S, margin, tiles, truth, Hr, Wr, confmats);
+  else if (source == SRC_LOGITS_Q4)
+    hipLaunchKernelGGL(window_confmat_kernel<SRC_LOGITS_Q4>, grid, dim3(256), 0, s, pred, C, S, margin, tiles, truth, Hr, Wr, confmats);
   else
     hipLaunchKernelGGL(window_confmat_kernel<SRC_RASTER>, grid, dim3(256), 0, s, pred, C, S, margin, tiles, truth, Hr, Wr, confmats);
   FLAIR_CHECK_LAUNCH();

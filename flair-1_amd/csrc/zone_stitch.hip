@@ -10,6 +10,7 @@
 //   blend_flush   finished ring columns -> convert('argmax') of sum(w p) / sum(w) into the (2, H, W) raster; zeroes them
 //   stitch_max    running (class, probability) per pixel in the (2, H, W) raster; a later window wins unless the past
 //                 probability is strictly greater (compare.py:135-136, on the confidence band)
+#include "logit_source.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -21,6 +22,8 @@ constexpr int MAXC = 32;
 
 __device__ __forceinline__ bool covers(int v, int o, int S, int margin) { return v >= o + margin && v < o + S - margin; }
 
+// SRC (logit_source.h): FullLogits reads (B, C, S, S); QuarterLogits interpolates (B, C, S/4, S/4) x4 in registers
+template <class SRC>
 __global__ __launch_bounds__(256) void blend_accum_kernel(const float* __restrict__ logits, int B, int C, int S, int margin,
                                                           const int* __restrict__ tiles, const float* __restrict__ wtab,
                                                           int x_lo, int y_lo, int rw, int rh, float* __restrict__ ring, int Hr) {
@@ -42,12 +45,12 @@ __global__ __launch_bounds__(256) void blend_accum_kernel(const float* __restric
         any = true;
       }
       const int i = y - y0, j = x - x0;
-      const float* p = logits + (long)b * C * SS + (long)i * S + j;
+      const SRC src(logits, b, C, S, SS, i, j);
       float v[MAXC];
       float m = -INFINITY;
 #pragma unroll
       for (int c = 0; c < MAXC; ++c)
-        if (c < C) { v[c] = p[(long)c * SS]; m = fmaxf(m, v[c]); }
+        if (c < C) { v[c] = src(c); m = fmaxf(m, v[c]); }
       float ssum = 0.f;
 #pragma unroll
       for (int c = 0; c < MAXC; ++c)
@@ -92,6 +95,7 @@ __global__ __launch_bounds__(256) void blend_flush_kernel(float* __restrict__ ri
 }
 
 // preds != null: the (class, probability) maps of flair_unet_want_preds; otherwise softmax + first argmax of the logits
+template <class SRC>
 __global__ __launch_bounds__(256) void stitch_max_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ preds,
                                                          const float* __restrict__ maxprob, int B, int C, int S, int margin,
                                                          const int* __restrict__ tiles, int x_lo, int y_lo, int rw, int rh,
@@ -113,12 +117,12 @@ __global__ __launch_bounds__(256) void stitch_max_kernel(const float* __restrict
         best = preds[(long)b * SS + src];
         pbest = maxprob[(long)b * SS + src];
       } else {
-        const float* p = logits + (long)b * C * SS + src;
+        const SRC lsrc(logits, b, C, S, SS, y - y0, x - x0, src);
         float v[MAXC];
         float m = -INFINITY;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
-          if (c < C) { v[c] = p[(long)c * SS]; m = fmaxf(m, v[c]); }
+          if (c < C) { v[c] = lsrc(c); m = fmaxf(m, v[c]); }
         float ssum = 0.f;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c)
@@ -149,16 +153,25 @@ inline bool rect_ok(int x_lo, int x_hi, int y_lo, int y_hi, int Hr, int Wr) {
 
 }  // namespace
 
-int detect_blend_accum(const float* logits, int B, int C, int S, int margin, const int* tiles, const float* wtab, int x_lo, int x_hi,
+int detect_blend_accum(const float* logits, int up, int B, int C, int S, int margin, const int* tiles, const float* wtab, int x_lo, int x_hi,
                        int y_lo, int y_hi, float* ring, int Hr, int Wr, hipStream_t s) {
   if (C < 1 || C > MAXC || B < 1 || margin < 0 || S - 2 * margin < 1 || !rect_ok(x_lo, x_hi, y_lo, y_hi, Hr, Wr)) return -2;
   if (x_hi - x_lo > S - 2 * margin) return -2;  // two columns of the rectangle would share a ring column
+  if ((up != 1 && up != 4) || S % up) return -2;
   const long px = (long)(x_hi - x_lo) * (y_hi - y_lo);
   if (px == 0) return 0;
   const long K = S - 2 * margin;
-  ProfScope ps("detect_blend_accum", 0.0, (double)B * K * K * 4.0 * C + (double)px * 8.0 * (C + 1), s);
-  hipLaunchKernelGGL(blend_accum_kernel, dim3(stream_blocks(px)), dim3(256), 0, s, logits, B, C, S, margin, tiles, wtab, x_lo, y_lo,
-                     x_hi - x_lo, y_hi - y_lo, ring, Hr);
+  const double bytes = (double)B * K * K * 4.0 * C / (up * up) + (double)px * 8.0 * (C + 1);
+  if (up == 4) {
+    ProfScope ps("detect_blend_accum_q4", 0.0, bytes, s);
+    hipLaunchKernelGGL(blend_accum_kernel<QuarterLogits>, dim3(stream_blocks(px)), dim3(256), 0, s, logits, B, C, S, margin, tiles, wtab,
+                       x_lo, y_lo, x_hi - x_lo, y_hi - y_lo, ring, Hr);
+    FLAIR_CHECK_LAUNCH();
+    return 0;
+  }
+  ProfScope ps("detect_blend_accum", 0.0, bytes, s);
+  hipLaunchKernelGGL(blend_accum_kernel<FullLogits>, dim3(stream_blocks(px)), dim3(256), 0, s, logits, B, C, S, margin, tiles, wtab, x_lo,
+                     y_lo, x_hi - x_lo, y_hi - y_lo, ring, Hr);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }
@@ -173,15 +186,24 @@ int detect_blend_flush(float* ring, int C, int K, int x_lo, int x_hi, float* out
   return 0;
 }
 
-int detect_stitch_max(const float* logits, const unsigned char* preds, const float* maxprob, int B, int C, int S, int margin,
+int detect_stitch_max(const float* logits, int up, const unsigned char* preds, const float* maxprob, int B, int C, int S, int margin,
                       const int* tiles, int x_lo, int x_hi, int y_lo, int y_hi, float* out, int Hr, int Wr, hipStream_t s) {
   if ((!preds && (C < 1 || C > MAXC)) || B < 1 || margin < 0 || S - 2 * margin < 1 || !rect_ok(x_lo, x_hi, y_lo, y_hi, Hr, Wr)) return -2;
+  if ((up != 1 && up != 4) || S % up || (preds && up != 1)) return -2;
   const long px = (long)(x_hi - x_lo) * (y_hi - y_lo);
   if (px == 0) return 0;
   const long K = S - 2 * margin;
-  ProfScope ps("detect_stitch_max", 0.0, (double)B * K * K * (preds ? 5.0 : 4.0 * C) + (double)px * 16.0, s);
-  hipLaunchKernelGGL(stitch_max_kernel, dim3(stream_blocks(px)), dim3(256), 0, s, logits, preds, maxprob, B, C, S, margin, tiles, x_lo,
-                     y_lo, x_hi - x_lo, y_hi - y_lo, out, Hr, Wr);
+  const double bytes = (double)B * K * K * (preds ? 5.0 : 4.0 * C / (up * up)) + (double)px * 16.0;
+  if (up == 4) {
+    ProfScope ps("detect_stitch_max_q4", 0.0, bytes, s);
+    hipLaunchKernelGGL(stitch_max_kernel<QuarterLogits>, dim3(stream_blocks(px)), dim3(256), 0, s, logits, preds, maxprob, B, C, S, margin,
+                       tiles, x_lo, y_lo, x_hi - x_lo, y_hi - y_lo, out, Hr, Wr);
+    FLAIR_CHECK_LAUNCH();
+    return 0;
+  }
+  ProfScope ps("detect_stitch_max", 0.0, bytes, s);
+  hipLaunchKernelGGL(stitch_max_kernel<FullLogits>, dim3(stream_blocks(px)), dim3(256), 0, s, logits, preds, maxprob, B, C, S, margin, tiles,
+                     x_lo, y_lo, x_hi - x_lo, y_hi - y_lo, out, Hr, Wr);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }

@@ -105,6 +105,11 @@ PROTOTYPES = {
     "flair_detect_stitch_max_preds": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_zone_window_confmat_preds": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "flair_zone_window_confmat_logits": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+    "flair_detect_convert_q4": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
+    "flair_detect_stitch_q4": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
+    "flair_detect_blend_accum_q4": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "flair_detect_stitch_max_q4": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
+    "flair_zone_window_confmat_logits_q4": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "flair_zone_window_confmat_raster": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "flair_zone_raster_confmat": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "flair_zone_error_map": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, vp, vp, vp]),
@@ -124,6 +129,7 @@ PROTOTYPES = {
     "flair_upernet_workspace_bytes": (i64, [vp, i32, i32, i32]),
     "flair_upernet_weights_changed": (None, [vp]),
     "flair_upernet_forward": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
+    "flair_upernet_forward_quarter": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, sz, vp]),
     "flair_tune_set": (i32, [C.c_char_p, i32]),
     "flair_debug_buffer": (i32, [vp]),
 }

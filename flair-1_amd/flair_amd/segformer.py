@@ -82,3 +82,9 @@ class SegformerForSemanticSegmentation(NativeModel):
     def forward_full(self, pixel_values):
         """logits after nn.functional.interpolate(size=input size, mode='bilinear', align_corners=False): (B, labels, H, W)"""
         return self._run(pixel_values, False, True)[1]
+
+    @torch.no_grad()
+    def forward_quarter(self, pixel_values):
+        """the decode head's own output, (B, labels, H/4, W/4) fp32 — the same tensor as ``forward(x).logits`` — for the
+        zone_detect consumers of quarter-resolution logits (``detect_convert(..., upsample=4)``)"""
+        return self._run(pixel_values, True, False)[0]

@@ -118,3 +118,15 @@ class UperNetForSemanticSegmentation(NativeModel):
             L.check(L.lib().flair_upernet_forward(self._h, L.ptr(flat), L.ptr(x), L.ptr(out), B, H, W, L.ptr(self._ws), self._ws.numel(),
                                                   L.stream()), "flair_upernet_forward")
         return out
+
+    @torch.no_grad()
+    def forward_quarter(self, pixel_values):
+        """the classifier's own output, (B, labels, H/4, W/4) fp32: ``forward_full`` is its x4 bilinear resize, which the
+        zone_detect consumers of quarter-resolution logits apply per pixel instead (``detect_convert(..., upsample=4)``)"""
+        flat, x = self._prepare(pixel_values)
+        B, _, H, W = x.shape
+        with torch.cuda.device(flat.device):
+            out = torch.empty(B, self.num_labels, H // 4, W // 4, dtype=torch.float32, device=x.device)
+            L.check(L.lib().flair_upernet_forward_quarter(self._h, L.ptr(flat), L.ptr(x), L.ptr(out), B, H, W, L.ptr(self._ws),
+                                                          self._ws.numel(), L.stream()), "flair_upernet_forward_quarter")
+        return out

@@ -12,8 +12,16 @@ modes 'average', 'average_weights' and 'max' (compare.py:84-136 as DESIGN §8 st
 by the gather-form kernels of csrc/zone_stitch.hip.  ``compare`` is the comparison loop without file I/O or metrics;
 ``run(raster, truth)`` also counts every window's confusion matrix on the device, and ``zone_metrics.evaluate`` is the
 comparison loop with metrics (main.py:255-372 with --metrics).
+
+The HuggingFace-provider models (SegFormer, UperNet) classify at 1/4 of the tile size and the library resizes x4 (bilinear,
+align_corners=False) to the tile.  A model with ``forward_quarter`` hands its (B, C, S/4, S/4) logits straight to the ``_q4``
+kernels, which interpolate per output pixel in registers: the tile-sized fp32 tensor is never written.
+``FLAIR_ZD_QUARTER=1`` / ``=0`` (read when a ``ZoneDetector`` is built) selects that path / the x4 pass and the full-resolution
+kernels; unset, ``QUARTER_DEFAULT`` decides.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -22,18 +30,26 @@ from . import _lib as L
 
 OUTPUT_TYPES = {"argmax": 0, "class_prob": 1}   # the values config["output_type"] may take (compare.py:69-82)
 _MODE_PROBS = 2                                   # private: every fp32 softmax probability, no convert (compare.py:35)
+# ZoneDetector's path for models with forward_quarter when FLAIR_ZD_QUARTER is unset.  DESIGN §10 sets the bar for True: windows/s
+# of scripts/bench_zone_detect.py (MODEL=segformer) and scripts/bench_upernet.py within 2 % of the x4 path's on the same box.
+QUARTER_DEFAULT = False
 _MAX_GRID_Y = 65535                               # windows per launch of the per-window confusion matrices (grid.y)
 
 
-def detect_convert(logits: torch.Tensor, margin: int, output_type: str, _probs: bool = False) -> torch.Tensor:
+def detect_convert(logits: torch.Tensor, margin: int, output_type: str, upsample: int = 1, _probs: bool = False) -> torch.Tensor:
     """softmax(dim=1) -> [:, m:S-m, m:S-m] -> convert(., output_type) for a batch of square tiles.
-    'argmax' -> float32 (B, 2, K, K); 'class_prob' -> uint8 (B, C, K, K)."""
+    'argmax' -> float32 (B, 2, K, K); 'class_prob' -> uint8 (B, C, K, K).
+    ``upsample=4``: the logits are (B, C, S/4, S/4) and are resized x4 (bilinear, align_corners=False) per output pixel inside
+    the kernel; ``margin`` and K are in full-resolution pixels."""
     if not _probs and output_type not in OUTPUT_TYPES:
         raise ValueError("The output type has not been interpreted.")
+    if upsample not in (1, 4):
+        raise ValueError(f"upsample must be 1 or 4, not {upsample!r}")
     if logits.dim() != 4 or logits.shape[2] != logits.shape[3]:
         raise ValueError("logits must be (B, C, S, S)")
     logits = logits.detach().float().contiguous()
-    B, C, S, _ = logits.shape
+    B, C = logits.shape[:2]
+    S = logits.shape[2] * upsample
     K = S - 2 * int(margin)
     if K < 1:
         raise ValueError("margin leaves no pixel")
@@ -43,8 +59,9 @@ def detect_convert(logits: torch.Tensor, margin: int, output_type: str, _probs: 
         out = torch.empty(B, 2, K, K, dtype=torch.float32, device=logits.device)
     else:
         out = torch.empty(B, C, K, K, dtype=torch.uint8, device=logits.device)
-    L.check(L.lib().flair_detect_convert(L.ptr(logits), B, C, S, int(margin), _MODE_PROBS if _probs else OUTPUT_TYPES[output_type], L.ptr(out),
-                                         L.stream()), "flair_detect_convert")
+    name = "flair_detect_convert_q4" if upsample == 4 else "flair_detect_convert"
+    L.check(getattr(L.lib(), name)(L.ptr(logits), B, C, S, int(margin), _MODE_PROBS if _probs else OUTPUT_TYPES[output_type], L.ptr(out),
+                                   L.stream()), name)
     return out
 
 
@@ -55,13 +72,23 @@ def inference(device, model, use_gpu: bool, config: dict, samples: dict, fused: 
         raise RuntimeError("flair_amd.zone_detect.inference runs on a HIP device only")
     imgs = samples["image"].to(device, non_blocking=True)
     with torch.no_grad():
-        logits = model(imgs)
+        up = 1
         if config.get("model_framework", {}).get("model_provider") == "HuggingFace":
-            logits = logits.logits
+            # the library's `.logits` of a SegFormer are 1/4 of the tile: softmax, margin crop and convert work at tile geometry,
+            # so quarter logits go through the kernels that resize x4 per pixel, never through the full-resolution ones
+            if hasattr(model, "forward_quarter") and imgs.shape[2] % 4 == 0 and imgs.shape[3] % 4 == 0:
+                logits, up = model.forward_quarter(imgs), 4
+            else:
+                logits = model(imgs).logits
+                if tuple(logits.shape[2:]) != tuple(imgs.shape[2:]):
+                    raise ValueError(f"the model's .logits are {tuple(logits.shape[2:])} for tiles of {tuple(imgs.shape[2:])}: margin crop "
+                                     "and convert need tile-sized logits, or a model with forward_quarter (1/4-size logits)")
+        else:
+            logits = model(imgs)
         if fused:
-            predictions = detect_convert(logits, config["margin"], config["output_type"])
+            predictions = detect_convert(logits, config["margin"], config["output_type"], upsample=up)
         else:   # the reference's own return value: every probability, uncropped (same HIP kernel, no ATen op on the path)
-            predictions = detect_convert(logits, 0, "", _probs=True)
+            predictions = detect_convert(logits, 0, "", upsample=up, _probs=True)
     indices = samples["index"].cpu().numpy()
     return predictions.cpu().numpy(), indices
 
@@ -204,10 +231,18 @@ class OverlapStitch:
                                                      self.H, self.W, L.stream()), "flair_detect_blend_flush")
             self._flushed = hi
 
-    def add(self, b0: int, tiles: torch.Tensor, logits: torch.Tensor = None, preds: torch.Tensor = None, prob: torch.Tensor = None):
-        """tiles: the device rows of job windows [b0, b0 + B); logits fp32 (B, C, S, S), or (preds u8, prob f32) (B, S, S)
-        from predict_classes (method 'max' only)."""
+    def add(self, b0: int, tiles: torch.Tensor, logits: torch.Tensor = None, preds: torch.Tensor = None, prob: torch.Tensor = None,
+            logits_q: torch.Tensor = None):
+        """tiles: the device rows of job windows [b0, b0 + B); logits fp32 (B, C, S, S), or logits_q fp32 (B, C, S/4, S/4)
+        (resized x4 per pixel in the kernel), or (preds u8, prob f32) (B, S, S) from predict_classes (method 'max' only)."""
         B = tiles.shape[0]
+        q4 = "_q4" if logits_q is not None else ""
+        if q4:
+            if logits is not None or preds is not None:
+                raise ValueError("logits_q excludes logits and preds")
+            if self.S % 4 or tuple(logits_q.shape[2:]) != (self.S // 4, self.S // 4):
+                raise ValueError(f"logits_q must be (B, C, {self.S} / 4, {self.S} / 4) with a patch size divisible by 4")
+            logits = logits_q
         cuts = [b0] + [b for b in range(b0 + 1, b0 + B) if self._col_start[b]] + [b0 + B]
         for s, e in zip(cuts[:-1], cuts[1:]):
             x0 = int(self.grid[s, 0])
@@ -222,16 +257,17 @@ class OverlapStitch:
                                                                L.stream())
                     L.check(rc, "flair_detect_stitch_max_preds")
                 else:
-                    rc = L.lib().flair_detect_stitch_max(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
-                                                         x_lo, x_hi, y_lo, y_hi, L.ptr(self.out), self.H, self.W, L.stream())
-                    L.check(rc, "flair_detect_stitch_max")
+                    fn = "flair_detect_stitch_max" + q4
+                    rc = getattr(L.lib(), fn)(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
+                                              x_lo, x_hi, y_lo, y_hi, L.ptr(self.out), self.H, self.W, L.stream())
+                    L.check(rc, fn)
                 continue
             if self._col_start[s]:
                 self._flush(min(x0 + self.m, self.W))
-            rc = L.lib().flair_detect_blend_accum(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
-                                                  L.ptr(self.wtab), x_lo, x_hi, y_lo, y_hi, L.ptr(self.ring), self.H, self.W,
-                                                  L.stream())
-            L.check(rc, "flair_detect_blend_accum")
+            fn = "flair_detect_blend_accum" + q4
+            rc = getattr(L.lib(), fn)(L.ptr(logits[s - b0:e - b0]), e - s, self.C, self.S, self.m, L.ptr(t),
+                                      L.ptr(self.wtab), x_lo, x_hi, y_lo, y_hi, L.ptr(self.ring), self.H, self.W, L.stream())
+            L.check(rc, fn)
 
     def finish(self) -> torch.Tensor:
         if self.ring is not None:
@@ -286,6 +322,9 @@ class ZoneDetector:
         self._stds = (C.c_double * n)(*[float(s) for s in stds[:n]]) if self.norm_type == "custom" else None
         self.n_classes = int(config["n_classes"])
         self.classes = config.get("classes")
+        # quarter-resolution logits straight into the _q4 kernels (no x4 pass, no tile-sized logits); FLAIR_ZD_QUARTER=0: the x4 path
+        want = os.environ.get("FLAIR_ZD_QUARTER", "1" if QUARTER_DEFAULT else "0") != "0"
+        self.quarter = want and hasattr(model, "forward_quarter") and self.S % 4 == 0
         self.window_confmats = None   # run(raster, truth): (n, C, C) int64 on the device, one per window in job order
         self.window_rects = None      # and their (col_off, row_off, width, height) core rectangles, numpy int32 (n, 4)
 
@@ -322,6 +361,13 @@ class ZoneDetector:
         if logits.shape[1] != self.n_classes:
             raise RuntimeError(f"model returned {logits.shape[1]} classes, config says {self.n_classes}")
         return logits
+
+    def _logits_quarter(self, imgs: torch.Tensor) -> torch.Tensor:
+        logits = self.model.forward_quarter(imgs)
+        if logits.shape[1] != self.n_classes or tuple(logits.shape[2:]) != (self.S // 4, self.S // 4) or logits.dtype != torch.float32:
+            raise RuntimeError(f"forward_quarter returned {tuple(logits.shape)} {logits.dtype}, expected fp32 "
+                               f"(B, {self.n_classes}, {self.S // 4}, {self.S // 4})")
+        return logits.contiguous()
 
     @torch.no_grad()
     def run(self, raster_u8: torch.Tensor, truth_u8: torch.Tensor = None) -> torch.Tensor:
@@ -363,6 +409,8 @@ class ZoneDetector:
                 if self.blend == "max" and self._fast_preds(mode):
                     preds, prob = self.model.predict_classes(imgs, want_prob=True)
                     blend.add(b0, tiles, preds=preds, prob=prob)
+                elif self.quarter:
+                    blend.add(b0, tiles, logits_q=self._logits_quarter(imgs))
                 else:
                     blend.add(b0, tiles, logits=self._logits(imgs))
                 continue
@@ -375,13 +423,13 @@ class ZoneDetector:
                                                                     L.ptr(truth_u8), Hr, Wr, L.ptr(confmats[b0:b0 + B]), L.stream()),
                             "flair_zone_window_confmat_preds")
                 continue
-            logits = self._logits(imgs)
-            L.check(L.lib().flair_detect_stitch(L.ptr(logits), B, self.n_classes, self.S, self.margin, mode, L.ptr(tiles),
-                                                L.ptr(out), Hr, Wr, L.stream()), "flair_detect_stitch")
+            logits, q4 = (self._logits_quarter(imgs), "_q4") if self.quarter else (self._logits(imgs), "")
+            L.check(getattr(L.lib(), "flair_detect_stitch" + q4)(L.ptr(logits), B, self.n_classes, self.S, self.margin, mode, L.ptr(tiles),
+                                                                 L.ptr(out), Hr, Wr, L.stream()), "flair_detect_stitch" + q4)
             if confmats is not None:
-                L.check(L.lib().flair_zone_window_confmat_logits(L.ptr(logits), B, self.n_classes, self.S, self.margin, L.ptr(tiles),
-                                                                 L.ptr(truth_u8), Hr, Wr, L.ptr(confmats[b0:b0 + B]), L.stream()),
-                        "flair_zone_window_confmat_logits")
+                fn = "flair_zone_window_confmat_logits" + q4
+                L.check(getattr(L.lib(), fn)(L.ptr(logits), B, self.n_classes, self.S, self.margin, L.ptr(tiles), L.ptr(truth_u8), Hr, Wr,
+                                             L.ptr(confmats[b0:b0 + B]), L.stream()), fn)
         if blend is not None:
             out = blend.finish()
             if confmats is not None:   # an overlap method's window is scored on the finished raster

@@ -190,6 +190,20 @@ int flair_detect_stitch_max(const float* logits_nchw, int B, int C, int S, int m
                             int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
 int flair_detect_stitch_max_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
                                   int x_lo, int x_hi, int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
+/* The _q4 family: the function of the same name without the suffix, argument for argument, except that logits_nchw is the
+ * QUARTER-resolution fp32 (B, C, S/4, S/4) tensor a HuggingFace-provider model's classifier writes (flair_segformer_forward's
+ * logits_quarter_nchw, flair_upernet_forward_quarter).  S, margin, tiles and every rectangle stay in tile / raster pixels.  Each
+ * thread computes, for its own pixel, the value nn.functional.interpolate(scale_factor=4, mode="bilinear", align_corners=False)
+ * gives there — the arithmetic of flair_sf_bilinear_nchw_f32, operation for operation — and goes on as the full-resolution
+ * function does, so the (B, C, S, S) tensor is never written.  S % 4 != 0 returns -2, as does whatever the full-resolution
+ * function rejects. */
+int flair_detect_convert_q4(const float* logits_nchw, int B, int C, int S, int margin, int output_type, void* out, void* stream);
+int flair_detect_stitch_q4(const float* logits_nchw, int B, int C, int S, int margin, int output_type, const int32_t* tiles,
+                           void* raster_out, int raster_h, int raster_w, void* stream);
+int flair_detect_blend_accum_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
+                                int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream);
+int flair_detect_stitch_max_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
+                               int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
 
 /* zone_detect's comparison metrics against a ground-truth raster (src/zone_detect/test/metrics.py; csrc/zone_metrics.hip).
  * truth_u8 (raster_h, raster_w): the stored label raster; its class is (truth - 1) in uint8 arithmetic, so a 0 becomes 255.
@@ -209,6 +223,9 @@ int flair_zone_window_confmat_preds(const uint8_t* preds_u8, int B, int C, int S
                                     const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream);
 int flair_zone_window_confmat_logits(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles,
                                      const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream);
+/* as flair_zone_window_confmat_logits from quarter-resolution logits (B, C, S/4, S/4): see the _q4 family above */
+int flair_zone_window_confmat_logits_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles,
+                                        const uint8_t* truth_u8, int raster_h, int raster_w, int64_t* confmats, void* stream);
 int flair_zone_window_confmat_raster(const float* raster, int B, int C, int S, int margin, const int32_t* tiles, const uint8_t* truth_u8,
                                      int raster_h, int raster_w, int64_t* confmats, void* stream);
 int flair_zone_raster_confmat(const float* raster, const uint8_t* truth_u8, int raster_h, int raster_w, int C, int64_t* confmat,
@@ -410,6 +427,10 @@ void flair_upernet_weights_changed(flair_upernet_t* h);
 /* logits_nchw: fp32 (B, labels, H, W) = the library's `.logits` (already resized to the input size) */
 int flair_upernet_forward(flair_upernet_t* h, const float* params, const float* x_nchw, float* logits_nchw, int B, int H, int W,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* logits_quarter_nchw: fp32 (B, labels, H/4, W/4), the classifier's output before the resize to the input size (what the _q4
+ * zone_detect functions consume); the same passes through the same workspace as flair_upernet_forward.  H % 4 or W % 4: -2. */
+int flair_upernet_forward_quarter(flair_upernet_t* h, const float* params, const float* x_nchw, float* logits_quarter_nchw, int B, int H,
+                                  int W, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostic tuning switch (kernel-variant A/B timing inside one process; keys are the FLAIR_* environment
  * variables DESIGN.md lists, the environment supplies the default).  Returns 0. */
