@@ -419,7 +419,7 @@ int launch_conv(int dtype, const ConvArgs& a, hipStream_t s) {
   if (a.out_sub && (a.out_nchw || a.stats || a.pool_c0 > 0 || a.bnr_partial || conv_hg_applicable(dtype, a) || conv_halo_applicable(a)))
     return -6;  // sub-sampled stores exist in the gather-form epilogue only
   // input / epilogue options only the halo-GEMM kernels implement (fused BN-backward apply, addend from another tensor, masked store)
-  if ((a.ap_y || a.acc_src || a.bnr_mask) && !conv_hg_applicable(dtype, a)) return -6;
+  if ((a.acc_src || a.bnr_mask) && !conv_hg_applicable(dtype, a)) return -6;
   if (a.acc_src && !conv_acc_src_ok(dtype, a)) return -6;
   if (a.bnr_mask && !a.bnr_partial) return -6;
   // the GELU epilogue exists in the gather-form kernel only

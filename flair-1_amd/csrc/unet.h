@@ -179,7 +179,9 @@ class UNet {
   // set by the BasicBlock walk just before the backward of a block's conv1: its data gradient adds this tensor (the masked
   // gradient of the block's output = the identity branch's share) instead of reading a copy of it from its own output buffer
   const void* acc_src_next_ = nullptr;
-  bool bwd_fuse() const;   // FLAIR_BWD_FUSE (default on): masked gradients + BatchNorm-backward apply inside the halo-GEMM data gradients
+  // FLAIR_BWD_FUSE (0 / 1, default on): the halo-GEMM data gradients store their result masked by the consumer unit's ReLU, the
+  // BatchNorm-backward apply pass then reads no mask source, and the identity branch takes the masked gradient without a copy
+  bool bwd_fuse() const;
   void* grad_of(const Act& a, bool* accumulate);
   void* grad_peek(const Act& a);
 

@@ -628,10 +628,10 @@ bool UNet::bwd_fuse() const { return tune("FLAIR_BWD_FUSE", 1) != 0; }
 // output when the unit was not materialised).  Produces parameter gradients, optionally the
 // residual-branch gradient dz (dres) and the input gradient (into grad_of(in0) or dx_override).
 //
-// Round 3: when the kernel that completed dout stored it masked by this unit's ReLU (Unit::bnr_masked) and the unit's data
-// gradient runs on the halo-GEMM, that kernel applies  dy = k1*dz + k2*y + k3  itself while it stages its halo and writes dy
-// once for the weight-gradient kernel, which is then forked BEHIND it: bn_bwd_apply (read dz, read y, write dy; for residual
-// units also read out, write dres) does not run for the unit.
+// FLAIR_BWD_FUSE (bwd_fuse(), default on): the halo-GEMM data gradient that completed dout stored it masked by this unit's ReLU
+// (Unit::bnr_masked), so dout is dz already.  bn_bwd_apply then needs no mask source (no read of `out` for residual units, no
+// recomputation of relu'(y) for the others), and the identity branch of a BasicBlock takes dz as it stands (acc_src_next_) instead
+// of a copy written as dres.
 void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bool need_dgrad, void* dx_override,
                          bool upcat) {
   Unit& u = units_[ui];
@@ -729,19 +729,11 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
       }
     }
   }
-  // fused BatchNorm-backward apply inside the data gradient: dout is dz already (masked), nobody else wants dz (dres)
-  bool fuse_dy = false;
-  if (masked && !dres && tune("FLAIR_BWD_FUSE", 1) >= 2 && (dg == DG_PLAIN || dg == DG_UPCAT_TILE)) {
-    ConvArgs t = a;
-    t.src0 = dout; t.ap_y = u.y.p; t.ap_coef = coef; t.ap_dy = dy;
-    if (conv_bnapply_fusable(dtype, t)) { a = t; fuse_dy = true; }
-  }
-
   // a masked gradient needs no mask source in the apply pass: the residual units' read of `out` and the others' recomputation
   // of relu'(y) go (bn_backward still needs one on paper when it runs the reduction itself, which it does not here: pre_nblk > 0)
   const bool nomask = masked && !dres && bwd_fuse();
   RUN(bn_backward(dtype, dout, (u.relu && !mask_from_y && !nomask) ? u.out.p : nullptr, u.y.p, u.mean, u.invstd, params_ + b.g_off,
-                  rows, b.C, partial, coef, grads_ + b.g_off, grads_ + b.b_off, 0, (fuse_apply || fuse_dy) ? nullptr : dy, dres,
+                  rows, b.C, partial, coef, grads_ + b.g_off, grads_ + b.b_off, 0, fuse_apply ? nullptr : dy, dres,
                   dres_acc ? 1 : 0, (mask_from_y && !nomask) ? u.scale : nullptr, (mask_from_y && !nomask) ? u.shift : nullptr,
                   pre_nblk, nomask ? 1 : 0, s_));
   if (fuse_apply) { w.dy = dout; w.fuse_y = u.y.p; w.fuse_coef = coef; w.fuse_msc = u.scale; w.fuse_msh = u.shift; }
@@ -749,11 +741,10 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   w.in_scale = u.in0.lz_scale; w.in_shift = u.in0.lz_shift;
   w.cus = side_cus(ui);
   w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
-  auto launch_wg = [&]() {
+  {
     hipStream_t ws = wgrad_stream();   // dy is complete on s_; nothing later on s_ writes what this kernel reads
     RUN(launch_wgrad(dtype, w, ws));
-  };
-  if (!fuse_dy) launch_wg();
+  }
   switch (dg) {
     case DG_NONE: break;
     case DG_UPCAT_SPLIT:
@@ -763,7 +754,6 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
     default:
       RUN(launch_conv(dtype, a, s_));
   }
-  if (fuse_dy) launch_wg();   // dy was written by the data gradient's staging pass
 }
 
 void UNet::head_bwd_impl(const void* dl) {

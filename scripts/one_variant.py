@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Compile ONE instantiation of the LDS-DMA halo-GEMM kernel (seconds instead of minutes) and print its register use.
-    python scripts/one_variant.py "bf16_t, 16, 8, 128, 1, 3, true, XF_APPLY" [-D...]
+    python scripts/one_variant.py "bf16_t, 16, 8, 128, 1, 3, true, XF_NONE" [-D...]
 Leaves the assembly in /tmp/one/ for reading."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
