@@ -53,6 +53,7 @@ const char* flair_strerror(int code) {
     case -12: return "gradient buffer already initialised";
     case -13: return "internal side stream: event record / wait failed";
     case -14: return "UperNet-Swin tile size: height and width must be multiples of 32 from 64 to 2048";
+    case -15: return "flair_unet_want_ce: needs an eval-mode forward without fp32 logits and without a flair_unet_want_preds request";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -91,6 +92,15 @@ int flair_unet_head_ld(const flair_unet_t* h) { return h ? h->net.convs.back().C
 int flair_unet_want_preds(flair_unet_t* h, uint8_t* preds_u8, float* maxprob_f32) {
   if (!h || (maxprob_f32 && !preds_u8)) return -1;
   h->net.want_preds(preds_u8, maxprob_f32);
+  return 0;
+}
+int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, const float* class_weight, float* loss,
+                       uint8_t* preds_u8, int64_t* confmat, void* ce_workspace) {
+  if (!h || !labels || !loss || !ce_workspace || label_kind < 0 || label_kind > 3) return -1;
+  UNet::CeReq r;
+  r.labels = labels; r.kind = label_kind; r.weight = class_weight; r.loss = loss; r.preds = preds_u8;
+  r.confmat = (long long*)confmat; r.ws = (float*)ce_workspace;
+  h->net.want_ce(r);
   return 0;
 }
 int flair_unet_reuse_constants(flair_unet_t* h, int on) {

@@ -12,7 +12,6 @@
 namespace flair {
 
 constexpr int MAXC = 32;
-constexpr int CE_MAX_BLOCKS = 2048;
 
 static inline int ce_blocks(long npix) {
   long b = (npix + 255) / 256;
@@ -350,22 +349,48 @@ __global__ __launch_bounds__(256) void ce_main_nhwc_kernel(const T* __restrict__
   }
 }
 
+CeWorkspace ce_workspace_layout(float* ws, long npix) {
+  CeWorkspace w;
+  w.lab8 = reinterpret_cast<unsigned char*>(ws);
+  w.den_partial = ws + (npix + 3) / 4;
+  w.loss_partial = w.den_partial + CE_MAX_BLOCKS;
+  w.den = w.loss_partial + CE_MAX_BLOCKS;
+  return w;
+}
+
+// labels of any kind -> lab8, sum of w[y] over the valid ones -> den
+int ce_labels(const void* labels, int kind, const float* weight, int B, int C, int H, int W, int* targets_i32, float* ws, hipStream_t s) {
+  const long HW = (long)H * W, npix = HW * B;
+  const int nb = ce_blocks(npix);
+  const CeWorkspace w = ce_workspace_layout(ws, npix);
+  ProfScope* p1 = new ProfScope("ce_labels", 0.0, (double)npix * (kind == 3 ? 4.0 * C : 1.0), s);
+  hipLaunchKernelGGL(ce_labels_kernel, dim3(nb), dim3(256), 0, s, labels, kind, weight, C, HW, npix, w.lab8, targets_i32, w.den_partial);
+  FLAIR_CHECK_LAUNCH();
+  delete p1;
+  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, s, w.den_partial, nb, w.den, (const float*)nullptr);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+// loss = (fp64 sum of the first nblk loss partials) / den
+int ce_finish(float* ws, long npix, int nblk, float* loss, hipStream_t s) {
+  if (nblk < 1 || nblk > CE_MAX_BLOCKS) return -2;
+  const CeWorkspace w = ce_workspace_layout(ws, npix);
+  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, s, w.loss_partial, nblk, loss, w.den);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
 int ce_head(const CeArgs& a, hipStream_t s) {
   if (a.C > MAXC || a.C < 1) return -2;
   if (a.dlogits_nhwc && (a.dlogits_ld < a.C || a.dlogits_ld > MAXC || a.dlogits_ld % (a.dlogits_dtype == DT_F32 ? 4 : 8))) return -3;
   const long HW = (long)a.H * a.W, npix = HW * a.B;
   const int nb = ce_blocks(npix);
-  unsigned char* lab8 = reinterpret_cast<unsigned char*>(a.workspace);
-  float* den_partial = a.workspace + (npix + 3) / 4;
-  float* loss_partial = den_partial + CE_MAX_BLOCKS;
-  float* den = loss_partial + CE_MAX_BLOCKS;
-  ProfScope* p1 = new ProfScope("ce_labels", 0.0, (double)npix * (a.label_kind == 3 ? 4.0 * a.C : 1.0), s);
-  hipLaunchKernelGGL(ce_labels_kernel, dim3(nb), dim3(256), 0, s, a.labels, a.label_kind, a.weight, a.C, HW, npix, lab8,
-                     a.targets_i32, den_partial);
-  FLAIR_CHECK_LAUNCH();
-  delete p1;
-  hipLaunchKernelGGL(ce_sum_kernel, dim3(1), dim3(256), 0, s, den_partial, nb, den, (const float*)nullptr);
-  FLAIR_CHECK_LAUNCH();
+  const CeWorkspace wsl = ce_workspace_layout(a.workspace, npix);
+  unsigned char* lab8 = wsl.lab8;
+  float* loss_partial = wsl.loss_partial;
+  float* den = wsl.den;
+  if (int rc = ce_labels(a.labels, a.label_kind, a.weight, a.B, a.C, a.H, a.W, a.targets_i32, a.workspace, s)) return rc;
   if (a.logits_nhwc) {
     const int ld = a.logits_ld;
     if ((ld != 16 && ld != 24 && ld != 32) || ld < a.C || a.dlogits_nchw || a.preds_i64 || (a.dlogits_nhwc && (a.dlogits_ld != ld || a.dlogits_dtype != a.logits_dtype)))

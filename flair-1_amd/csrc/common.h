@@ -154,9 +154,20 @@ struct ConvArgs {
   // of this gradient need no mask source (halo-GEMM epilogue only)
   int bnr_mask;  // optional exact (erf) GELU on the output, after the bias: the fc1 of a Swin MLP (gather-form kernel only, NHWC output)
   int ogelu;
+  // optional (CE flavour of the persistent small-channel kernel, conv_halo_ce_ok()): the per-pixel head of the reference's step() on
+  // the Cout logits of every pixel while they sit in registers — weighted cross-entropy terms and the confusion-matrix bincount next
+  // to the epilogue argmax (preds_u8 stays optional); `out` may then be null.  Same arithmetic as ce_main_nhwc_kernel.
+  const unsigned char* ce_lab8;   // labels [N][H][W] as ce_labels_kernel writes them: 255 (anything >= Cout) = ignored
+  const float* ce_weight;         // optional [Cout] class weights
+  float* ce_loss_partial;         // [gridDim.x]: sum of w[y] * nll over the workgroup's pixels (conv_grid_rows() entries)
+  long long* ce_confmat;          // optional int64 [Cout][Cout], confmat[target][pred] += 1 for valid labels
 };
 bool conv_acc_src_ok(int dtype, const ConvArgs& a);        // a.acc_src set: does the kernel launch_conv picks honour it?
 bool conv_halo_preds_ok(int dtype, const ConvArgs& a);
+// tune key FLAIR_HEAD_CE.  Off by default: measured against head convolution + ce_head the CE flavour is 2.7 % slower with 13 classes in
+// bf16 (beyond the run-to-run spread), level in fp32 and 1.6 % faster with 19 classes in bf16 (profiles/validate_step.json)
+constexpr int FLAIR_HEAD_CE_DEFAULT = 0;
+bool conv_halo_ce_ok(int dtype, const ConvArgs& a);         // a.ce_lab8 set: is the CE flavour available for this shape?
 
 int launch_conv(int dtype, const ConvArgs& a, hipStream_t s);
 int conv_grid_rows(int dtype, const ConvArgs& a);  // number of row blocks (= partial-stat rows)

@@ -8,6 +8,7 @@
 // shifted fragment reads; K is walked tap-major in chunks of CK input channels.  Same operands, epilogue
 // (LDS transpose -> 16-byte NHWC stores / fp32 NCHW logits, BN partial sums) and numerics as conv_igemm.
 #include "common.h"
+#include "ops.h"
 #include "prof.h"
 #include "tile_store.h"
 #include "tile_direct.h"
@@ -275,17 +276,20 @@ int launch_halo_cfg_l(const ConvArgs& a, hipStream_t s) {
 // workgroup overlaps the LDS/MFMA phase of its neighbours only by luck.  Here a workgroup keeps the weights in LDS for
 // the whole launch, walks many tiles, prefetches the next tile's halo into registers while the current one is
 // multiplied, and keeps its BatchNorm partial statistics in registers ([2][Cout][gridDim.x] partials).
-template <typename T, int CK, int BN>
+// CE (the flavour with the per-pixel head in its epilogue, ConvArgs::ce_lab8) appends its histogram, class weights and reduction
+// scratch (DirectCe) behind the statistics; the other flavours keep their size, which the occupancy query sizes their grids by
+template <typename T, int CK, int BN, bool CE = false>
 struct HaloPCfg {
   using B = HaloCfg<T, CK, BN>;
   static constexpr int WOFF = 0, HOFF = (B::WBYTES + 255) / 256 * 256, SOFF = HOFF + (B::HALO + 255) / 256 * 256;
-  static constexpr int SMEM = SOFF + B::STATS;   // no C tile: the epilogue goes from registers to HBM (tile_direct.h)
+  static constexpr int CEOFF = SOFF + B::STATS;
+  static constexpr int SMEM = SOFF + B::STATS + (CE ? DirectCe::LDS_BYTES : 0);   // no C tile: the epilogue goes from registers to HBM (tile_direct.h)
 };
 
-template <typename T, int CK, int BN, bool LZ, bool BNR = false>
+template <typename T, int CK, int BN, bool LZ, bool BNR = false, bool CE = false>
 __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, int ntiles) {
   using Cfg = HaloCfg<T, CK, BN>;
-  using PC = HaloPCfg<T, CK, BN>;
+  using PC = HaloPCfg<T, CK, BN, CE>;
   constexpr int CH = Cfg::CH, KF = Cfg::KF, CPP = Cfg::CPP, TN = BN / 16, TM = 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* wl = smem + PC::WOFF;
@@ -329,6 +333,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
   for (int e = 0; e < 4 * TN; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
   DirectBnr<TN> bn;
   if constexpr (BNR) bn.init(a, 0, lq);
+  DirectCe ce;
+  if constexpr (CE) ce.init(a, smem + PC::CEOFF, t);   // (visible after the barrier behind the first halo_store)
 
   // Two register slots: the halo of tile i + 2 is requested while tile i is multiplied (the MFMA phase of a 16-32-channel tile
   // is ~0.3 us, an HBM round trip under load ~2 us: with one slot every iteration waited for its loads)
@@ -434,7 +440,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
       const int n = tile / (tiles_x * tiles_y);
       const int trem = tile - n * tiles_x * tiles_y;
       const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
-      direct_store<T, TW, TN, !BNR, BNR>(a, acc, n, y0, x0, 0, wave, lane, cf, s1, s2, &bn);   // (a data gradient has no affine / statistics)
+      if constexpr (CE) direct_store<T, TW, TN, true, false, true>(a, acc, n, y0, x0, 0, wave, lane, cf, s1, s2, nullptr, &ce);
+      else direct_store<T, TW, TN, !BNR, BNR>(a, acc, n, y0, x0, 0, wave, lane, cf, s1, s2, &bn);   // (a data gradient has no affine / statistics)
     }
     __syncthreads();   // every wave is done with the halo
     halo_store(stg, stbits);
@@ -444,6 +451,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
     do_tile(tile, hregA, hbitsA, hregB, hbitsB);   // slot A went to LDS before this tile; B holds the next one
     if (tile + gridDim.x < ntiles) do_tile(tile + gridDim.x, hregB, hbitsB, hregA, hbitsA);
   }
+  if constexpr (CE) ce.finish(a, t);   // one loss partial per workgroup: the grid is a function of the shape and the tune state only
   if constexpr (BNR) {   // one partial per workgroup and channel, like the statistics: [2][bnr_C][gridDim.x]
     direct_stats_wave<TN>(bn.r1, bn.r2, st, BN, 0, wave, lane);
     __syncthreads();
@@ -481,15 +489,15 @@ static bool conv_halo_bnr_ok(const ConvArgs& a) {
 // persistent grid = the workgroups that are resident at once (registers and LDS: asked from the runtime once per variant; a
 // grid above that runs its surplus as a second, unbalanced round — 16 -> 16 at 512^2: 141 us with 4 per CU against 125 with the
 // 3 that fit).  Without a device (planning on a CPU-only host) the LDS bound stands in.
-template <typename T, int CK, int BN, bool LZ, bool BNR = false>
+template <typename T, int CK, int BN, bool LZ, bool BNR = false, bool CE = false>
 int halo_p_per_cu() {
   static const int per_cu = [] {
-    int lds = (160 * 1024) / HaloPCfg<T, CK, BN>::SMEM;
+    int lds = (160 * 1024) / HaloPCfg<T, CK, BN, CE>::SMEM;
     lds = lds > 4 ? 4 : (lds < 1 ? 1 : lds);
     int nb = 0;
-    auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloPCfg<T, CK, BN>::SMEM) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, HaloPCfg<T, CK, BN>::SMEM) != hipSuccess || nb < 1) {
+    auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloPCfg<T, CK, BN, CE>::SMEM) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, HaloPCfg<T, CK, BN, CE>::SMEM) != hipSuccess || nb < 1) {
       (void)hipGetLastError();
       return lds;
     }
@@ -502,15 +510,18 @@ int halo_p_per_cu() {
 template <typename T, int CK, int BN>
 int halo_p_blocks(const ConvArgs& a) {
   const long ntiles = (long)a.N * a.Hout * a.Wout / (TH * TW);
-  const long cap = 256L * (a.bnr_partial ? halo_p_per_cu<T, CK, BN, false, true>()
-                                         : a.in_scale ? halo_p_per_cu<T, CK, BN, true>() : halo_p_per_cu<T, CK, BN, false>());
+  long cap = 256L * (a.bnr_partial ? halo_p_per_cu<T, CK, BN, false, true>()
+                                   : a.in_scale ? halo_p_per_cu<T, CK, BN, true>() : halo_p_per_cu<T, CK, BN, false>());
+  if constexpr (CK == 16) {   // (the head's 16 input channels: the only CE instances, conv_halo_ce_ok)
+    if (a.ce_lab8) cap = 256L * halo_p_per_cu<T, CK, BN, false, false, true>();
+  }
   return (int)(ntiles < cap ? ntiles : cap);
 }
 
-template <typename T, int CK, int BN, bool LZ, bool BNR = false>
+template <typename T, int CK, int BN, bool LZ, bool BNR = false, bool CE = false>
 int launch_halo_p_l(const ConvArgs& a, hipStream_t s) {
-  using PC = HaloPCfg<T, CK, BN>;
-  auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR>;
+  using PC = HaloPCfg<T, CK, BN, CE>;
+  auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PC::SMEM);
@@ -532,6 +543,10 @@ int launch_halo_p_l(const ConvArgs& a, hipStream_t s) {
 
 template <typename T, int CK, int BN>
 int launch_halo_p(const ConvArgs& a, hipStream_t s) {
+  if (a.ce_lab8) {
+    if constexpr (CK == 16) return launch_halo_p_l<T, CK, BN, false, false, true>(a, s);
+    return -6;
+  }
   if (a.bnr_partial) return conv_halo_bnr_ok(a) ? launch_halo_p_l<T, CK, BN, false, true>(a, s) : -6;
   return a.in_scale ? launch_halo_p_l<T, CK, BN, true>(a, s) : launch_halo_p_l<T, CK, BN, false>(a, s);
 }
@@ -778,10 +793,18 @@ int conv_halo_grid_rows(int dtype, const ConvArgs& a) {
   return (int)((long)a.N * a.Hout * a.Wout / (TH * TW));
 }
 
+// fused per-pixel head (ConvArgs::ce_lab8): the same kernel, fed by the head's 16 materialised input channels, one loss partial per
+// workgroup into the CE workspace
+bool conv_halo_ce_ok(int dtype, const ConvArgs& a) {
+  return tune("FLAIR_HEAD_CE", FLAIR_HEAD_CE_DEFAULT) && conv_halo_preds_ok(dtype, a) && a.C0 + a.C1 == 16 && !a.in_scale && !a.stats &&
+         a.ce_loss_partial && conv_halo_grid_rows(dtype, a) <= CE_MAX_BLOCKS;
+}
+
 int launch_conv_halo(int dtype, const ConvArgs& a, hipStream_t s) {
   const int Cin = a.C0 + a.C1;
   const bool n16 = a.Cout <= 16;
   if (a.preds_u8 && !conv_halo_preds_ok(dtype, a)) return -6;
+  if (a.ce_lab8 && !conv_halo_ce_ok(dtype, a)) return -6;
   if (halo_persistent_multi(dtype, a))
     return a.in_scale ? launch_halo_pm_l<bf16_t, 32, 32, 4, true>(a, s) : launch_halo_pm_l<bf16_t, 32, 32, 4, false>(a, s);
   if (halo_persistent(a)) {

@@ -416,6 +416,7 @@ static int launch_t(const ConvArgs& a, hipStream_t s) {
 
 int launch_conv(int dtype, const ConvArgs& a, hipStream_t s) {
   if (a.preds_u8 && !conv_halo_preds_ok(dtype, a)) return -6;   // fused argmax: persistent small-channel kernel only
+  if (a.ce_lab8 && !conv_halo_ce_ok(dtype, a)) return -6;       // fused per-pixel head: its CE flavour only
   if (a.out_sub && (a.out_nchw || a.stats || a.pool_c0 > 0 || a.bnr_partial || conv_hg_applicable(dtype, a) || conv_halo_applicable(a)))
     return -6;  // sub-sampled stores exist in the gather-form epilogue only
   // input / epilogue options only the halo-GEMM kernels implement (fused BN-backward apply, addend from another tensor, masked store)

@@ -80,6 +80,13 @@ struct CeArgs {
 };
 size_t ce_workspace_floats(int B, int H, int W);
 int ce_head(const CeArgs& a, hipStream_t s);
+// The two ends of ce_head() for a caller whose per-pixel pass runs elsewhere (the CE flavour of the head convolution, ConvArgs::ce_lab8):
+// ce_labels, the caller's pass with at most CE_MAX_BLOCKS loss partials, ce_finish.
+constexpr int CE_MAX_BLOCKS = 2048;
+struct CeWorkspace { unsigned char* lab8; float* den_partial; float* loss_partial; float* den; };
+CeWorkspace ce_workspace_layout(float* workspace, long npix);
+int ce_labels(const void* labels, int label_kind, const float* weight, int B, int C, int H, int W, int* targets_i32, float* workspace, hipStream_t s);
+int ce_finish(float* workspace, long npix, int nblk, float* loss, hipStream_t s);
 int softmax_argmax(const float* logits, int B, int C, int H, int W, unsigned char* preds_u8, long long* preds_i64,
                    float* maxprob, hipStream_t s);
 int softmax_argmax_nhwc(const void* logits, int dtype, int ld, long npix, int C, unsigned char* preds_u8, long long* preds_i64,

@@ -106,12 +106,52 @@ struct DirectBnr {
   }
 };
 
+// CE flavour (ConvArgs::ce_lab8): per-lane loss accumulator and the workgroup's LDS scratch, [hist C*C unsigned][w 32 float][sh 4 float]
+struct DirectCe {
+  static constexpr int MAXC = 32;
+  static constexpr int LDS_BYTES = MAXC * MAXC * 4 + MAXC * 4 + 16;
+  float acc;
+  unsigned* hist;
+  const float* w;
+  float* sh;
+  __device__ __forceinline__ void init(const ConvArgs& a, unsigned char* lds, int t) {   // (a barrier must follow before the first tile)
+    acc = 0.f;
+    hist = reinterpret_cast<unsigned*>(lds);
+    float* wl = reinterpret_cast<float*>(lds + MAXC * MAXC * 4);
+    w = wl;
+    sh = wl + MAXC;
+    for (int i = t; i < a.Cout * a.Cout; i += 256) hist[i] = 0u;
+    if (t < MAXC) wl[t] = t < a.Cout ? (a.ce_weight ? a.ce_weight[t] : 1.f) : 0.f;
+  }
+  // block sum of acc -> ce_loss_partial[blockIdx.x] (the reduction tree of ce_head.hip's block_sum), hist -> ce_confmat with one
+  // 64-bit integer atomic per non-zero cell; every thread of the workgroup calls it once, after its last tile
+  __device__ __forceinline__ void finish(const ConvArgs& a, int t) {
+    float v = acc;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((t & 63) == 0) sh[t >> 6] = v;
+    __syncthreads();   // (also orders the LDS histogram increments of every wave before the reads below)
+    if (t == 0) {
+      float r = 0.f;
+      for (int w4 = 0; w4 < 4; ++w4) r += sh[w4];
+      a.ce_loss_partial[blockIdx.x] = r;
+    }
+    if (a.ce_confmat) {
+      for (int i = t; i < a.Cout * a.Cout; i += 256) {
+        const unsigned hv = hist[i];
+        if (hv) atomicAdd(reinterpret_cast<unsigned long long*>(a.ce_confmat + i), (unsigned long long)hv);
+      }
+    }
+  }
+};
+
 // AFF = false: no per-channel affine and no statistics (plain data gradients): cf / s1 / s2 are not touched
 // BNR: `bn` accumulates sum(dz*m), sum(dz*m*y) of the stored gradient (the pooled half when pool_c0 > 0)
-template <typename T, int TW_, int TN, bool AFF = true, bool BNR = false>
+// CE: the per-pixel head (loss term, confusion-matrix increment) next to the argmax, state in `ce`
+template <typename T, int TW_, int TN, bool AFF = true, bool BNR = false, bool CE = false>
 __device__ __forceinline__ void direct_store(const ConvArgs& a, const f32x4_t (&acc)[4][TN], int n, int y0, int x0, int n0, int wave,
                                              int lane, const DirectCoef<TN>& cf, float (&s1)[4 * TN], float (&s2)[4 * TN],
-                                             DirectBnr<TN>* bn = nullptr) {
+                                             DirectBnr<TN>* bn = nullptr, DirectCe* ce = nullptr) {
   constexpr int CH = Elem<T>::CH, NCH = 4 * TN;
   typedef LaneVec<T, NCH> LV;
   const int lr = lane & 15, lq = lane >> 4;
@@ -134,7 +174,7 @@ __device__ __forceinline__ void direct_store(const ConvArgs& a, const f32x4_t (&
           v[i][e] = Elem<T>::to_f(Elem<T>::from_f(acc[i][q][rr]));
         }
       }
-  if (a.preds_u8) {
+  if (CE || a.preds_u8) {
     // argmax over the column block's channels: a lane holds 4*TN consecutive ones of pixel lr, lanes lr + 16*lq the others
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -156,15 +196,36 @@ __device__ __forceinline__ void direct_store(const ConvArgs& a, const f32x4_t (&
         if (take) { bv = ov; bi = oi; }
       }
       const long pix = ((long)n * H + y0 + 2 * wave + (i >> 1)) * W + x0 + (i & 1) * 16 + lr;
-      if (lq == 0) a.preds_u8[pix] = (unsigned char)bi;
-      if (a.maxprob_f32) {   // softmax probability of the winner: exp(0) / sum_c exp(x_c - max)
+      if constexpr (CE) {
+        if (lq == 0 && a.preds_u8) a.preds_u8[pix] = (unsigned char)bi;
+      } else {
+        if (lq == 0) a.preds_u8[pix] = (unsigned char)bi;
+      }
+      if (CE || a.maxprob_f32) {   // softmax probability of the winner: exp(0) / sum_c exp(x_c - max)
         float ssum = 0.f;
 #pragma unroll
         for (int e = 0; e < NCH; ++e)
           if (nn + e < a.Cout) ssum += __expf(v[i][e] - bv);   // (2e-7 relative per term; the reference tolerance on this band is 1e-6)
         ssum += __shfl_xor(ssum, 16);
         ssum += __shfl_xor(ssum, 32);
-        if (lq == 0) a.maxprob_f32[pix] = 1.f / ssum;
+        if constexpr (!CE) {
+          if (lq == 0) a.maxprob_f32[pix] = 1.f / ssum;
+        } else {
+          if (lq == 0 && a.maxprob_f32) a.maxprob_f32[pix] = 1.f / ssum;
+          // nll = log(sum) - (x_y - max), the arithmetic of ce_main_nhwc_kernel: the label's logit sits in one of the pixel's four
+          // lanes (compare-selects over the lane's channels, no dynamic register index), the others contribute an exact zero
+          const int y = a.ce_lab8[pix];
+          float xy = 0.f;
+#pragma unroll
+          for (int e = 0; e < NCH; ++e)
+            if (nn + e == y) xy = v[i][e];
+          xy += __shfl_xor(xy, 16);
+          xy += __shfl_xor(xy, 32);
+          if (lq == 0 && y < a.Cout) {
+            ce->acc += ce->w[y] * (logf(ssum) - (xy - bv));
+            if (a.ce_confmat && (unsigned)bi < (unsigned)a.Cout) atomicAdd(&ce->hist[y * a.Cout + bi], 1u);
+          }
+        }
       }
     }
   }

@@ -114,9 +114,16 @@ class UNet {
   // every entry point other than forward() lays the arena out differently (the split path re-imports five feature tensors
   // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone, and so are pending
   // one-shot requests
-  void invalidate_reuse() { last_valid_ = false; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; }
+  void invalidate_reuse() { last_valid_ = false; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); }
   // the next forward without fp32 logits writes argmax predictions [B][H][W] uint8 here (one-shot, like reuse_constants)
   void want_preds(unsigned char* p, float* maxprob) { preds_req_ = p; maxprob_req_ = maxprob; }
+  // the next eval-mode forward without fp32 logits evaluates the per-pixel head of step() on its logits (one-shot): weighted CE
+  // mean -> loss, argmax -> preds (optional), confmat += bincount (optional); ws: ce_workspace_floats(B, H, W) floats
+  struct CeReq {
+    const void* labels = nullptr; int kind = 0; const float* weight = nullptr;
+    float* loss = nullptr; unsigned char* preds = nullptr; long long* confmat = nullptr; float* ws = nullptr;
+  };
+  void want_ce(const CeReq& r) { ce_req_ = r; }
   void* last_dlogits_nhwc() const { return dl_nhwc_; }
   const void* logits_nhwc() const { return logits_nhwc_; }
   int head_ld() const { return convs.back().Cout_p; }
@@ -158,6 +165,7 @@ class UNet {
   bool side_pending_ = false;
   unsigned char* preds_req_ = nullptr;
   float* maxprob_req_ = nullptr;
+  CeReq ce_req_;
   bool side_init();
   hipStream_t wgrad_stream();
   int side_cus(int unit) const;   // forks the side stream behind everything queued on s_ so far

@@ -465,6 +465,34 @@ void UNet::head_fwd_impl(float* logits_nchw) {
   unsigned char* preds = (!logits_nchw && !training_) ? preds_req_ : nullptr;
   float* maxprob = preds ? maxprob_req_ : nullptr;
   preds_req_ = nullptr; maxprob_req_ = nullptr;
+  const CeReq ce = ce_req_;   // (forward() lets it through for eval-mode calls without fp32 logits only)
+  ce_req_ = CeReq();
+  if (ce.labels && !dry_) {
+    // validation: loss term, argmax and confusion-matrix increment in the head convolution's register epilogue, between the label
+    // pass and the fp64 sum of ce_head (the logits never reach HBM); otherwise the head convolution to NHWC logits and ce_head on
+    // them — one behaviour for the caller on every shape
+    const long npix = dec_out_.rows();
+    const CeWorkspace w = ce_workspace_layout(ce.ws, npix);
+    ConvArgs b = a;
+    b.out = nullptr; b.preds_u8 = ce.preds;
+    b.ce_lab8 = w.lab8; b.ce_weight = ce.weight; b.ce_loss_partial = w.loss_partial; b.ce_confmat = ce.confmat;
+    if (conv_halo_ce_ok(dtype, b)) {
+      logits_nhwc_ = nullptr;
+      RUN(ce_labels(ce.labels, ce.kind, ce.weight, dec_out_.N, c.Cout, dec_out_.H, dec_out_.W, nullptr, ce.ws, s_));
+      RUN(launch_conv(dtype, b, s_));
+      RUN(ce_finish(ce.ws, npix, conv_grid_rows(dtype, b), ce.loss, s_));
+      return;
+    }
+    RUN(launch_conv(dtype, a, s_));
+    CeArgs h;
+    h.logits = nullptr; h.logits_nhwc = logits_nhwc_; h.logits_dtype = dtype; h.logits_ld = c.Cout_p;
+    h.labels = ce.labels; h.label_kind = ce.kind; h.weight = ce.weight;
+    h.B = dec_out_.N; h.C = c.Cout; h.H = dec_out_.H; h.W = dec_out_.W; h.loss = ce.loss;
+    h.dlogits_nchw = nullptr; h.dlogits_nhwc = nullptr; h.dlogits_dtype = dtype; h.dlogits_ld = c.Cout_p;
+    h.preds_u8 = ce.preds; h.preds_i64 = nullptr; h.targets_i32 = nullptr; h.confmat = ce.confmat; h.workspace = ce.ws;
+    RUN(ce_head(h, s_));
+    return;
+  }
   if (preds && !dry_) {
     // predict: argmax in the head convolution's register epilogue, the logits never reach HBM (536 MB of traffic and the
     // softmax_argmax launch saved); otherwise the separate kernel over the NHWC logits
@@ -488,10 +516,13 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   unsigned char* const preds_now = preds_req_;
   float* const maxprob_now = maxprob_req_;
   const bool reuse_now = reuse_req_;
-  preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false;
+  const CeReq ce_now = ce_req_;
+  preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false; ce_req_ = CeReq();
+  // two heads asked of one forward, or the CE head of a forward that is not an eval-mode one without fp32 logits
+  if (ce_now.labels && (preds_now || training || logits_nchw)) return -15;
   if ((H % 32) || (W % 32)) return -10;
   reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && B == last_B_ && H == last_H_ && W == last_W_;
-  preds_req_ = preds_now; maxprob_req_ = maxprob_now;   // consumed by head_fwd_impl below
+  preds_req_ = preds_now; maxprob_req_ = maxprob_now; ce_req_ = ce_now;   // consumed by head_fwd_impl below
   begin(ws, ws_bytes, s, false);
   fwd_common_begin(params, buffers, B, H, W, training);
   const int lazy_env = tune("FLAIR_LAZY_BN", 1);

@@ -10,12 +10,12 @@ from .segformer import SegformerForSemanticSegmentation
 from .upernet import UperNetForSemanticSegmentation
 from .head import FusedCrossEntropyLoss, MulticlassJaccardIndex, MeanMetric
 from .task_module import segmentation_task_training, segmentation_task_predict
-from .train import SegTrainer, bucket_ranges, allreduce_buckets, shard_indices
+from .train import SegTrainer, bucket_ranges, allreduce_buckets, shard_indices, reduce_validation_state
 from .data_feed import TileFeed, draw_d4
 from . import checkpoint, metrics, tasks_utils, writer, zone_detect, zone_metrics
 
 __all__ = ["Unet", "create_model", "FLAIR_ModelFactory", "MetadataMLP", "FusedCrossEntropyLoss", "SegformerForSemanticSegmentation",
            "UperNetForSemanticSegmentation",
            "MulticlassJaccardIndex", "MeanMetric", "segmentation_task_training", "segmentation_task_predict",
-           "SegTrainer", "bucket_ranges", "allreduce_buckets", "shard_indices", "TileFeed", "draw_d4", "checkpoint", "metrics", "tasks_utils",
+           "SegTrainer", "bucket_ranges", "allreduce_buckets", "shard_indices", "reduce_validation_state", "TileFeed", "draw_d4", "checkpoint", "metrics", "tasks_utils",
            "writer", "zone_detect", "zone_metrics"]

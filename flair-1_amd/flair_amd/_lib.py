@@ -98,6 +98,7 @@ PROTOTYPES = {
     "flair_metadata_mlp_backward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
     "flair_unet_reuse_constants": (i32, [vp, i32]),
     "flair_unet_want_preds": (i32, [vp, vp, vp]),
+    "flair_unet_want_ce": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
     "flair_detect_stitch_preds": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp]),
     "flair_detect_blend_accum": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_detect_blend_flush": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),

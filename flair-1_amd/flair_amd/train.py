@@ -54,6 +54,18 @@ def allreduce_buckets(flat_grads, buckets, group=None, async_op=False):
     return works
 
 
+def reduce_validation_state(loss_sum, count, confmat, group=None):
+    """Sum the validation accumulators over the ranks, in place: what ``sync_dist=True`` / torchmetrics'
+    ``dist_reduce_fx="sum"`` do to MeanMetric's (value, weight) and to the confusion matrix of MulticlassJaccardIndex
+    (task_module.py:111-135).  Plain torch.distributed on whatever device the tensors live on."""
+    lc = torch.stack([loss_sum, count.to(loss_sum.dtype)])
+    dist.all_reduce(lc, op=dist.ReduceOp.SUM, group=group)
+    dist.all_reduce(confmat, op=dist.ReduceOp.SUM, group=group)
+    loss_sum.copy_(lc[0])
+    count.copy_(lc[1])
+    return loss_sum, count, confmat
+
+
 def shard_indices(n_items, rank, world, epoch_seed=0, shuffle=True, drop_last=False):
     """The partition Lightning's DistributedSampler gives the reference: a seeded
     permutation, padded to a multiple of ``world`` by wrapping, rank r takes r, r+W, r+2W, ..."""
@@ -71,8 +83,9 @@ class SegTrainer:
     """Owns the flat gradient buffer, the fused head outputs and the RCCL exchange for one rank."""
 
     def __init__(self, model, lr, class_weight=None, group=None, overlap=True, min_bucket_elems=1 << 18,
-                 force_exchange=False, broadcast_buffers=True):
+                 force_exchange=False, broadcast_buffers=True, class_names=None):
         self.model = model
+        self.class_names = None if class_names is None else [str(n) for n in class_names]
         self.sync_buffers = bool(broadcast_buffers)   # torch DDP's broadcast_buffers (tasks.py:83-88 keeps the default, True)
         self._src0 = 0 if group is None else dist.get_global_rank(group, 0)
         self.lr = float(lr)
@@ -93,6 +106,13 @@ class SegTrainer:
         self._dl = None
         self._preds = None
         self._ce_ws = None
+        # validation accumulators (validate_step / validation_epoch_end): MulticlassJaccardIndex's confusion matrix and
+        # MeanMetric's (sum of values, sum of weights), every batch with weight 1
+        self.val_confmat = torch.zeros(model.classes, model.classes, dtype=torch.int64, device=dev)
+        self.val_loss_sum = torch.zeros((), dtype=torch.float64, device=dev)
+        self.val_count = torch.zeros((), dtype=torch.float64, device=dev)
+        self._val_preds = None
+        self._val_ws = None
         if self.exchange:
             # HIGH priority: its own hardware queues (HIP multiplexes streams over a few queues per priority level; a
             # normal-priority stream can land on the caller's queue and serialise the collectives behind the backward
@@ -174,3 +194,50 @@ class SegTrainer:
         # separate pass over the NHWC logits inside the same native call): the logits never reach HBM
         m._c_forward(img, training=False, want_logits=False, preds=preds)
         return preds
+
+    @torch.no_grad()
+    def validate_step(self, img, labels):
+        """validation_step of the reference (task_module.py:104-109) on the eval handle and the eval workspace, with the
+        running statistics whatever ``model.training`` says: one native call, the loss term, the argmax and the confusion
+        matrix increment come out of the head convolution's epilogue (flair_unet_want_ce).  img / labels as for train_step.
+        Returns this batch's device scalar loss (no host sync), adds it to the running mean and the batch's confusion matrix to
+        ``val_confmat``; the predictions stay in ``_val_preds``.  No parameter, buffer or training activation is touched."""
+        with torch.cuda.device(self.grads.device):
+            return self._validate_step(img, labels)
+
+    def _validate_step(self, img, labels):
+        m = self.model
+        B, _, H, W = img.shape
+        dev = self.grads.device
+        if self._val_preds is None or self._val_preds.shape != (B, H, W):
+            self._val_preds = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+            self._val_ws = torch.empty(L.lib().flair_ce_workspace_bytes(B, H, W) + 256, dtype=torch.uint8, device=dev)
+        kind = 3 if labels.dtype == torch.float32 else ops._LABEL_KIND[labels.dtype]
+        labels = labels.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=dev)   # (a tensor of its own: the caller may keep every batch's)
+        m._c_forward(img, training=False, want_logits=False,
+                     ce=(L.ptr(labels), kind, L.ptr(self.class_weight), L.ptr(loss), L.ptr(self._val_preds),
+                         L.ptr(self.val_confmat), L.ptr(self._val_ws)))
+        self.val_loss_sum += loss
+        self.val_count += 1
+        return loss
+
+    @torch.no_grad()
+    def validation_epoch_end(self):
+        """on_validation_epoch_end of the reference (task_module.py:111-154): with a process group the accumulators are
+        first summed over the ranks; ``val_loss`` = mean of the batch losses, ``val_miou`` = support-weighted Jaccard,
+        ``val_iou`` = per-class Jaccard (flair_jaccard), ``val_iou_named`` = the classes of non-zero weight by name (by index
+        without ``class_names``).  Resets the accumulators."""
+        with torch.cuda.device(self.grads.device):
+            if self.world > 1:
+                reduce_validation_state(self.val_loss_sum, self.val_count, self.val_confmat, self.group)
+            per, weighted, _ = ops.jaccard(self.val_confmat)
+            val_loss = (self.val_loss_sum / self.val_count).to(torch.float32)
+            C = self.model.classes
+            names = self.class_names if self.class_names is not None else list(range(C))
+            cw = [1.0] * C if self.class_weight is None else self.class_weight.tolist()
+            named = {n: float(v) for n, w, v in zip(names, cw, per.tolist()) if w != 0}
+            self.val_confmat.zero_()
+            self.val_loss_sum.zero_()
+            self.val_count.zero_()
+            return {"val_loss": val_loss, "val_miou": weighted, "val_iou": per, "val_iou_named": named}

@@ -462,10 +462,12 @@ class Unet(nn.Module):
         return None if ent["logits"] is None else ent["logits"].clone()
 
     @_on_model_device
-    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None):
+    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None):
         """want_logits=False (fused trainer): the head's output stays in the workspace as NHWC rows of the compute dtype
         (flair_unet_logits_nhwc) and no fp32 NCHW tensor is produced; returns None.  preds / prob (eval mode, no logits): uint8
-        argmax and its fp32 probability from the head convolution's epilogue (flair_unet_want_preds)."""
+        argmax and its fp32 probability from the head convolution's epilogue (flair_unet_want_preds).  ce (eval mode, no
+        logits): the arguments of flair_unet_want_ce behind the handle — the validation head in the same call; such a forward
+        always runs eagerly (never captured, not counted towards the captures of the plain paths)."""
         x = self._prep(x)
         B, _, H, W = x.shape
         ws = self._workspace(B, H, W, training)
@@ -477,7 +479,7 @@ class Unet(nn.Module):
             if self.__dict__.get("_eval_key") != key:
                 graphs.clear()
                 self._eval_hits = {}
-            elif (os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0" and B * H * W <= self._GRAPH_MAX_PIXELS
+            elif (ce is None and os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0" and B * H * W <= self._GRAPH_MAX_PIXELS
                   and not torch.cuda.is_current_stream_capturing()):
                 gkey = (want_logits, preds is not None, prob is not None)
                 hits = self.__dict__.setdefault("_eval_hits", {})
@@ -487,6 +489,8 @@ class Unet(nn.Module):
         logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
         if preds is not None:
             L.check(L.lib().flair_unet_want_preds(h, L.ptr(preds), L.ptr(prob)), "flair_unet_want_preds")
+        if ce is not None:
+            L.check(L.lib().flair_unet_want_ce(h, *ce), "flair_unet_want_ce")
         if not training:
             # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
             # BatchNorm-coefficient launches.  torch bumps a tensor's _version on every in-place write (optimizers,

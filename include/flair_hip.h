@@ -67,6 +67,17 @@ int flair_unet_reuse_constants(flair_unet_t* h, int on);
  * (device pointer) — predict_step's argmax(softmax(logits)), task_module.py:206-213 — from the head convolution's epilogue; the
  * logits are then not kept (flair_unet_logits_nhwc returns NULL until the next forward). */
 int flair_unet_want_preds(flair_unet_t* h, uint8_t* preds_u8, float* maxprob_f32 /* optional: the winner's softmax probability */);
+/* One-shot: the next flair_unet_forward with training = 0 and logits = NULL evaluates the head of step() on its logits —
+ * task_module.py:71-79, tasks_utils.py:88-93, what validation_step needs: the weighted cross-entropy mean -> loss, argmax(softmax) ->
+ * preds_u8, confmat[target][pred] += 1 (int64 [C][C]).  Labels as for flair_ce_head.  Where the head convolution's persistent kernel takes
+ * the shape — flair_unet_want_preds's condition, and the head's 16 input channels materialised (not handed over as a lazy
+ * BatchNorm input, FLAIR_LAZY_BN >= 2) — and the tune key FLAIR_HEAD_CE is on (default off) all of it happens in that kernel's epilogue and the logits are not kept
+ * (flair_unet_logits_nhwc returns NULL); otherwise the same call runs the head convolution and flair_ce_head_nhwc's kernels on its
+ * NHWC logits.  All pointers are device pointers that must stay valid until that forward has run.  A forward that also holds a
+ * flair_unet_want_preds request, trains or returns fp32 logits is refused (-15); the request is dropped by any forward. */
+int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, const float* class_weight, float* loss,
+                       uint8_t* preds_u8 /* optional */, int64_t* confmat /* optional */,
+                       void* ce_workspace /* flair_ce_workspace_bytes(B, H, W) */);
 
 /* seg_model.encoder(x) / .decoder(*feats) / .segmentation_head(t) — the metadata path model.py:57-62.
  * feats[i] = feature i+1 of the encoder, NCHW fp32: (B,64,H/2,W/2) ... (B,512,H/32,W/32). */

@@ -23,4 +23,4 @@ if r.returncode:
 for c in rows:
     if pat in c["name"]:
         nm = re.sub(r"flair::\(anonymous namespace\)::|flair::|void ", "", c["name"])
-        print(f"{nm[:100]:100s} v{c.get('VGPRs',0):4d} a{c.get('AGPRs',0):4d} s{c.get('TotalSGPRs',0):4d} scratch{c.get('ScratchSize',0):5d} vspill{c.get('VGPRs Spill',0):3d} occ{c.get('Occupancy',0)}")
+        print(f"{nm[:100]:100s} v{c.get('VGPRs',0):4d} a{c.get('AGPRs',0):4d} s{c.get('TotalSGPRs',0):4d} lds{c.get('LDS Size',0):6d} scratch{c.get('ScratchSize',0):5d} vspill{c.get('VGPRs Spill',0):3d} occ{c.get('Occupancy',0)}")
