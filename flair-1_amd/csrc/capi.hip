@@ -4,6 +4,7 @@
 
 #include "../../include/flair_hip.h"
 #include "unet.h"
+#include "parity_pack.h"
 #include "segformer.h"
 #include "upernet.h"
 #include "segformer_ops.h"
@@ -444,11 +445,32 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
 // ---- the fused forms of the same launchers (plain structs in, ConvArgs / WgradArgs out; no kernel differs)
 static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a, int& Cin, int& rows_f) {
   if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
-  if (p->mode != 0 && p->mode != 1) return -2;
-  if (p->mode == 1 && p->stride != 1) return -6;   // the parity-class stride-2 data gradient packs its weights in unet.hip
+  if (p->mode != 0 && p->mode != 1 && p->mode != 2) return -2;
+  if (p->mode == 1 && p->stride != 1) return -6;   // (mode 2 is the stride-2 data gradient)
   memset(&a, 0, sizeof(a));
   int Kg, Kpad;
   conv_geom(p->dtype, p->C0, p->x1 ? p->C1 : 0, p->Cout, p->R, Cin, Kg, Kpad, rows_f);
+  if (p->mode == 2) {
+    // UNet::unit_backward, DG_PARITY: stride-1 convolutions over dY, stores interleaved into dX
+    const bool r3 = p->R == 3 && p->pad == 1, r1 = p->R == 1 && p->pad == 0;
+    if (p->stride != 2 || (!r3 && !r1) || p->x1 || p->up0) return -6;
+    a.src0 = p->x0; a.C0 = p->C0; a.N = p->N; a.Hin = p->H; a.Win = p->W; a.Hout = p->H; a.Wout = p->W;
+    a.R = p->R; a.S = p->R; a.out_mul = 1; a.pad = 0; a.in_div = 1; a.out_sub = 1;
+    a.Cout = p->Cout; a.Kg = Kg; a.Kpad = Kpad;
+    a.out = p->y_nhwc; a.out_ld = p->out_ld > 0 ? p->out_ld : p->Cout; a.accumulate = p->accumulate;
+    if (r3) {
+      a.ncls = 4; a.R = 2; a.S = 2;
+      int kg[4];
+      for (int cls = 0; cls < 4; ++cls) parity_class_geom(p->dtype, p->C0, cls, kg[cls], a.cls_kpad[cls]);
+      a.Kg = (kg[0] + kg[1] + kg[2] + kg[3]) / 4;
+      a.Kpad = a.cls_kpad[3];
+    }
+    // every other option of the struct belongs to kernels this form never reaches
+    if (p->bias || p->y_nchw || p->stats || p->in_scale || p->in_shift || p->oscale || p->oshift || p->ores || p->orelu || p->acc_src ||
+        p->pool_c0 || p->out_skip || p->preds_u8 || p->maxprob_f32 || p->ogelu || p->bnr_y || p->bnr_out || p->bnr_partial || p->bnr_mask)
+      return -6;
+    return 0;
+  }
   a.src0 = p->x0; a.src1 = p->x1; a.C0 = p->C0; a.C1 = p->x1 ? p->C1 : 0; a.up0 = p->up0; a.N = p->N;
   a.Hin = p->up0 ? 2 * p->H : p->H; a.Win = p->up0 ? 2 * p->W : p->W;
   const int pad = p->mode == 1 ? p->R - 1 - p->pad : p->pad;
@@ -460,18 +482,72 @@ static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a, int& Cin, int& ro
   a.accumulate = p->accumulate; a.acc_src = p->acc_src;
   a.pool_c0 = p->pool_c0; a.out_skip = p->out_skip; a.out_skip_ld = p->out_skip_ld; a.skip_accumulate = p->skip_accumulate;
   a.preds_u8 = p->preds_u8; a.maxprob_f32 = p->maxprob_f32; a.ogelu = p->ogelu;
+  a.bnr_mask = p->bnr_mask;
+  if (p->bnr_partial || p->bnr_y) {
+    a.bnr_y = p->bnr_y; a.bnr_out = p->bnr_out; a.bnr_scale = p->bnr_scale; a.bnr_shift = p->bnr_shift; a.bnr_C = a.out_ld;
+    a.bnr_partial = p->bnr_partial;
+  }
   return 0;
+}
+
+// The sizing queries launch nothing, and the dispatch predicates they ask only look at which pointers are set: the weights stand
+// in as the struct itself, and a request for the fused reduction whose partial is still to be sized (bnr_y without bnr_partial)
+// as `standin`, host storage of the query.  Arguments prepared here never reach launch_conv.
+static void conv_ex_sizing(const flair_conv_ex_t* p, ConvArgs& a, float* standin) {
+  a.w = p;
+  if (p->mode != 2 && p->bnr_y && !a.bnr_partial) a.bnr_partial = standin;
+}
+
+// the four class packs of mode 2 (R = 3), or its one transposed pack (R = 1): descriptors relative to the workspace base
+static size_t conv_ex_parity_packs(const flair_conv_ex_t* p, ConvArgs& a, unsigned char* base, PackTable& tb) {
+  const size_t es = dtype_size(p->dtype);
+  const int rows_d = conv_weight_rows_pad(p->Cout);
+  PackDesc d;
+  memset(&d, 0, sizeof(d));
+  d.w_off = 0; d.dst_off = 0; d.Cout = p->C0; d.Cin = p->Cout; d.R = p->R; d.S = p->R;
+  d.Cin_p = p->C0; d.rows_pad = rows_d; d.Kpad = a.Kpad; d.tf = 1;
+  tb.n = 0;
+  size_t top = 0;
+  if (!a.ncls) {
+    tb.d[tb.n++] = d;
+    a.w = base;
+    return (size_t)round_up((long)((size_t)rows_d * a.Kpad * es), 256);
+  }
+  for (int cls = 0; cls < 4; ++cls) {
+    tb.d[tb.n++] = parity_class_pack(d, cls, top, a.cls_kpad[cls]);
+    a.cls_w[cls] = base + top;
+    top += (size_t)round_up((long)((size_t)rows_d * a.cls_kpad[cls] * es), 256);
+  }
+  a.w = a.cls_w[3];
+  return top;
 }
 
 size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p) {
   ConvArgs a;
   int Cin, rows_f;
+  float standin;
   if (!p || conv_ex_fill(p, a, Cin, rows_f)) return 0;
-  a.w = p;  // (non-null: the dispatch predicates only look at which pointers are set)
+  conv_ex_sizing(p, a, &standin);
+  if (p->mode == 2) {
+    PackTable tb;
+    return conv_ex_parity_packs(p, a, nullptr, tb) + 256;
+  }
   a.stats = p->stats;
   size_t b = (size_t)round_up((long)((size_t)rows_f * a.Kpad * dtype_size(p->dtype)), 256);
   if (p->stats) b += (size_t)round_up((long)conv_grid_rows(p->dtype, a) * 2 * p->Cout * 4, 256);
   return b + 256;
+}
+
+int flair_conv2d_ex_grid_rows(const flair_conv_ex_t* p) {
+  ConvArgs a;
+  int Cin, rows_f;
+  float standin;
+  if (!p) return -1;
+  const int rc = conv_ex_fill(p, a, Cin, rows_f);
+  if (rc) return rc;
+  conv_ex_sizing(p, a, &standin);
+  a.stats = p->stats;
+  return conv_grid_rows(p->dtype, a);
 }
 
 int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void* stream) {
@@ -481,9 +557,20 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
   int Cin, rows_f;
   int rc = conv_ex_fill(p, a, Cin, rows_f);
   if (rc) return rc;
+  if (p->mode == 2) {
+    if (!p->y_nhwc) return -1;
+    PackTable tb;
+    if (conv_ex_parity_packs(p, a, (unsigned char*)workspace, tb) > wsb) return -100;
+    rc = pack_weights_all(p->dtype, p->w_oihw, workspace, tb, s);
+    return rc ? rc : launch_conv(p->dtype, a, s);
+  }
+  // the epilogue reads bnr_y, bnr_scale and bnr_shift unconditionally, and a reduction without a partial has nowhere to go
+  if (p->bnr_partial ? (!p->bnr_y || !p->bnr_scale || !p->bnr_shift) : (p->bnr_y != nullptr)) return -1;
   OpArena ar(workspace, wsb);
   void* wp = ar.get((size_t)rows_f * a.Kpad * dtype_size(p->dtype));
   a.w = wp;
+  // the partial is the caller's, one row per row block of the launch
+  if (p->bnr_partial && p->bnr_rows < conv_grid_rows(p->dtype, a)) return -100;
   float* partial = nullptr;
   int nblk = 0;
   if (p->stats) {
@@ -513,6 +600,7 @@ static int wgrad_ex_fill(const flair_wgrad_ex_t* p, WgradArgs& w) {
   w.dy = p->dy; w.dy_ld = p->dy_ld > 0 ? p->dy_ld : p->Cout; w.Cout = p->Cout; w.dw = p->dw;
   w.Cin_real = p->Cin_real > 0 ? p->Cin_real : w.C0 + w.C1;
   w.accumulate = p->accumulate; w.in_scale = p->in_scale; w.in_shift = p->in_shift; w.cus = p->cus; w.dbias = p->dbias;
+  w.fuse_y = p->fuse_y; w.fuse_coef = p->fuse_coef; w.fuse_msc = p->fuse_msc; w.fuse_msh = p->fuse_msh;
   return 0;
 }
 
@@ -581,6 +669,94 @@ int flair_bn_relu_backward(int dtype, const void* dout, const void* out, const v
   if (ar.bad) return -100;
   return bn_backward(dtype, dout, relu ? out : nullptr, y, save_mean, save_invstd, gamma, rows, C, partial, coef, dgamma,
                      dbeta, 0, dy, dres, 0, nullptr, nullptr, 0, 0, (hipStream_t)stream);
+}
+
+int flair_bn_backward_ex(const flair_bn_bwd_ex_t* p, void* workspace, size_t wsb, void* stream) {
+  if (!p || !p->dout || !p->y || !p->mean || !p->invstd || !workspace || p->rows < 1 || p->C < 1) return -1;
+  if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
+  if (p->dres && !p->dy) return -1;              // the apply pass always writes dy
+  if (!p->dgamma != !p->dbeta) return -1;
+  if (p->pre_nblk > 0 && !p->partial) return -1;
+  OpArena ar(workspace, wsb);
+  float* partial = p->pre_nblk > 0 ? p->partial : (float*)ar.get((size_t)bn_bwd_blocks(p->rows) * 2 * p->C * 4);
+  float* coef = p->coef ? p->coef : (float*)ar.get(3 * (size_t)p->C * 4);
+  if (ar.bad) return -100;
+  return bn_backward(p->dtype, p->dout, p->out, p->y, p->mean, p->invstd, p->gamma, (long)p->rows, p->C, partial, coef, p->dgamma,
+                     p->dbeta, p->accumulate_param, p->dy, p->dres, p->dres_accumulate, p->mscale, p->mshift, p->pre_nblk,
+                     p->premasked, (hipStream_t)stream);
+}
+
+int flair_maxpool_backward_ex(int dtype, const void* dy, const uint8_t* idx, void* dx, int accumulate, int N, int H, int W, int C,
+                              const void* bnr_y, const float* bnr_msc, const float* bnr_msh, float* bnr_partial, void* stream) {
+  if (!dy || !idx || !dx || N < 1 || H < 1 || W < 1 || C < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return maxpool3x3s2_bwd(dtype, dy, idx, dx, accumulate, N, H, W, C, (hipStream_t)stream, bnr_y, bnr_msc, bnr_msh, bnr_partial);
+}
+int flair_bn_act(int dtype, const void* y, const float* scale, const float* shift, void* out, int64_t rows, int C, int relu, void* stream) {
+  if (!y || !scale || !shift || !out || rows < 1 || C < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return bn_act(dtype, y, scale, shift, nullptr, nullptr, nullptr, out, (long)rows, C, relu, (hipStream_t)stream);
+}
+int flair_bn_act_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* act, void* out, uint8_t* idx, int N,
+                         int H, int W, int C, void* stream) {
+  if (!y || !scale || !shift || !act || !out || N < 1 || H < 1 || W < 1 || C < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return bn_act_maxpool3x3s2(dtype, y, scale, shift, act, out, idx, N, H, W, C, (hipStream_t)stream);
+}
+int flair_upcat_bwd(int dtype, const void* dcat, void* dx0, int dx0_accumulate, void* dskip, int dskip_accumulate, int N, int H, int W,
+                    int C0, int C1, void* stream) {
+  if (!dcat || !dx0 || (C1 > 0 && !dskip) || N < 1 || H < 1 || W < 1 || C0 < 1 || C1 < 0) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return upcat_bwd(dtype, dcat, dx0, dx0_accumulate, dskip, dskip_accumulate, N, H, W, C0, C1, (hipStream_t)stream);
+}
+int flair_ew_add(int dtype, void* dst, const void* src, int64_t n, void* stream) {
+  if (!dst || !src || n < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return ew_add(dtype, dst, src, (long)n, (hipStream_t)stream);
+}
+int flair_colsum(int dtype, const void* x, int64_t rows, int ld, int C, float* out, void* workspace, size_t wsb, void* stream) {
+  if (!x || !out || !workspace || rows < 1 || ld < 1 || C < 1) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  OpArena ar(workspace, wsb);
+  float* partial = (float*)ar.get((size_t)bn_bwd_blocks((long)rows) * ld * 4);
+  if (ar.bad) return -100;
+  return colsum(dtype, x, (long)rows, ld, C, partial, out, (hipStream_t)stream);
+}
+int flair_pack_weights(int dtype, const float* params, const flair_pack_desc_t* descs, int n, void* base, void* stream) {
+  if (!params || !descs || !base) return -1;
+  if ((dtype != DT_F32 && dtype != DT_BF16) || n < 1 || n > PackTable::MAX) return -2;
+  PackTable tb;
+  tb.n = n;
+  for (int i = 0; i < n; ++i) {
+    const flair_pack_desc_t& q = descs[i];
+    // the kernel trusts its table: a pack must hold its own real region
+    const int taps = q.Rc > 0 ? q.Rc * q.Sc : q.R * q.S;
+    if (q.Cout < 1 || q.Cin < 1 || q.R < 1 || q.S < 1 || taps < 1 || (long)taps * q.Cin_p > q.Kpad || q.Cin_p < (q.tf ? q.Cout : q.Cin) ||
+        q.rows_pad < (q.tf ? q.Cin : q.Cout) || q.w_off < 0)
+      return -2;
+    // the bf16 forward 3x3 branch and the transposed 32 x 32 branch of the kernel load the master 16 bytes at a time
+    const bool vec = dtype == DT_BF16 && q.R * q.S == 9 &&
+                     (q.tf ? ((q.Cin & 31) == 0 && (q.Cout & 31) == 0) : (q.Rc == 0 && (q.Cin & 3) == 0));
+    if (vec && (((uintptr_t)params & 15) || (q.w_off & 3))) return -2;
+    if (q.Rc > 0 && (q.r0 + (q.Rc - 1) * q.rstep >= q.R || q.s0 + (q.Sc - 1) * q.sstep >= q.S || q.r0 < 0 || q.s0 < 0 || q.rstep < 1 || q.sstep < 1))
+      return -2;
+    PackDesc& d = tb.d[i];
+    memset(&d, 0, sizeof(d));
+    d.w_off = (long)q.w_off; d.dst_off = (size_t)q.dst_off; d.Cout = q.Cout; d.Cin = q.Cin; d.R = q.R; d.S = q.S;
+    d.Cin_p = q.Cin_p; d.rows_pad = q.rows_pad; d.Kpad = q.Kpad; d.tf = q.tf;
+    d.r0 = (unsigned char)q.r0; d.rstep = (unsigned char)q.rstep; d.Rc = (unsigned char)q.Rc;
+    d.s0 = (unsigned char)q.s0; d.sstep = (unsigned char)q.sstep; d.Sc = (unsigned char)q.Sc;
+  }
+  return pack_weights_all(dtype, params, base, tb, (hipStream_t)stream);
+}
+int flair_pack_weight(int dtype, const float* w_oihw, void* dst, int Cout, int Cin, int R, int S, int Cin_p, int rows_pad, int Kpad,
+                      int tf, void* stream) {
+  if (!w_oihw || !dst) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  // as in flair_pack_weights: the pack holds its own real region (the kernel writes rows_pad x Kpad elements and reads w inside it)
+  if (Cout < 1 || Cin < 1 || R < 1 || S < 1 || (long)R * S * Cin_p > Kpad || Cin_p < (tf ? Cout : Cin) || rows_pad < (tf ? Cin : Cout))
+    return -2;
+  return pack_weight(dtype, w_oihw, dst, Cout, Cin, R, S, Cin_p, rows_pad, Kpad, tf ? 1 : 0, (hipStream_t)stream);
 }
 
 int flair_maxpool_forward(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream) {

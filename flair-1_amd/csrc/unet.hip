@@ -4,6 +4,7 @@
 #include <stdlib.h>
 
 #include "unet.h"
+#include "parity_pack.h"
 #include "tune.h"
 
 #include <string.h>
@@ -216,13 +217,10 @@ void UNet::begin(void* ws, size_t ws_bytes, hipStream_t s, bool dry) {
   for (auto& c : convs) {
     c.wd = top_; alloc((size_t)c.rows_d * c.Kpad_d * dtype_size(dtype));
   }
-  const int kstep = dtype == DT_F32 ? 32 : 64;
   for (auto& c : convs) {
     if (!c.parity_dgrad()) continue;
     for (int cls = 0; cls < 4; ++cls) {
-      const int taps = ((cls >> 1) ? 2 : 1) * ((cls & 1) ? 2 : 1);
-      c.Kg_cls[cls] = taps * c.Cout_p;
-      c.Kpad_cls[cls] = (int)round_up(c.Kg_cls[cls], kstep);
+      parity_class_geom(dtype, c.Cout_p, cls, c.Kg_cls[cls], c.Kpad_cls[cls]);
       c.wd_cls[cls] = top_; alloc((size_t)c.rows_d * c.Kpad_cls[cls] * dtype_size(dtype));
     }
   }
@@ -253,15 +251,8 @@ void UNet::pack_dgrad_weights() {
     d.Cin_p = c.Cout_p; d.rows_pad = c.rows_d; d.Kpad = c.Kpad_d; d.tf = 1;
     d.Rc = 0; d.r0 = d.rstep = d.s0 = d.sstep = d.Sc = 0;
     if (c.parity_dgrad()) {
-      for (int cls = 0; cls < 4; ++cls) {
-        // gather-form tap kr reads dY row (ho - 1 + kr) / 2: even output rows use kr = 1, odd rows kr = 0 and 2
-        PackDesc& e = tb.d[tb.n++];
-        e = d;
-        e.dst_off = c.wd_cls[cls]; e.Kpad = c.Kpad_cls[cls];
-        const int py = cls >> 1, px = cls & 1;
-        e.Rc = py ? 2 : 1; e.r0 = py ? 0 : 1; e.rstep = 2;
-        e.Sc = px ? 2 : 1; e.s0 = px ? 0 : 1; e.sstep = 2;
-      }
+      const PackDesc full = d;
+      for (int cls = 0; cls < 4; ++cls) tb.d[tb.n++] = parity_class_pack(full, cls, c.wd_cls[cls], c.Kpad_cls[cls]);
     }
   }
   RUN(pack_weights_all(dtype, params_, base_, tb, s_));

@@ -62,11 +62,21 @@ PROTOTYPES = {
     "flair_conv2d_backward": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "flair_conv2d_ex_workspace_bytes": (sz, [vp]),
     "flair_conv2d_ex": (i32, [vp, vp, sz, vp]),
+    "flair_conv2d_ex_grid_rows": (i32, [vp]),
     "flair_conv2d_wgrad_ex_workspace_bytes": (sz, [vp]),
     "flair_conv2d_wgrad_ex": (i32, [vp, vp, sz, vp]),
     "flair_bn_workspace_bytes": (sz, [i64, i32]),
     "flair_bn_relu_forward": (i32, [i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "flair_bn_relu_backward": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "flair_bn_backward_ex": (i32, [vp, vp, sz, vp]),
+    "flair_maxpool_backward_ex": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "flair_bn_act": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "flair_bn_act_maxpool": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "flair_upcat_bwd": (i32, [i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "flair_ew_add": (i32, [i32, vp, vp, i64, vp]),
+    "flair_colsum": (i32, [i32, vp, i64, i32, i32, vp, vp, sz, vp]),
+    "flair_pack_weights": (i32, [i32, vp, vp, i32, vp, vp]),
+    "flair_pack_weight": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "flair_maxpool_forward": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "flair_maxpool_backward": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),
     "flair_nchw_to_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
@@ -145,7 +155,9 @@ class ConvEx(C.Structure):
                 ("in_scale", vp), ("in_shift", vp), ("oscale", vp), ("oshift", vp), ("ores", vp), ("orelu", i32),
                 ("accumulate", i32), ("acc_src", vp),
                 ("pool_c0", i32), ("out_skip", vp), ("out_skip_ld", i32), ("skip_accumulate", i32),
-                ("preds_u8", vp), ("maxprob_f32", vp), ("ogelu", i32)]
+                ("preds_u8", vp), ("maxprob_f32", vp), ("ogelu", i32),
+                ("bnr_y", vp), ("bnr_out", vp), ("bnr_scale", vp), ("bnr_shift", vp),
+                ("bnr_partial", vp), ("bnr_rows", i32), ("bnr_mask", i32)]
 
 
 class WgradEx(C.Structure):
@@ -154,7 +166,23 @@ class WgradEx(C.Structure):
                 ("N", i32), ("H", i32), ("W", i32), ("C0", i32), ("C1", i32), ("up0", i32),
                 ("dy", vp), ("dy_ld", i32), ("Cout", i32), ("R", i32), ("stride", i32), ("pad", i32),
                 ("dw", vp), ("Cin_real", i32), ("accumulate", i32), ("in_scale", vp), ("in_shift", vp),
-                ("dbias", vp), ("cus", i32)]
+                ("dbias", vp), ("cus", i32),
+                ("fuse_y", vp), ("fuse_coef", vp), ("fuse_msc", vp), ("fuse_msh", vp)]
+
+
+class BnBwdEx(C.Structure):
+    """flair_bn_bwd_ex_t"""
+    _fields_ = [("dtype", i32), ("dout", vp), ("out", vp), ("y", vp), ("mean", vp), ("invstd", vp), ("gamma", vp),
+                ("rows", i64), ("C", i32), ("partial", vp), ("pre_nblk", i32), ("premasked", i32),
+                ("mscale", vp), ("mshift", vp), ("dgamma", vp), ("dbeta", vp), ("accumulate_param", i32),
+                ("dy", vp), ("dres", vp), ("dres_accumulate", i32), ("coef", vp)]
+
+
+class PackDesc(C.Structure):
+    """flair_pack_desc_t"""
+    _fields_ = [("w_off", i64), ("dst_off", C.c_uint64),
+                ("Cout", i32), ("Cin", i32), ("R", i32), ("S", i32), ("Cin_p", i32), ("rows_pad", i32), ("Kpad", i32), ("tf", i32),
+                ("r0", i32), ("rstep", i32), ("Rc", i32), ("s0", i32), ("sstep", i32), ("Sc", i32)]
 
 
 class FlairHipError(RuntimeError):

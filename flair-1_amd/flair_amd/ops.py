@@ -68,25 +68,25 @@ def conv2d_backward(x, w, dy, stride=1, pad=1, need_dx=True, need_dw=True):
     return dx, dw
 
 
-def conv2d_ex(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, want_nhwc=True, want_nchw=False, want_stats=False,
-              in_scale=None, in_shift=None, oscale=None, oshift=None, ores=None, orelu=False, out=None, accumulate=False,
-              acc_src=None, pool_c0=0, out_skip=None, skip_accumulate=False, want_preds=False, want_maxprob=False, ogelu=False):
-    """flair_conv2d_ex: the fused forms of the convolution launcher.  mode 0: forward, w = [Cout][C0 + C1][R][R]; mode 1: stride-1
-    data gradient, x0 = dy, w = the forward layer's [C0][Cout][R][R].  `out` (NHWC, optional) is the tensor accumulated into / written;
-    with pool_c0 it is [N][H/2][W/2][pool_c0] and out_skip [N][H][W][Cout - pool_c0].  ogelu: erf-GELU of the
-    accumulator (+ bias) before ores / orelu (gather-form GEMM only).
-    Returns a dict: y, out_skip, y_nchw, stats, preds, maxprob (absent outputs None)."""
-    import ctypes as C
+def _conv_ex_args(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, want_nhwc=True, want_nchw=False, want_stats=False,
+                  in_scale=None, in_shift=None, oscale=None, oshift=None, ores=None, orelu=False, out=None, accumulate=False,
+                  acc_src=None, pool_c0=0, out_skip=None, skip_accumulate=False, want_preds=False, want_maxprob=False, ogelu=False,
+                  bnr_y=None, bnr_out=None, bnr_scale=None, bnr_shift=None, bnr_partial=None, bnr_mask=False):
+    """(flair_conv_ex_t, outputs) of conv2d_ex / conv2d_ex_grid_rows.  The library picks its kernel from which pointers are set, so
+    the sizing query gets the same struct, outputs included, as the launch."""
     N, H, W, C0 = x0.shape
     C1 = x1.shape[3] if x1 is not None else 0
     R = w.shape[2]
-    Cout = w.shape[1] if mode == 1 else w.shape[0]
-    assert (w.shape[0] if mode == 1 else w.shape[1]) == C0 + C1
+    Cout = w.shape[1] if mode else w.shape[0]
+    assert (w.shape[0] if mode else w.shape[1]) == C0 + C1
     dt = _dt(x0)
     Hin, Win = (2 * H, 2 * W) if up0 else (H, W)
     p_eff = R - 1 - pad if mode == 1 else pad
     Ho, Wo = (Hin + 2 * p_eff - R) // stride + 1, (Win + 2 * p_eff - R) // stride + 1
     dev = x0.device
+    if mode == 2:
+        assert out is not None, "mode 2 writes into the caller's dx"
+        Ho, Wo = H, W
     if out is None and want_nhwc:
         assert not accumulate or acc_src is not None, "accumulate needs the tensor to add to"
         out = (torch.empty(N, Ho // 2, Wo // 2, pool_c0, dtype=x0.dtype, device=dev) if pool_c0 else
@@ -104,16 +104,43 @@ def conv2d_ex(x0, w, mode=0, bias=None, stride=1, pad=1, x1=None, up0=False, wan
                  in_shift=L.ptr(in_shift), oscale=L.ptr(oscale), oshift=L.ptr(oshift), ores=L.ptr(ores), orelu=int(orelu),
                  accumulate=int(accumulate), acc_src=L.ptr(acc_src), pool_c0=pool_c0, out_skip=L.ptr(out_skip),
                  out_skip_ld=out_skip.shape[3] if out_skip is not None else 0, skip_accumulate=int(skip_accumulate),
-                 preds_u8=L.ptr(pr), maxprob_f32=L.ptr(mp), ogelu=int(ogelu))
+                 preds_u8=L.ptr(pr), maxprob_f32=L.ptr(mp), ogelu=int(ogelu),
+                 bnr_y=L.ptr(bnr_y), bnr_out=L.ptr(bnr_out), bnr_scale=L.ptr(bnr_scale), bnr_shift=L.ptr(bnr_shift),
+                 bnr_partial=L.ptr(bnr_partial), bnr_rows=bnr_partial.shape[2] if bnr_partial is not None else 0, bnr_mask=int(bnr_mask))
+    return a, {"y": out, "out_skip": out_skip, "y_nchw": yn, "stats": st, "preds": pr, "maxprob": mp}
+
+
+def conv2d_ex(x0, w, **kw):
+    """flair_conv2d_ex: the fused forms of the convolution launcher (keywords: those of _conv_ex_args).
+    mode 0: forward, w = [Cout][C0 + C1][R][R]; mode 1: stride-1 data gradient, x0 = dy, w = the forward layer's [C0][Cout][R][R].  `out` (NHWC, optional) is the tensor accumulated into / written;
+    with pool_c0 it is [N][H/2][W/2][pool_c0] and out_skip [N][H][W][Cout - pool_c0].  ogelu: erf-GELU of the
+    accumulator (+ bias) before ores / orelu (gather-form GEMM only).
+    mode 2: the stride-2 data gradient by parity class, x0 = dy, w as in mode 1, `out` = dx [N][2H][2W][Cout] (required).
+    bnr_partial (fp32 [2][out_ld][rows], rows >= conv2d_ex_grid_rows(...)): the fused BatchNorm-backward reduction of the epilogue
+    against bnr_y (and bnr_scale / bnr_shift, or bnr_out); bnr_mask stores the masked gradient.
+    Returns a dict: y, out_skip, y_nchw, stats, preds, maxprob (absent outputs None)."""
+    import ctypes as C
+    a, outs = _conv_ex_args(x0, w, **kw)
     l = L.lib()
-    ws = _ws(l.flair_conv2d_ex_workspace_bytes(C.addressof(a)), dev)
+    ws = _ws(l.flair_conv2d_ex_workspace_bytes(C.addressof(a)), x0.device)
     L.check(l.flair_conv2d_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream()), "conv2d_ex")
-    return {"y": out, "out_skip": out_skip, "y_nchw": yn, "stats": st, "preds": pr, "maxprob": mp}
+    return outs
+
+
+def conv2d_ex_grid_rows(x0, w, **kw):
+    """flair_conv2d_ex_grid_rows for the arguments of conv2d_ex (nothing is launched): the row blocks of stats / bnr_partial.
+    Pass bnr_y to ask for the launch WITH the fused reduction."""
+    import ctypes as C
+    a, _ = _conv_ex_args(x0, w, **kw)
+    rows = L.lib().flair_conv2d_ex_grid_rows(C.addressof(a))
+    L.check(min(rows, 0), "conv2d_ex_grid_rows")
+    return rows
 
 
 def conv2d_wgrad_ex(x0, dy, Cout, R=3, stride=1, pad=1, x1=None, up0=False, in_scale=None, in_shift=None, dw=None, accumulate=False,
-                    want_dbias=False, cus=0, cin_real=0):
-    """flair_conv2d_wgrad_ex: dw (and the fused dbias) of conv(cat([up2(x0)?, x1])) against dy [N][Ho][Wo][dy_ld >= Cout]."""
+                    want_dbias=False, cus=0, cin_real=0, fuse_y=None, fuse_coef=None, fuse_msc=None, fuse_msh=None):
+    """flair_conv2d_wgrad_ex: dw (and the fused dbias) of conv(cat([up2(x0)?, x1])) against dy [N][Ho][Wo][dy_ld >= Cout].
+    fuse_y / fuse_coef (k1 | k2 | k3) / fuse_msc / fuse_msh: the stem kernel's fused BatchNorm-backward apply on dy."""
     import ctypes as C
     N, H, W, C0 = x0.shape
     C1 = x1.shape[3] if x1 is not None else 0
@@ -125,7 +152,8 @@ def conv2d_wgrad_ex(x0, dy, Cout, R=3, stride=1, pad=1, x1=None, up0=False, in_s
     db = torch.empty(Cout, dtype=torch.float32, device=dev) if want_dbias else None
     a = L.WgradEx(dtype=dt, x0=L.ptr(x0), x1=L.ptr(x1), N=N, H=H, W=W, C0=C0, C1=C1, up0=int(up0), dy=L.ptr(dy), dy_ld=dy.shape[3],
                   Cout=Cout, R=R, stride=stride, pad=pad, dw=L.ptr(dw), Cin_real=cin_real, accumulate=int(accumulate),
-                  in_scale=L.ptr(in_scale), in_shift=L.ptr(in_shift), dbias=L.ptr(db), cus=cus)
+                  in_scale=L.ptr(in_scale), in_shift=L.ptr(in_shift), dbias=L.ptr(db), cus=cus,
+                  fuse_y=L.ptr(fuse_y), fuse_coef=L.ptr(fuse_coef), fuse_msc=L.ptr(fuse_msc), fuse_msh=L.ptr(fuse_msh))
     l = L.lib()
     ws = _ws(l.flair_conv2d_wgrad_ex_workspace_bytes(C.addressof(a)), dev)
     L.check(l.flair_conv2d_wgrad_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream()), "conv2d_wgrad_ex")
@@ -157,6 +185,111 @@ def bn_relu_backward(dout, out, y, gamma, mean, invstd, relu=True, want_dres=Fal
                                            L.ptr(invstd), int(relu), L.ptr(dy), L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta),
                                            L.ptr(ws), ws.numel(), L.stream()), "bn_relu_backward")
     return dy, dres, dgamma, dbeta
+
+
+def bn_backward_ex(dout, y, mean, invstd, gamma=None, out=None, mscale=None, mshift=None, partial=None, pre_nblk=0, premasked=False,
+                   dgamma=None, dbeta=None, accumulate_param=False, want_dy=True, dy=None, dres=None, want_dres=False,
+                   dres_accumulate=False, coef=None, rc=False):
+    """flair_bn_backward_ex: bn_backward as the network calls it.  partial [2][C][pre_nblk] fp32 with pre_nblk > 0: the producer's
+    block sums; dy, dgamma / dbeta, coef are allocated unless given (accumulate_param adds into dgamma / dbeta); dres given or want_dres.
+    Returns a dict: dy, dres, dgamma, dbeta, coef [3][C]."""
+    import ctypes as C
+    Cc = y.shape[-1]
+    rows = y.numel() // Cc
+    dev = y.device
+    if dy is None and want_dy:
+        dy = torch.empty_like(y)
+    if dres is None and want_dres:
+        assert not dres_accumulate
+        dres = torch.empty_like(y)
+    if dgamma is None:
+        assert not accumulate_param
+        dgamma = torch.empty(Cc, dtype=torch.float32, device=dev)
+        dbeta = torch.empty(Cc, dtype=torch.float32, device=dev)
+    if coef is None:
+        coef = torch.empty(3, Cc, dtype=torch.float32, device=dev)
+    a = L.BnBwdEx(dtype=_dt(y), dout=L.ptr(dout), out=L.ptr(out), y=L.ptr(y), mean=L.ptr(mean), invstd=L.ptr(invstd), gamma=L.ptr(gamma),
+                  rows=rows, C=Cc, partial=L.ptr(partial), pre_nblk=pre_nblk, premasked=int(premasked), mscale=L.ptr(mscale),
+                  mshift=L.ptr(mshift), dgamma=L.ptr(dgamma), dbeta=L.ptr(dbeta), accumulate_param=int(accumulate_param), dy=L.ptr(dy),
+                  dres=L.ptr(dres), dres_accumulate=int(dres_accumulate), coef=L.ptr(coef))
+    ws = _ws(L.lib().flair_bn_workspace_bytes(rows, Cc), dev)
+    r = L.lib().flair_bn_backward_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream())
+    return _ret(r, "bn_backward_ex", {"dy": dy, "dres": dres, "dgamma": dgamma, "dbeta": dbeta, "coef": coef}, rc)
+
+
+def maxpool_backward_ex(dy, idx, H, W, dx=None, accumulate=False, bnr_y=None, bnr_msc=None, bnr_msh=None, bnr_partial=None, rc=False):
+    """flair_maxpool_backward_ex: dx (+= with accumulate); bnr_partial fp32 [2][C][N * H] receives the fused reduction."""
+    N, _, _, Cc = dy.shape
+    if dx is None:
+        assert not accumulate
+        dx = torch.empty(N, H, W, Cc, dtype=dy.dtype, device=dy.device)
+    r = L.lib().flair_maxpool_backward_ex(_dt(dy), L.ptr(dy), L.ptr(idx), L.ptr(dx), int(accumulate), N, H, W, Cc, L.ptr(bnr_y),
+                                          L.ptr(bnr_msc), L.ptr(bnr_msh), L.ptr(bnr_partial), L.stream())
+    return _ret(r, "maxpool_backward_ex", dx, rc)
+
+
+def bn_act_maxpool(y, scale, shift, rc=False):
+    """flair_bn_act_maxpool: (act, pooled, idx) of relu(y * scale + shift) and its 3x3 / stride-2 max pool."""
+    N, H, W, Cc = y.shape
+    act = torch.empty_like(y)
+    out = torch.empty(N, H // 2, W // 2, Cc, dtype=y.dtype, device=y.device)
+    idx = torch.empty(N, H // 2, W // 2, Cc, dtype=torch.uint8, device=y.device)
+    r = L.lib().flair_bn_act_maxpool(_dt(y), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(act), L.ptr(out), L.ptr(idx), N, H, W, Cc,
+                                     L.stream())
+    return _ret(r, "bn_act_maxpool", (act, out, idx), rc)
+
+
+def bn_act(y, scale, shift, relu=True, rc=False):
+    """flair_bn_act: [relu](y * scale + shift), the standalone pass bn_act_maxpool folds into the pool."""
+    Cc = y.shape[-1]
+    out = torch.empty_like(y)
+    r = L.lib().flair_bn_act(_dt(y), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(out), y.numel() // Cc, Cc, int(relu), L.stream())
+    return _ret(r, "bn_act", out, rc)
+
+
+def upcat_bwd(dcat, C0, dx0=None, dx0_accumulate=False, dskip=None, dskip_accumulate=False, rc=False):
+    """flair_upcat_bwd: dcat [N][H][W][C0 + C1] -> (dx0 [N][H/2][W/2][C0], dskip [N][H][W][C1] or None)."""
+    N, H, W, Ct = dcat.shape
+    C1 = Ct - C0
+    if dx0 is None:
+        assert not dx0_accumulate
+        dx0 = torch.empty(N, H // 2, W // 2, C0, dtype=dcat.dtype, device=dcat.device)
+    if dskip is None and C1:
+        assert not dskip_accumulate
+        dskip = torch.empty(N, H, W, C1, dtype=dcat.dtype, device=dcat.device)
+    r = L.lib().flair_upcat_bwd(_dt(dcat), L.ptr(dcat), L.ptr(dx0), int(dx0_accumulate), L.ptr(dskip), int(dskip_accumulate), N, H, W,
+                                C0, C1, L.stream())
+    return _ret(r, "upcat_bwd", (dx0, dskip), rc)
+
+
+def ew_add_(dst, src, n=None, rc=False):
+    """flair_ew_add: dst[:n] += src[:n] in place (flat element count, default all)."""
+    n = dst.numel() if n is None else n
+    return _ret(L.lib().flair_ew_add(_dt(dst), L.ptr(dst), L.ptr(src), n, L.stream()), "ew_add", dst, rc)
+
+
+def colsum(x, C, rc=False):
+    """flair_colsum: fp32 [C] column sums of x [rows][ld], C <= ld."""
+    rows, ld = x.shape
+    out = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws = _ws(L.lib().flair_bn_workspace_bytes(rows, ld), x.device)
+    r = L.lib().flair_colsum(_dt(x), L.ptr(x), rows, ld, C, L.ptr(out), L.ptr(ws), ws.numel(), L.stream())
+    return _ret(r, "colsum", out, rc)
+
+
+def pack_weights(dtype, params, descs, arena, rc=False):
+    """flair_pack_weights: descs = list of dicts with the fields of flair_pack_desc_t (missing ones 0); params flat fp32, arena a
+    uint8 tensor the dst_off byte offsets point into."""
+    import ctypes as C
+    arr = (L.PackDesc * len(descs))(*[L.PackDesc(**d) for d in descs])
+    r = L.lib().flair_pack_weights(L.dtype_code(dtype), L.ptr(params), C.addressof(arr), len(descs), L.ptr(arena), L.stream())
+    return _ret(r, "pack_weights", arena, rc)
+
+
+def pack_weight(dtype, w, dst, Cout, Cin, R, S, Cin_p, rows_pad, Kpad, tf, rc=False):
+    """flair_pack_weight: the single-layer packer of the operator entry points, w (fp32 OIHW) -> dst [rows_pad][Kpad] of `dtype`."""
+    r = L.lib().flair_pack_weight(L.dtype_code(dtype), L.ptr(w), L.ptr(dst), Cout, Cin, R, S, Cin_p, rows_pad, Kpad, int(tf), L.stream())
+    return _ret(r, "pack_weight", dst, rc)
 
 
 def maxpool_forward(x):

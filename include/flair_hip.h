@@ -280,6 +280,16 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
  *   of x0 as stored), lazy input as above, dy rows of dy_ld elements (0 = Cout), Cin_real = 0: C0 + C1.  dbias [Cout]: the column
  *   sums of dy from the same kernel (16 -> <= 16 channel layers with dy_ld == 16; -6 elsewhere).  cus: workgroup budget of the
  *   register-resident kernel (0 = default).
+ *   bnr_partial: the fused first pass of the BatchNorm backward of the unit that produced this data gradient's target (halo-tile
+ *     kernels, mode 1): y_nhwc (the pooled part with pool_c0) is the complete gradient dz; bnr_y is that unit's pre-BN tensor (shape
+ *     and row stride of y_nhwc), m = [bnr_y * bnr_scale[c] + bnr_shift[c] > 0], or [bnr_out > 0] with bnr_out (NHWC, as y_nhwc).
+ *     The kernel leaves sum(dz * m) and sum(dz * m * y) per row block in the caller's bnr_partial[2][out_ld][rows], rows =
+ *     flair_conv2d_ex_grid_rows() of the same struct; bnr_rows is the capacity of the buffer in row blocks (-100 when too small).
+ *     bnr_mask: store dz * m instead of dz (halo-GEMM only).
+ *   mode 2: the stride-2 data gradient by output parity class, as the network's backward pass launches it.  x0 is dy [N][H][W][C0],
+ *     w_oihw the FORWARD layer's [C0][Cout][R][R], y_nhwc is dx [N][2H][2W][out_ld].  R = 3, pad = 1: the four classes (1, 2, 2 and 4
+ *     taps) in one launch, their weights packed by the network's own class descriptors; R = 1, pad = 0: the (even, even) pixels
+ *     only (the network uses it with accumulate).  Any other geometry: -6.
  * Workspace: the _workspace_bytes call on the same struct (under the same flair_tune_set settings). */
 typedef struct flair_conv_ex {
   int dtype, mode;
@@ -295,6 +305,8 @@ typedef struct flair_conv_ex {
   int pool_c0; void* out_skip; int out_skip_ld; int skip_accumulate;
   uint8_t* preds_u8; float* maxprob_f32;
   int ogelu;   /* y = gelu_erf(acc (+ bias)) before ores / orelu: the gather-form GEMM only (-6 elsewhere) */
+  const void* bnr_y; const void* bnr_out; const float* bnr_scale; const float* bnr_shift;
+  float* bnr_partial; int bnr_rows; int bnr_mask;
 } flair_conv_ex_t;
 typedef struct flair_wgrad_ex {
   int dtype;
@@ -305,9 +317,15 @@ typedef struct flair_wgrad_ex {
   float* dw; int Cin_real; int accumulate;
   const float* in_scale; const float* in_shift;
   float* dbias; int cus;
+  /* the stem's weight-gradient kernel only (-6 elsewhere): dy is the gradient w.r.t. the unit's ReLU output and the kernel stages
+   * k1 * dz + k2 * y + k3, dz = dy * [fuse_y * fuse_msc + fuse_msh > 0], fuse_coef = k1 | k2 | k3 (Cout floats each) */
+  const void* fuse_y; const float* fuse_coef; const float* fuse_msc; const float* fuse_msh;
 } flair_wgrad_ex_t;
 size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p);
 int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
+/* row blocks of the launch flair_conv2d_ex makes for this struct (= rows of stats / bnr_partial); bnr_y set counts as a request
+ * for the fused reduction even while bnr_partial is still NULL.  Negative: the struct is refused. */
+int flair_conv2d_ex_grid_rows(const flair_conv_ex_t* p);
 size_t flair_conv2d_wgrad_ex_workspace_bytes(const flair_wgrad_ex_t* p);
 int flair_conv2d_wgrad_ex(const flair_wgrad_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
 /* workspace of flair_bn_relu_forward / _backward for `rows` rows of C channels */
@@ -320,9 +338,58 @@ int flair_bn_relu_backward(int dtype, const void* dout, const void* out, const v
                            const float* gamma, const float* save_mean, const float* save_invstd, int relu, void* dy,
                            void* dres, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes,
                            void* stream);
+/* bn_backward with every argument the network sets.  pre_nblk > 0: `partial` [2][C][pre_nblk] is the caller's and already holds
+ * that many producer-side block sums (flair_conv2d_ex bnr_partial, flair_maxpool_backward_ex); premasked: dout is dz already.
+ * pre_nblk == 0: the reduction runs here on workspace (flair_bn_workspace_bytes), mask from `out` (> 0), else from
+ * y * mscale + mshift > 0, else none.  dgamma / dbeta (+= with accumulate_param), dy = k1 dz + k2 y + k3, dres (+)= dz;
+ * dy == dres == NULL: coefficients only.  coef (optional) receives k1 | k2 | k3, 3 * C floats. */
+typedef struct flair_bn_bwd_ex {
+  int dtype;
+  const void* dout; const void* out; const void* y;
+  const float* mean; const float* invstd; const float* gamma;
+  int64_t rows; int C;
+  float* partial; int pre_nblk; int premasked;
+  const float* mscale; const float* mshift;
+  float* dgamma; float* dbeta; int accumulate_param;
+  void* dy; void* dres; int dres_accumulate;
+  float* coef;
+} flair_bn_bwd_ex_t;
+int flair_bn_backward_ex(const flair_bn_bwd_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
 int flair_maxpool_forward(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
 int flair_maxpool_backward(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
                            void* stream);
+/* dx (+= with accumulate); bnr_partial [2][C][N * H]: per input row, sum(dx * m) and sum(dx * m * bnr_y), m = [bnr_y * bnr_msc +
+ * bnr_msh > 0], of the stored dx (the stem's BatchNorm-backward reduction) */
+int flair_maxpool_backward_ex(int dtype, const void* dy, const uint8_t* idx, void* dx, int accumulate, int N, int H, int W, int C,
+                              const void* bnr_y, const float* bnr_msc, const float* bnr_msh, float* bnr_partial, void* stream);
+int flair_bn_act(int dtype, const void* y, const float* scale, const float* shift, void* out, int64_t rows, int C, int relu,
+                 void* stream);   /* out = [relu](y * scale[c] + shift[c]) */
+/* act = relu(y * scale + shift) [N][H][W][C] and its 3x3 / stride-2 max pool out, idx [N][H/2][W/2][C] in one pass */
+int flair_bn_act_maxpool(int dtype, const void* y, const float* scale, const float* shift, void* act, void* out, uint8_t* idx, int N,
+                         int H, int W, int C, void* stream);
+/* backward of cat([up2(x0), skip]): dcat [N][H][W][C0 + C1] -> dx0 [N][H/2][W/2][C0] (2x2 sums), dskip [N][H][W][C1] */
+int flair_upcat_bwd(int dtype, const void* dcat, void* dx0, int dx0_accumulate, void* dskip, int dskip_accumulate, int N, int H, int W,
+                    int C0, int C1, void* stream);
+int flair_ew_add(int dtype, void* dst, const void* src, int64_t n, void* stream);   /* dst += src, n elements */
+/* out[c] = sum over rows of x[rows][ld], c < C; workspace: flair_bn_workspace_bytes(rows, ld) */
+int flair_colsum(int dtype, const void* x, int64_t rows, int ld, int C, float* out, void* workspace, size_t workspace_bytes,
+                 void* stream);
+/* pack_weights_all: n (<= 64) fp32 OIHW masters at params + w_off -> packed copies at base + dst_off (bytes) in one launch.
+ * tf = 0: dst[k][tap * Cin_p + c] = w[k][c][r][s]; tf = 1: dst[c][tap * Cin_p + k] = w[k][c][R-1-r][S-1-s]; rows_pad x Kpad
+ * elements, everything outside the real region zero.  Rc > 0: packed tap (ri, si), ri < Rc, si < Sc, is tap (r0 + ri * rstep,
+ * s0 + si * sstep) of the full pack.  In bf16 the 3x3 packs whose channel counts allow it (tf = 0: Cin % 4 == 0 and no tap
+ * subset; tf = 1: Cin % 32 == 0 and Cout % 32 == 0) read their master 16 bytes at a time: params 16-byte aligned and
+ * w_off % 4 == 0, else -2. */
+typedef struct flair_pack_desc {
+  int64_t w_off; uint64_t dst_off;
+  int Cout, Cin, R, S, Cin_p, rows_pad, Kpad, tf;
+  int r0, rstep, Rc, s0, sstep, Sc;
+} flair_pack_desc_t;
+int flair_pack_weights(int dtype, const float* params, const flair_pack_desc_t* descs, int n, void* base, void* stream);
+/* pack_weight, the single-layer packer of the operator entry points above: the same layout (no tap subsets) into
+ * dst[rows_pad][Kpad]. */
+int flair_pack_weight(int dtype, const float* w_oihw, void* dst, int Cout, int Cin, int R, int S, int Cin_p, int rows_pad, int Kpad,
+                      int tf, void* stream);
 int flair_nchw_to_nhwc(int dtype, const float* x_nchw, void* y_nhwc, int N, int C, int H, int W, int Cpad, void* stream);
 int flair_nhwc_to_nchw(int dtype, const void* x_nhwc, float* y_nchw, int N, int C, int H, int W, int Cpad, void* stream);
 

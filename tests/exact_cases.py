@@ -70,17 +70,20 @@ def hg_tile_pixels(Hout, Wout, Cout):
     return 128 if can128 else 256 if can256 else 0
 
 
-def hg_applicable(dt, C0, C1, Cout, R, out_mul, in_div, pad, Hin, Win, Hout, Wout, has_out, nchw, in_scale=False, pool_c0=0):
+def hg_applicable(dt, C0, C1, Cout, R, out_mul, in_div, pad, Hin, Win, Hout, Wout, has_out, nchw, in_scale=False, pool_c0=0, bnr=False):
+    """conv_hg_applicable; bnr: ConvArgs::bnr_partial is set."""
     ck = 32 if dt == "f32" else 64
     Cin = C0 + C1
     if R != 3 or out_mul != 1 or in_div != 1 or pad != 1:
         return False
     if Hout != Hin or Wout != Win or nchw or not has_out:
         return False
+    if in_scale and bnr:
+        return False
     if Cin % ck or C0 % ck:
         return False
     if Cout == 32:
-        return not in_scale and pool_c0 == 0 and ((Wout % 32 == 0 and Hout % 8 == 0) or (Wout % 16 == 0 and Hout % 16 == 0))
+        return not bnr and not in_scale and pool_c0 == 0 and ((Wout % 32 == 0 and Hout % 8 == 0) or (Wout % 16 == 0 and Hout % 16 == 0))
     if Cout < 64 or Cout % 64:
         return False
     return hg_tile_pixels(Hout, Wout, Cout) != 0
@@ -96,14 +99,30 @@ def hg_shape(Hout, Wout, Cout):
     return (32, 8, bn) if Wout % 32 == 0 else (16, 16, bn)
 
 
+def halo_bnr_ok(C0, C1, Cout, out_ld, pool_c0=0, nchw=False, stats=False, bias=False, in_scale=False, epilogue=False, bnr_out=False):
+    """conv_halo_bnr_ok for a shape the small-channel halo kernel takes (bnr_C = out_ld)."""
+    persistent = C1 == 0 and C0 in (16, 32) and Cout <= 32
+    return (persistent and not (in_scale or stats or epilogue or bias or nchw or bnr_out) and out_ld <= 32
+            and out_ld <= (16 if Cout <= 16 else 32) and pool_c0 in (0, Cout))
+
+
 def conv_kernel(dt, N, Hin, Win, Hout, Wout, C0, C1, Cout, R, out_mul, in_div, pad, has_out=True, nchw=False, stats=False,
-                bias=False, in_scale=False, pool_c0=0, epilogue=False, bm32=2):
-    """(family, profile name) of the kernel launch_conv picks.  Families: stem, hg_n32/64/128, halo_pm, halo_p, halo, igemm."""
+                bias=False, in_scale=False, pool_c0=0, epilogue=False, bm32=2, bnr=False, bnr_out=False, bnr_mask=False, acc_src=False):
+    """(family, profile name) of the kernel launch_conv picks.  Families: stem, hg_n32/64/128, halo_pm, halo_p, halo, igemm.
+    bnr (ConvArgs::bnr_partial): the fused BatchNorm-backward reduction; a combination launch_conv refuses is an AssertionError."""
     Cin = C0 + C1
     tdt = dt  # profile names spell the type this way
     geo = (C0, C1, Cout, R, out_mul, in_div, pad, Hin, Win, Hout, Wout)
-    hg = hg_applicable(dt, *geo, has_out, nchw, in_scale, pool_c0)
+    hg = hg_applicable(dt, *geo, has_out, nchw, in_scale, pool_c0, bnr)
     halo = halo_applicable(*geo)
+    if bnr_mask or acc_src:
+        assert hg, "bnr_mask / acc_src: halo-GEMM only"
+    if bnr_mask:
+        assert bnr, "bnr_mask needs bnr_partial"
+    if bnr:
+        assert Hout % 2 == 0 and Wout % 2 == 0
+        assert hg or (halo and halo_bnr_ok(C0, C1, Cout, pool_c0 or Cout, pool_c0, nchw, stats, bias, in_scale, epilogue, bnr_out)), \
+            "fused reduction: halo-GEMM or the persistent small-channel kernel only"
     if in_scale:
         assert hg or halo, "lazy input: halo-GEMM or small-channel halo kernel only"
     kstep = 32 if dt == "f32" else 64
