@@ -182,9 +182,26 @@ def wgrad_kernel(dt, N, Hin, Win, Hout, Wout, C0, C1, Cout, R, stride, pad, dy_l
         name = "wgrad3x3_halo_f32" if dt == "f32" else f"wgrad3x3_halo_bf16_ck{CK}"
         return "halo", name, {"ntiles": N * Hin * Win // 256, "per": (Cin // CK) * (cout_pad // CO), "step": 2}
     assert not in_scale and not dbias
+    geo = wg_plan(dt, N * Hout * Wout, Cin, Cout, R)
     if dt == "f32":
-        return "plain", "wgrad_f32_64x64", {}
-    return "plain", ("wgrad_bf16_128x128" if (Cout >= 128 and R * R * Cin >= 128) else "wgrad_bf16_64x64"), {}
+        return "plain", "wgrad_f32_64x64", geo
+    return "plain", ("wgrad_bf16_128x128" if (Cout >= 128 and R * R * Cin >= 128) else "wgrad_bf16_64x64"), geo
+
+
+def wg_plan(dt, M, Cin, Cout, R):
+    """wg_plan and launch_wgrad_reduce of the gather-form weight gradient (wgrad.hip): the split count over the M output pixels, the
+    pixels per split and of the last one, and the reduce kernel: its EL (elements per workgroup row), its grid and the passes a
+    workgroup makes over the gradient (the grid is capped at 8 192 workgroups for EL = 64)."""
+    Kg = R * R * Cin
+    b = 128 if (dt == "bf16" and Cout >= 128 and Kg >= 128) else 64
+    tiles = (_rup(Cout, b) // b) * (_rup(Kg, b) // b)
+    want = max(1, min(_cdiv(768, tiles), max(1, _cdiv(M, 64 * 8))))
+    pps = _rup(_cdiv(M, want), 64)
+    splits = _cdiv(M, pps)
+    total = Cout * Kg
+    el = 16 if (splits >= 64 and total <= 65536) else 64
+    grid = _cdiv(total, el) if el == 16 else min(_cdiv(total, 64), 8192)
+    return {"splits": splits, "pps": pps, "last": M - (splits - 1) * pps, "reduce_el": el, "reduce_grid": grid, "reduce_total": total}
 
 
 def tiles_per_workgroup(ntiles, grid):
@@ -335,6 +352,13 @@ CONV_CASES = [
     ConvCase("g3x3_16to13_bias_nchw_240px", 1, 12, 20, 16, 13, bias=True, nchw=True, stats=False, backward=False, fwd="igemm"),
     ConvCase("g3x3_64to192_120px", 1, 10, 12, 64, 192, nchw=True, fwd="igemm", dx="igemm_bm32", dw="plain"),
     ConvCase("g3x3_32to16_nontileable", 2, 20, 24, 32, 16, fwd="igemm", dx="igemm", dw="plain"),
+    # the gather-form weight gradient past one or two splits (WG_PLAN_WANT below has the numbers): 14 splits of 512 pixels, the last
+    # with 256, reduced by wgrad_reduce_kernel<64> in its four-way loop (slab groups 0 and 1) and its remainder loop (2 and 3);
+    # 66 splits of a 2 304-element gradient: wgrad_reduce_kernel<16>; a 1 179 648-element gradient: the reduce grid at its 8 192-block
+    # cap, three passes, the last one ragged
+    ConvCase("g3x3s2_64to128_14splits", 3, 96, 96, 64, 128, stride=2, fwd="igemm", dx="igemm_bm32", dw="plain"),
+    ConvCase("g3x3_16to16_w48_66splits", 1, 704, 48, 16, 16, density=0.25, fwd="igemm", dx="igemm", dw="plain"),
+    ConvCase("g3x3s2_256to512_reduce_cap", 1, 8, 8, 256, 512, stride=2, density=0.25, fwd="igemm", dx="igemm_bm32", dw="plain"),
     # 7x7 stride-2 stem, 5 real channels of 8: fp32 gather form, bf16 direct kernels (8x16 tiles, 512 persistent workgroups:
     # 560 tiles -> 2 and 1 per workgroup)
     ConvCase("stem_560tiles", 5, 256, 224, 8, 64, R=7, stride=2, pad=3, need_dx=False, real_cin=5,
@@ -343,6 +367,30 @@ CONV_CASES = [
              fwd={"f32": "igemm", "bf16": "stem"}, dw={"f32": "plain", "bf16": "stem"}),
     ConvCase("stem_18x20_gather_form", 2, 36, 40, 8, 64, R=7, stride=2, pad=3, need_dx=False, real_cin=5, fwd="igemm", dw="plain"),
 ]
+
+
+# name -> (splits, pixels per split, pixels of the last split, reduce EL, reduce grid), both dtypes alike
+WG_PLAN_WANT = {
+    "g3x3s2_64to128_14splits": (14, 512, 256, 64, 1152),
+    "g3x3_16to16_w48_66splits": (66, 512, 512, 16, 144),
+    "g3x3s2_256to512_reduce_cap": (1, 64, 16, 64, 8192),
+}
+WG_ACCUMULATE_CASE = "g3x3s2_64to128_14splits"     # run again through conv2d_wgrad_ex(dw=prefilled, accumulate=True)
+
+
+def check_wg_plan(c):
+    """The gather-form weight gradient of the case splits and reduces as the table says (asserted on the restated wg_plan)."""
+    for dt in c.dtypes:
+        fam, _, g = c.dw_kernel(dt)
+        assert fam == "plain", (c.name, dt, fam)
+        got = (g["splits"], g["pps"], g["last"], g["reduce_el"], g["reduce_grid"])
+        assert got == WG_PLAN_WANT[c.name], (c.name, dt, got)
+        if g["reduce_el"] == 64 and g["splits"] > 1:     # G = 4 slab groups: the four-way loop runs where z + 12 < splits
+            four = [zg for zg in range(4) if zg + 12 < g["splits"]]
+            assert four and len(four) < 4, (c.name, "both loops of wgrad_reduce_kernel<64>")
+        if g["reduce_grid"] == 8192:
+            blocks = _cdiv(g["reduce_total"], 64)
+            assert blocks > 2 * 8192 and blocks % 8192, (c.name, "ragged last pass", blocks)
 
 
 def case_inputs(c):

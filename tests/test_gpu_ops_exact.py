@@ -119,6 +119,22 @@ def test_conv_exact(dev, dt, case):
         _same(dw.cpu(), ref["dw"], "dw")
 
 
+@pytest.mark.parametrize("dt", E.DTYPES)
+def test_gather_wgrad_accumulates_into_a_prefilled_dw(dev, dt):
+    """The 14-split gather-form case again through flair_conv2d_wgrad_ex with accumulate: wgrad_reduce_kernel adds its sum to what
+    dw held (integers: exact)."""
+    from flair_amd import ops
+    case = next(c for c in E.CONV_CASES if c.name == E.WG_ACCUMULATE_CASE)
+    ref = E.case_reference(case)
+    E.check_wg_plan(case)
+    prev = E.ints(tuple(ref["dw"].shape), torch.Generator().manual_seed(14), -64, 64)
+    dw = prev.to(dev)
+    _, ran = _profiled(lambda: ops.conv2d_wgrad_ex(_nhwc(ref["x0"], dt, dev), _nhwc(ref["dy"], dt, dev), case.Cout, stride=case.stride,
+                                                   pad=case.pad, dw=dw, accumulate=True))
+    assert ran == {case.dw_kernel(dt)[1]: 1}, ran
+    _same(dw.cpu(), ref["dw"] + prev.double(), "dw += weight gradient")
+
+
 # ------------------------------------------------------------------------------------------------ fused forms (flair_conv2d_ex / _wgrad_ex)
 def _vec(t, dev):
     return None if t is None else t.to(dev)

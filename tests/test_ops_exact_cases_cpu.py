@@ -54,5 +54,15 @@ def test_the_table_covers_what_it_promises():
     assert {(dt, k) for dt in E.DTYPES for k in ("big_kg1", "big_kg2", "halo", "plain")} <= kgs and ("bf16", "stem") in kgs
 
 
+def test_gather_form_weight_gradient_splits_as_the_table_says():
+    """14 splits with a short last one (both loops of the 64-wide reduce), 66 splits (the 16-wide reduce), and a gradient past the
+    reduce grid's cap; one of them runs again with accumulate."""
+    cases = {c.name: c for c in E.CONV_CASES}
+    assert set(E.WG_PLAN_WANT) <= set(cases) and E.WG_ACCUMULATE_CASE in E.WG_PLAN_WANT
+    for name in E.WG_PLAN_WANT:
+        E.check_wg_plan(cases[name])
+    assert {v[0] for v in E.WG_PLAN_WANT.values()} == {14, 66, 1}
+
+
 def test_reduction_shapes_pass_their_caps():
     E.check_reduction_shapes()
