@@ -4,6 +4,7 @@
 
 #include "../../include/flair_hip.h"
 #include "unet.h"
+#include "conv_args.h"
 #include "parity_pack.h"
 #include "segformer.h"
 #include "upernet.h"
@@ -349,92 +350,56 @@ struct OpArena {
   }
 };
 
-static void conv_geom(int dtype, int C0, int C1, int Cout, int R, int& Cin, int& Kg, int& Kpad, int& rows_f) {
-  Cin = C0 + C1;
-  const int kstep = dtype == DT_F32 ? 32 : 64;
-  Kg = R * R * Cin;
-  Kpad = (int)round_up(Kg, kstep);
-  rows_f = conv_weight_rows_pad(Cout);
-}
-
 size_t flair_conv2d_workspace_bytes(int dtype, int N, int H, int W, int C0, int C1, int up0, int Cout, int R, int stride,
                                     int pad) {
-  int Cin, Kg, Kpad, rows_f;
-  conv_geom(dtype, C0, C1, Cout, R, Cin, Kg, Kpad, rows_f);
-  const int Hin = up0 ? 2 * H : H, Win = up0 ? 2 * W : W;
-  const int Ho = (Hin + 2 * pad - R) / stride + 1, Wo = (Win + 2 * pad - R) / stride + 1;
   const size_t es = dtype_size(dtype);
-  size_t b = (size_t)rows_f * Kpad * es + 4096;
-  b += ((size_t)N * Ho * Wo / 128 + 2) * 2 * Cout * 4 + 4096;            // stats partial
-  int CoutP = (int)round_up(Cout, 8);
-  const int kstep = dtype == DT_F32 ? 32 : 64;
-  b += (size_t)conv_weight_rows_pad(Cin) * round_up((long)R * R * CoutP, kstep) * es + 4096;  // dgrad pack
+  const ConvInput in{nullptr, nullptr, C0, C1, up0, N, H, W};
+  ConvArgs a;
+  conv_fwd_args(a, dtype, in, R, stride, pad, Cout);
+  size_t b = (size_t)conv_weight_rows_pad(Cout) * a.Kpad * es + 4096;
+  b += ((size_t)N * a.Hout * a.Wout / 128 + 2) * 2 * Cout * 4 + 4096;            // stats partial
+  const int CoutP = (int)round_up(Cout, 8);
+  b += (size_t)conv_weight_rows_pad(C0 + C1) * conv_kpad(dtype, R * R * CoutP) * es + 4096;  // dgrad pack
   WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  w.C0 = C0; w.C1 = C1; w.N = N; w.Hin = Hin; w.Win = Win; w.Hout = Ho; w.Wout = Wo; w.R = R; w.S = R; w.Cout = Cout;
-  w.stride = stride; w.pad = pad; w.up0 = up0; w.dy_ld = CoutP;
+  wgrad_args(w, in, R, stride, pad, nullptr, CoutP, Cout, nullptr, 0);
   b += wgrad_workspace_bytes(dtype, w) + 4096;
   return b;
 }
 
+// the plain forward is the fused form with every option off: one code path, the same arena layout and launches
 int flair_conv2d_forward(int dtype, const void* x0, const void* x1, int N, int H, int W, int C0, int C1, int up0,
                          const float* w_oihw, const float* bias, int Cout, int R, int stride, int pad, void* y_nhwc,
                          float* y_nchw, float* stats, void* workspace, size_t wsb, void* stream) {
-  if (!x0 || !w_oihw || !workspace) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  int Cin, Kg, Kpad, rows_f;
-  conv_geom(dtype, C0, x1 ? C1 : 0, Cout, R, Cin, Kg, Kpad, rows_f);
-  OpArena ar(workspace, wsb);
-  void* wp = ar.get((size_t)rows_f * Kpad * dtype_size(dtype));
-  ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src0 = x0; a.src1 = x1; a.C0 = C0; a.C1 = x1 ? C1 : 0; a.up0 = up0; a.N = N;
-  a.Hin = up0 ? 2 * H : H; a.Win = up0 ? 2 * W : W;
-  a.Hout = (a.Hin + 2 * pad - R) / stride + 1; a.Wout = (a.Win + 2 * pad - R) / stride + 1;
-  a.R = R; a.S = R; a.out_mul = stride; a.pad = pad; a.in_div = 1; a.Cout = Cout; a.Kg = Kg; a.Kpad = Kpad; a.w = wp;
-  a.bias = bias; a.out = y_nhwc; a.out_ld = Cout; a.out_nchw = y_nchw;
-  // the row count must be that of the kernel launch_conv picks WITH statistics on (bf16 32 -> 128: the multi-block persistent
-  // kernel writes none and has a capped grid; the per-tile kernel that runs instead has one row per tile)
-  a.stats = stats;
-  const int nblk = conv_grid_rows(dtype, a);
-  float* partial = stats ? (float*)ar.get((size_t)nblk * 2 * Cout * 4) : nullptr;
-  a.stats = partial;
-  if (ar.bad) return -100;
-  int rc = pack_weight(dtype, w_oihw, wp, Cout, Cin, R, R, Cin, rows_f, Kpad, 0, s);
-  if (rc) return rc;
-  rc = launch_conv(dtype, a, s);
-  if (rc) return rc;
-  if (stats) rc = partial_rows_sum(partial, nblk, 2 * Cout, stats, s);
-  return rc;
+  flair_conv_ex_t p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = dtype; p.x0 = x0; p.x1 = x1; p.N = N; p.H = H; p.W = W; p.C0 = C0; p.C1 = C1; p.up0 = up0;
+  p.w_oihw = w_oihw; p.bias = bias; p.Cout = Cout; p.R = R; p.stride = stride; p.pad = pad;
+  p.y_nhwc = y_nhwc; p.y_nchw = y_nchw; p.stats = stats;
+  return flair_conv2d_ex(&p, workspace, wsb, stream);
 }
 
 int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Cin, const float* w_oihw, int Cout, int R,
                           int stride, int pad, const void* dy, void* dx, float* dw, void* workspace, size_t wsb, void* stream) {
   if (!x0 || !w_oihw || !dy || !workspace) return -1;
   hipStream_t s = (hipStream_t)stream;
-  const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
+  const int Ho = conv_out_extent(H, R, stride, pad), Wo = conv_out_extent(W, R, stride, pad);
   OpArena ar(workspace, wsb);
   int rc = 0;
   if (dx) {
-    const int kstep = dtype == DT_F32 ? 32 : 64;
-    const int Kgd = R * R * Cout, Kpad_d = (int)round_up(Kgd, kstep), rows_d = conv_weight_rows_pad(Cin);
-    void* wd = ar.get((size_t)rows_d * Kpad_d * dtype_size(dtype));
-    if (ar.bad) return -100;
-    rc = pack_weight(dtype, w_oihw, wd, Cout, Cin, R, R, Cout, rows_d, Kpad_d, 1, s);
-    if (rc) return rc;
     ConvArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src0 = dy; a.C0 = Cout; a.N = N; a.Hin = Ho; a.Win = Wo; a.Hout = H; a.Wout = W; a.R = R; a.S = R;
-    a.out_mul = 1; a.pad = R - 1 - pad; a.in_div = stride; a.Cout = Cin; a.Kg = Kgd; a.Kpad = Kpad_d; a.w = wd;
-    a.out = dx; a.out_ld = Cin;
+    conv_dgrad_args(a, dtype, ConvInput{dy, nullptr, Cout, 0, 0, N, Ho, Wo}, R, stride, pad, H, W, Cin);
+    const int rows_d = conv_weight_rows_pad(Cin);
+    void* wd = ar.get((size_t)rows_d * a.Kpad * dtype_size(dtype));
+    if (ar.bad) return -100;
+    rc = pack_weight(dtype, w_oihw, wd, Cout, Cin, R, R, Cout, rows_d, a.Kpad, 1, s);
+    if (rc) return rc;
+    a.w = wd; a.out = dx; a.out_ld = Cin;
     rc = launch_conv(dtype, a, s);
     if (rc) return rc;
   }
   if (dw) {
     WgradArgs w;
-    memset(&w, 0, sizeof(w));
-    w.x0 = x0; w.C0 = Cin; w.N = N; w.Hin = H; w.Win = W; w.Hout = Ho; w.Wout = Wo; w.R = R; w.S = R;
-    w.stride = stride; w.pad = pad; w.dy = dy; w.dy_ld = Cout; w.Cout = Cout; w.dw = dw; w.Cin_real = Cin;
+    wgrad_args(w, ConvInput{x0, nullptr, Cin, 0, 0, N, H, W}, R, stride, pad, dy, Cout, Cout, dw, Cin);
     w.partial = (float*)ar.get(wgrad_workspace_bytes(dtype, w));
     if (ar.bad) return -100;
     rc = launch_wgrad(dtype, w, s);
@@ -443,40 +408,33 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
 }
 
 // ---- the fused forms of the same launchers (plain structs in, ConvArgs / WgradArgs out; no kernel differs)
-static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a, int& Cin, int& rows_f) {
+static int conv_ex_fill(const flair_conv_ex_t* p, ConvArgs& a) {
   if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
   if (p->mode != 0 && p->mode != 1 && p->mode != 2) return -2;
   if (p->mode == 1 && p->stride != 1) return -6;   // (mode 2 is the stride-2 data gradient)
-  memset(&a, 0, sizeof(a));
-  int Kg, Kpad;
-  conv_geom(p->dtype, p->C0, p->x1 ? p->C1 : 0, p->Cout, p->R, Cin, Kg, Kpad, rows_f);
+  const ConvInput in{p->x0, p->x1, p->C0, p->x1 ? p->C1 : 0, p->up0, p->N, p->H, p->W};
+  const int out_ld = p->out_ld > 0 ? p->out_ld : p->Cout;
   if (p->mode == 2) {
-    // UNet::unit_backward, DG_PARITY: stride-1 convolutions over dY, stores interleaved into dX
+    // the network's stride-2 data gradient (UNet::unit_backward, DG_PARITY): x0 is dY, the output twice its extent
     const bool r3 = p->R == 3 && p->pad == 1, r1 = p->R == 1 && p->pad == 0;
     if (p->stride != 2 || (!r3 && !r1) || p->x1 || p->up0) return -6;
-    a.src0 = p->x0; a.C0 = p->C0; a.N = p->N; a.Hin = p->H; a.Win = p->W; a.Hout = p->H; a.Wout = p->W;
-    a.R = p->R; a.S = p->R; a.out_mul = 1; a.pad = 0; a.in_div = 1; a.out_sub = 1;
-    a.Cout = p->Cout; a.Kg = Kg; a.Kpad = Kpad;
-    a.out = p->y_nhwc; a.out_ld = p->out_ld > 0 ? p->out_ld : p->Cout; a.accumulate = p->accumulate;
-    if (r3) {
-      a.ncls = 4; a.R = 2; a.S = 2;
-      int kg[4];
-      for (int cls = 0; cls < 4; ++cls) parity_class_geom(p->dtype, p->C0, cls, kg[cls], a.cls_kpad[cls]);
-      a.Kg = (kg[0] + kg[1] + kg[2] + kg[3]) / 4;
-      a.Kpad = a.cls_kpad[3];
-    }
     // every other option of the struct belongs to kernels this form never reaches
     if (p->bias || p->y_nchw || p->stats || p->in_scale || p->in_shift || p->oscale || p->oshift || p->ores || p->orelu || p->acc_src ||
         p->pool_c0 || p->out_skip || p->preds_u8 || p->maxprob_f32 || p->ogelu || p->bnr_y || p->bnr_out || p->bnr_partial || p->bnr_mask)
       return -6;
+    conv_dgrad_args(a, p->dtype, in, p->R, p->stride, p->pad, 2 * p->H, 2 * p->W, p->Cout);
+    conv_parity_args(a, p->dtype, p->R);
+    a.out = p->y_nhwc; a.out_ld = out_ld; a.accumulate = p->accumulate;
     return 0;
   }
-  a.src0 = p->x0; a.src1 = p->x1; a.C0 = p->C0; a.C1 = p->x1 ? p->C1 : 0; a.up0 = p->up0; a.N = p->N;
-  a.Hin = p->up0 ? 2 * p->H : p->H; a.Win = p->up0 ? 2 * p->W : p->W;
-  const int pad = p->mode == 1 ? p->R - 1 - p->pad : p->pad;
-  a.Hout = (a.Hin + 2 * pad - p->R) / p->stride + 1; a.Wout = (a.Win + 2 * pad - p->R) / p->stride + 1;
-  a.R = p->R; a.S = p->R; a.out_mul = p->stride; a.pad = pad; a.in_div = 1; a.Cout = p->Cout; a.Kg = Kg; a.Kpad = Kpad;
-  a.bias = p->bias; a.out = p->y_nhwc; a.out_ld = p->out_ld > 0 ? p->out_ld : p->Cout; a.out_nchw = p->y_nchw;
+  // mode 1: the data gradient of a stride-1 layer, to the extent of that layer's input
+  if (p->mode == 1) {
+    const int fp = p->R - 1 - p->pad, up = in.up0 ? 2 : 1;   // (the flipped padding gives that layer's input extent)
+    conv_dgrad_args(a, p->dtype, in, p->R, 1, p->pad, conv_out_extent(up * in.H, p->R, 1, fp), conv_out_extent(up * in.W, p->R, 1, fp), p->Cout);
+  } else {
+    conv_fwd_args(a, p->dtype, in, p->R, p->stride, p->pad, p->Cout);
+  }
+  a.bias = p->bias; a.out = p->y_nhwc; a.out_ld = out_ld; a.out_nchw = p->y_nchw;
   a.in_scale = p->in_scale; a.in_shift = p->in_shift;
   a.oscale = p->oscale; a.oshift = p->oshift; a.ores = p->ores; a.orelu = p->orelu;
   a.accumulate = p->accumulate; a.acc_src = p->acc_src;
@@ -502,10 +460,7 @@ static void conv_ex_sizing(const flair_conv_ex_t* p, ConvArgs& a, float* standin
 static size_t conv_ex_parity_packs(const flair_conv_ex_t* p, ConvArgs& a, unsigned char* base, PackTable& tb) {
   const size_t es = dtype_size(p->dtype);
   const int rows_d = conv_weight_rows_pad(p->Cout);
-  PackDesc d;
-  memset(&d, 0, sizeof(d));
-  d.w_off = 0; d.dst_off = 0; d.Cout = p->C0; d.Cin = p->Cout; d.R = p->R; d.S = p->R;
-  d.Cin_p = p->C0; d.rows_pad = rows_d; d.Kpad = a.Kpad; d.tf = 1;
+  const PackDesc d = pack_desc(0, 0, p->C0, p->Cout, p->R, p->C0, rows_d, a.Kpad, 1);
   tb.n = 0;
   size_t top = 0;
   if (!a.ncls) {
@@ -524,26 +479,24 @@ static size_t conv_ex_parity_packs(const flair_conv_ex_t* p, ConvArgs& a, unsign
 
 size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p) {
   ConvArgs a;
-  int Cin, rows_f;
   float standin;
-  if (!p || conv_ex_fill(p, a, Cin, rows_f)) return 0;
+  if (!p || conv_ex_fill(p, a)) return 0;
   conv_ex_sizing(p, a, &standin);
   if (p->mode == 2) {
     PackTable tb;
     return conv_ex_parity_packs(p, a, nullptr, tb) + 256;
   }
   a.stats = p->stats;
-  size_t b = (size_t)round_up((long)((size_t)rows_f * a.Kpad * dtype_size(p->dtype)), 256);
+  size_t b = (size_t)round_up((long)((size_t)conv_weight_rows_pad(p->Cout) * a.Kpad * dtype_size(p->dtype)), 256);
   if (p->stats) b += (size_t)round_up((long)conv_grid_rows(p->dtype, a) * 2 * p->Cout * 4, 256);
   return b + 256;
 }
 
 int flair_conv2d_ex_grid_rows(const flair_conv_ex_t* p) {
   ConvArgs a;
-  int Cin, rows_f;
   float standin;
   if (!p) return -1;
-  const int rc = conv_ex_fill(p, a, Cin, rows_f);
+  const int rc = conv_ex_fill(p, a);
   if (rc) return rc;
   conv_ex_sizing(p, a, &standin);
   a.stats = p->stats;
@@ -554,8 +507,7 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
   if (!p || !p->x0 || !p->w_oihw || !workspace) return -1;
   hipStream_t s = (hipStream_t)stream;
   ConvArgs a;
-  int Cin, rows_f;
-  int rc = conv_ex_fill(p, a, Cin, rows_f);
+  int rc = conv_ex_fill(p, a);
   if (rc) return rc;
   if (p->mode == 2) {
     if (!p->y_nhwc) return -1;
@@ -567,6 +519,7 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
   // the epilogue reads bnr_y, bnr_scale and bnr_shift unconditionally, and a reduction without a partial has nowhere to go
   if (p->bnr_partial ? (!p->bnr_y || !p->bnr_scale || !p->bnr_shift) : (p->bnr_y != nullptr)) return -1;
   OpArena ar(workspace, wsb);
+  const int Cin = a.C0 + a.C1, rows_f = conv_weight_rows_pad(p->Cout);
   void* wp = ar.get((size_t)rows_f * a.Kpad * dtype_size(p->dtype));
   a.w = wp;
   // the partial is the caller's, one row per row block of the launch
@@ -592,13 +545,9 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
 
 static int wgrad_ex_fill(const flair_wgrad_ex_t* p, WgradArgs& w) {
   if (p->dtype != DT_F32 && p->dtype != DT_BF16) return -2;
-  memset(&w, 0, sizeof(w));
-  w.x0 = p->x0; w.x1 = p->x1; w.C0 = p->C0; w.C1 = p->x1 ? p->C1 : 0; w.up0 = p->up0; w.N = p->N;
-  w.Hin = p->up0 ? 2 * p->H : p->H; w.Win = p->up0 ? 2 * p->W : p->W;
-  w.Hout = (w.Hin + 2 * p->pad - p->R) / p->stride + 1; w.Wout = (w.Win + 2 * p->pad - p->R) / p->stride + 1;
-  w.R = p->R; w.S = p->R; w.stride = p->stride; w.pad = p->pad;
-  w.dy = p->dy; w.dy_ld = p->dy_ld > 0 ? p->dy_ld : p->Cout; w.Cout = p->Cout; w.dw = p->dw;
-  w.Cin_real = p->Cin_real > 0 ? p->Cin_real : w.C0 + w.C1;
+  const ConvInput in{p->x0, p->x1, p->C0, p->x1 ? p->C1 : 0, p->up0, p->N, p->H, p->W};
+  wgrad_args(w, in, p->R, p->stride, p->pad, p->dy, p->dy_ld > 0 ? p->dy_ld : p->Cout, p->Cout, p->dw,
+             p->Cin_real > 0 ? p->Cin_real : in.C0 + in.C1);
   w.accumulate = p->accumulate; w.in_scale = p->in_scale; w.in_shift = p->in_shift; w.cus = p->cus; w.dbias = p->dbias;
   w.fuse_y = p->fuse_y; w.fuse_coef = p->fuse_coef; w.fuse_msc = p->fuse_msc; w.fuse_msh = p->fuse_msh;
   return 0;

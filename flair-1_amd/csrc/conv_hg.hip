@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "tile_store.h"
 #include "tune.h"
@@ -832,8 +833,6 @@ int set_debug_buffer(void* p) {
   return -7;   // not a diagnostic build
 #endif
 }
-
-bool conv_acc_src_ok(int dtype, const ConvArgs& a) { return a.acc_src && a.accumulate && a.pool_c0 == 0 && conv_hg_applicable(dtype, a); }
 
 int launch_conv_hg(int dtype, const ConvArgs& a, hipStream_t s) {
   const int tp = hg_tile_pixels(dtype, a);

@@ -10,6 +10,7 @@
 // Epilogue: accumulators -> LDS -> 16-byte coalesced NHWC stores (or fp32 NCHW for the head),
 // plus per-row-block partial BatchNorm sums (deterministic: no atomics).
 #include "common.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "tune.h"
 
@@ -342,44 +343,39 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
 static inline int pick_bn(int cout) { return cout >= 128 ? 128 : cout >= 64 ? 64 : cout >= 32 ? 32 : 16; }
 static inline int pick_bm(int cout) { return cout >= 64 ? 128 : 256; }
 
-bool conv_halo_applicable(const ConvArgs& a);           // conv_halo.hip
-int conv_halo_grid_rows(int dtype, const ConvArgs& a);
-int launch_conv_halo(int dtype, const ConvArgs& a, hipStream_t s);
-bool conv_halo_bnr_applicable(const ConvArgs& a);
-bool conv_stem_applicable(int dtype, const ConvArgs& a);  // stem.hip
-int conv_stem_grid_rows(const ConvArgs& a);
-int launch_conv_stem(const ConvArgs& a, hipStream_t s);
-bool conv_hg_applicable(int dtype, const ConvArgs& a);  // conv_hg.hip
-int conv_hg_grid_rows(int dtype, const ConvArgs& a);
-int launch_conv_hg(int dtype, const ConvArgs& a, hipStream_t s);
+ConvFamily conv_family(int dtype, const ConvArgs& a) {
+  if (conv_stem_applicable(dtype, a)) return CONV_STEM;   // 7x7 stride-2 stem
+  if (conv_hg_applicable(dtype, a)) return CONV_HG;       // MFMA-bound 3x3 s1 layers: halo GEMM
+  if (conv_halo_applicable(a)) return CONV_HALO;          // HBM-bound small-channel 3x3 layers: halo-tile direct kernel
+  return CONV_GATHER;
+}
 
-// true when launch_conv will pick a halo-tile kernel whose epilogue implements pool_c0 / out_skip
-bool conv_tile_epilogue_ok(int dtype, const ConvArgs& a) {
+static bool tile_epilogue_ok(ConvFamily f, const ConvArgs& a) {
   if ((a.Hout & 1) || (a.Wout & 1)) return false;
-  if (conv_hg_applicable(dtype, a)) return a.pool_c0 % ((a.Cout % 128) == 0 ? 128 : 64) == 0;
-  if (conv_halo_applicable(a)) return a.pool_c0 % (a.Cout <= 16 ? 16 : 32) == 0 && !a.out_nchw;
+  if (f == CONV_HG) return a.pool_c0 % ((a.Cout % 128) == 0 ? 128 : 64) == 0;
+  if (f == CONV_HALO) return a.pool_c0 % (a.Cout <= 16 ? 16 : 32) == 0 && !a.out_nchw;
   return false;
 }
 
+bool conv_tile_epilogue_ok(int dtype, const ConvArgs& a) { return tile_epilogue_ok(conv_family(dtype, a), a); }
+
 bool conv_mfma_bound(int dtype, const ConvArgs& a) {
-  static int mode = -1;  // tuning override FLAIR_BNR: 0 = never fuse, 1 = 128-wide halo-GEMM only, 2 = every halo-GEMM
-  if (mode < 0) {
-    const char* e = getenv("FLAIR_BNR");
-    mode = e ? atoi(e) : 2;
-  }
+  const int mode = tune("FLAIR_BNR", 2);   // 0 = never fuse, 1 = 128-wide halo-GEMM only, 2 = every halo-GEMM
   if (mode == 0) return false;
-  if (!conv_hg_applicable(dtype, a)) return conv_halo_bnr_applicable(a);   // (not MFMA-bound: the persistent small-channel kernel
-                                                                           // saves the reduce pass's read of the gradient)
+  if (conv_family(dtype, a) != CONV_HG) return conv_halo_bnr_applicable(a);   // (not MFMA-bound: the persistent small-channel kernel
+                                                                              // saves the reduce pass's read of the gradient)
   return mode == 2 || (a.Cout % 128) == 0;
 }
 
+bool conv_acc_src_ok(int dtype, const ConvArgs& a) { return a.acc_src && a.accumulate && a.pool_c0 == 0 && conv_family(dtype, a) == CONV_HG; }
+
 int conv_grid_rows(int dtype, const ConvArgs& a) {
-  if (a.in_scale && conv_hg_applicable(dtype, a)) return conv_hg_grid_rows(dtype, a);
-  if (a.in_scale && conv_halo_applicable(a)) return conv_halo_grid_rows(dtype, a);
-  if (conv_stem_applicable(dtype, a)) return conv_stem_grid_rows(a);
-  if (conv_hg_applicable(dtype, a)) return conv_hg_grid_rows(dtype, a);
-  if (conv_halo_applicable(a)) return conv_halo_grid_rows(dtype, a);
-  return cdiv((long)a.N * a.Hout * a.Wout, pick_bm(a.Cout));
+  switch (conv_family(dtype, a)) {
+    case CONV_STEM: return conv_stem_grid_rows(a);
+    case CONV_HG: return conv_hg_grid_rows(dtype, a);
+    case CONV_HALO: return conv_halo_grid_rows(dtype, a);
+    default: return cdiv((long)a.N * a.Hout * a.Wout, pick_bm(a.Cout));
+  }
 }
 
 int conv_weight_rows_pad(int cout) { return (int)round_up(cout, pick_bn(cout)); }
@@ -415,38 +411,33 @@ static int launch_t(const ConvArgs& a, hipStream_t s) {
 }
 
 int launch_conv(int dtype, const ConvArgs& a, hipStream_t s) {
+  const ConvFamily f = conv_family(dtype, a);
   if (a.preds_u8 && !conv_halo_preds_ok(dtype, a)) return -6;   // fused argmax: persistent small-channel kernel only
   if (a.ce_lab8 && !conv_halo_ce_ok(dtype, a)) return -6;       // fused per-pixel head: its CE flavour only
-  if (a.out_sub && (a.out_nchw || a.stats || a.pool_c0 > 0 || a.bnr_partial || conv_hg_applicable(dtype, a) || conv_halo_applicable(a)))
-    return -6;  // sub-sampled stores exist in the gather-form epilogue only
+  // sub-sampled stores and the GELU epilogue exist in the gather-form kernel only
+  if (a.out_sub && (a.out_nchw || a.stats || a.pool_c0 > 0 || a.bnr_partial || f != CONV_GATHER)) return -6;
   // input / epilogue options only the halo-GEMM kernels implement (fused BN-backward apply, addend from another tensor, masked store)
-  if ((a.acc_src || a.bnr_mask) && !conv_hg_applicable(dtype, a)) return -6;
-  if (a.acc_src && !conv_acc_src_ok(dtype, a)) return -6;
+  if ((a.acc_src || a.bnr_mask) && f != CONV_HG) return -6;
+  if (a.acc_src && !(a.accumulate && a.pool_c0 == 0)) return -6;   // (conv_acc_src_ok)
   if (a.bnr_mask && !a.bnr_partial) return -6;
-  // the GELU epilogue exists in the gather-form kernel only
-  if (a.ogelu && (!a.out || a.out_nchw || a.in_scale || conv_stem_applicable(dtype, a) || conv_hg_applicable(dtype, a) || conv_halo_applicable(a)))
-    return -6;
-  if (a.in_scale) {   // lazy BN + ReLU on the input: the halo-GEMM (>= 64 channels) and the small-channel halo kernel apply it
-    if (conv_hg_applicable(dtype, a)) return (a.pool_c0 > 0 || a.bnr_partial) ? -6 : launch_conv_hg(dtype, a, s);
-    if (!conv_halo_applicable(a) || (a.pool_c0 > 0 && !conv_tile_epilogue_ok(dtype, a))) return -6;
-    const int ch = dtype == DT_F32 ? 4 : 8;
-    // the tile epilogue stores whole 16-byte chunks: a ragged channel count needs the row padded to the next chunk
-    // (the padded columns receive the zero-weight rows' results)
-    if (a.out && (a.Cout % ch) && a.out_ld < (int)round_up(a.Cout, ch)) return -3;
-    return launch_conv_halo(dtype, a, s);
+  if (a.ogelu && (!a.out || a.out_nchw || a.in_scale || f != CONV_GATHER)) return -6;
+  // lazy BN + ReLU on the input: the halo-GEMM (>= 64 channels, no data-gradient epilogue) and the small-channel halo kernel apply it
+  if (a.in_scale && ((f != CONV_HG && f != CONV_HALO) || (f == CONV_HG && (a.pool_c0 > 0 || a.bnr_partial)))) return -6;
+  const bool tile_ok = tile_epilogue_ok(f, a);
+  if (a.pool_c0 > 0 && !tile_ok) return -6;
+  if (a.bnr_partial && !a.in_scale && !(tile_ok && (f == CONV_HG || conv_halo_bnr_applicable(a)))) return -6;
+  switch (f) {
+    case CONV_STEM: return launch_conv_stem(a, s);
+    case CONV_HG: return launch_conv_hg(dtype, a, s);
+    case CONV_HALO: {
+      const int ch = dtype == DT_F32 ? 4 : 8;
+      // the tile epilogue stores whole 16-byte chunks: a ragged channel count needs the row padded to the next chunk
+      // (the padded columns receive the zero-weight rows' results)
+      if (a.out && (a.Cout % ch) && a.out_ld < (int)round_up(a.Cout, ch)) return -3;
+      return launch_conv_halo(dtype, a, s);
+    }
+    default: return dtype == DT_F32 ? launch_t<float>(a, s) : launch_t<bf16_t>(a, s);
   }
-  if (a.pool_c0 > 0 && !conv_tile_epilogue_ok(dtype, a)) return -6;
-  if (a.bnr_partial && !(conv_tile_epilogue_ok(dtype, a) && (conv_hg_applicable(dtype, a) || conv_halo_bnr_applicable(a)))) return -6;
-  if (conv_stem_applicable(dtype, a)) return launch_conv_stem(a, s);     // 7x7 stride-2 stem
-  if (conv_hg_applicable(dtype, a)) return launch_conv_hg(dtype, a, s);  // MFMA-bound 3x3 s1 layers: halo GEMM
-  if (conv_halo_applicable(a)) {  // HBM-bound small-channel 3x3 layers: halo-tile direct kernel
-    const int ch = dtype == DT_F32 ? 4 : 8;
-    // the tile epilogue stores whole 16-byte chunks: a ragged channel count needs the row padded to the next chunk
-    // (the padded columns receive the zero-weight rows' results)
-    if (a.out && (a.Cout % ch) && a.out_ld < (int)round_up(a.Cout, ch)) return -3;
-    return launch_conv_halo(dtype, a, s);
-  }
-  return dtype == DT_F32 ? launch_t<float>(a, s) : launch_t<bf16_t>(a, s);
 }
 
 }  // namespace flair

@@ -1,6 +1,7 @@
 // Host-callable launchers of the elementwise / reduction kernels (bn.hip, misc.hip, ce_head.hip).
 #pragma once
 #include "common.h"
+#include "conv_route.h"
 
 namespace flair {
 
@@ -46,13 +47,19 @@ struct PackDesc {
   // full R x S pack (Rc = 0: all taps).  Used by the parity classes of a stride-2 data gradient.
   unsigned char r0, rstep, Rc, s0, sstep, Sc, pad_[2];
 };
+// full R x R pack of one layer: tf = 0 the forward [Cout][(r,s),Cin_p] copy, tf = 1 the flipped / transposed data-gradient copy
+inline PackDesc pack_desc(long w_off, size_t dst_off, int Cout, int Cin, int R, int Cin_p, int rows_pad, int Kpad, int tf) {
+  PackDesc d = {};
+  d.w_off = w_off; d.dst_off = dst_off; d.Cout = Cout; d.Cin = Cin; d.R = R; d.S = R;
+  d.Cin_p = Cin_p; d.rows_pad = rows_pad; d.Kpad = Kpad; d.tf = tf;
+  return d;
+}
 struct PackTable {
   static constexpr int MAX = 64;
   int n;
   PackDesc d[MAX];
 };
 int pack_weights_all(int dtype, const float* params, void* base, const PackTable& tb, hipStream_t s);
-int conv_weight_rows_pad(int cout);   // conv_igemm.hip: rows of a packed weight (Cout up to whole column tiles)
 int sgd_step(float* params, const float* grads, long n, float lr, hipStream_t s);
 int add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, hipStream_t s);
 int ew_add(int dtype, void* dst, const void* src, long n, hipStream_t s);

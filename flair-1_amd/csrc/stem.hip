@@ -9,6 +9,7 @@
 // X and dY cross HBM exactly once.  One fp32 slab per workgroup, summed in a fixed order by wgrad_reduce_kernel.
 // bf16 only; fp32 (the parity mode) stays on the generic kernel.
 #include "common.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "tune.h"
 

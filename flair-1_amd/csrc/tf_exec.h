@@ -19,7 +19,7 @@ struct SfTensor {
 struct SfLin {   // Linear (k = 1) or Conv2d(k, stride, pad) as an implicit GEMM
   int cin, cout, k, stride, pad, cin_p;
   long w_off, b_off;
-  int Kg, Kpad, rows;
+  int Kpad, rows;
   size_t packed = 0;
 };
 struct SfNorm { int C; long g_off, b_off; };

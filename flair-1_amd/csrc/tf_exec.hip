@@ -1,8 +1,7 @@
 // Host-side core of the transformer inference executors (see tf_exec.h).  No kernels here: every launch goes to misc.hip
 // (weight packing) or conv_igemm.hip (the products).
 #include "tf_exec.h"
-
-#include <string.h>
+#include "conv_args.h"
 
 namespace flair {
 
@@ -22,8 +21,7 @@ SfLin TfExec::make_lin(int cin, int cout, int k, int stride, int pad) const {
   L.cin = cin; L.cout = cout; L.k = k; L.stride = stride; L.pad = pad;
   L.cin_p = (int)round_up(cin, 8);
   L.w_off = -1; L.b_off = -1;
-  L.Kg = k * k * L.cin_p;
-  L.Kpad = (int)round_up(L.Kg, dtype == DT_F32 ? 32 : 64);   // whole K steps of the kernel
+  L.Kpad = conv_kpad(dtype, k * k * L.cin_p);   // whole K steps of the kernel
   L.rows = conv_weight_rows_pad(cout);
   return L;
 }
@@ -79,10 +77,7 @@ void TfExec::pack_lins(bool fresh) {
   if (fresh || dry_) return;
   for (const SfLin& L : lins) {
     if (packs_.n == PackTable::MAX) flush_packs();
-    PackDesc& d = packs_.d[packs_.n++];
-    memset(&d, 0, sizeof(d));
-    d.w_off = L.w_off; d.dst_off = L.packed; d.Cout = L.cout; d.Cin = L.cin; d.R = L.k; d.S = L.k;
-    d.Cin_p = L.cin_p; d.rows_pad = L.rows; d.Kpad = L.Kpad; d.tf = 0;
+    packs_.d[packs_.n++] = pack_desc(L.w_off, L.packed, L.cout, L.cin, L.k, L.cin_p, L.rows, L.Kpad, 0);
   }
   flush_packs();
 }
@@ -94,10 +89,8 @@ size_t TfExec::fuse_rows(const SfLin& G, const SfPart* parts, int n, bool fresh,
   *bias = (float*)alloc((size_t)n * C * 4);
   if (fresh || dry_) return off;
   for (int part = 0; part < n; ++part) {
-    PackDesc& d = packs_.d[packs_.n++];
-    memset(&d, 0, sizeof(d));
-    d.w_off = parts[part].w_off; d.dst_off = off + (size_t)part * C * G.Kpad * es; d.Cout = C; d.Cin = G.cin; d.R = 1; d.S = 1;
-    d.Cin_p = G.cin_p; d.rows_pad = part + 1 < n ? C : G.rows - (n - 1) * C; d.Kpad = G.Kpad; d.tf = 0;   // the last part carries the padding rows
+    packs_.d[packs_.n++] = pack_desc(parts[part].w_off, off + (size_t)part * C * G.Kpad * es, C, G.cin, 1, G.cin_p,
+                                     part + 1 < n ? C : G.rows - (n - 1) * C, G.Kpad, 0);   // the last part carries the padding rows
     if (!err_ && hipMemcpyAsync(*bias + part * C, params_ + parts[part].b_off, (size_t)C * 4, hipMemcpyDeviceToDevice, s_) != hipSuccess)
       err_ = -101;
   }
@@ -108,11 +101,8 @@ size_t TfExec::fuse_rows(const SfLin& G, const SfPart* parts, int n, bool fresh,
 void TfExec::gemm(const SfLin& L, const void* in, int B, int Hin, int Win, void* out, int out_ld, const void* res, const float* oscale,
                   const float* oshift, int relu, float* out_nchw, int gelu, const void* wpacked, const float* bias) {
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src0 = in; a.C0 = L.cin_p; a.N = B; a.Hin = Hin; a.Win = Win;
-  a.Hout = (Hin + 2 * L.pad - L.k) / L.stride + 1; a.Wout = (Win + 2 * L.pad - L.k) / L.stride + 1;
-  a.R = L.k; a.S = L.k; a.out_mul = L.stride; a.pad = L.pad; a.in_div = 1;
-  a.Cout = L.cout; a.Kg = L.Kg; a.Kpad = L.Kpad; a.w = wpacked ? wpacked : base_ + L.packed;
+  conv_fwd_args(a, dtype, ConvInput{in, nullptr, L.cin_p, 0, 0, B, Hin, Win}, L.k, L.stride, L.pad, L.cout);
+  a.w = wpacked ? wpacked : base_ + L.packed;
   a.bias = bias ? bias : L.b_off >= 0 ? params_ + L.b_off : nullptr;
   a.out = out; a.out_ld = out_ld; a.out_nchw = out_nchw;
   a.ores = res; a.oscale = oscale; a.oshift = oshift; a.orelu = relu; a.ogelu = gelu;

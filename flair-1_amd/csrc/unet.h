@@ -29,12 +29,12 @@ struct ConvDesc {
   long w_off = -1, b_off = -1;  // float offsets in the flat parameter buffer
   // packed copies (byte offsets into the workspace weight arena)
   size_t wf = 0, wd = 0;
-  int Kg, Kpad, rows_f;   // forward pack
-  int Kgd, Kpad_d, rows_d;  // data-gradient pack (rows = Cin_p, K = R*S*Cout_p)
+  int Kpad, rows_f;       // forward pack (K = R*S*Cin_p, padded to whole K steps)
+  int Kpad_d, rows_d;     // data-gradient pack (rows = Cin_p, K = R*S*Cout_p)
   // 3x3 stride-2 layers: the data gradient splits by output parity (py, px) into four stride-1 convolutions over dY
   // with 1, 2, 2 and 4 of the nine taps (class = 2*py + px) — a quarter of the gather-form kernel's MFMA work
   size_t wd_cls[4] = {0, 0, 0, 0};
-  int Kg_cls[4] = {0, 0, 0, 0}, Kpad_cls[4] = {0, 0, 0, 0};
+  int Kpad_cls[4] = {0, 0, 0, 0};
   bool parity_dgrad() const { return stride == 2 && R == 3 && S == 3 && pad == 1; }
 };
 
@@ -167,8 +167,8 @@ class UNet {
   float* maxprob_req_ = nullptr;
   CeReq ce_req_;
   bool side_init();
-  hipStream_t wgrad_stream();
-  int side_cus(int unit) const;   // forks the side stream behind everything queued on s_ so far
+  hipStream_t wgrad_stream();     // forks the side stream behind everything queued on s_ so far
+  int side_cus() const;           // WgradArgs::cus of a launch on the side stream
   void side_join();
  public:
   ~UNet();

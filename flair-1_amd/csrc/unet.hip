@@ -4,15 +4,12 @@
 #include <stdlib.h>
 
 #include "unet.h"
+#include "conv_args.h"
+#include "conv_route.h"
 #include "parity_pack.h"
 #include "tune.h"
 
-#include <string.h>
-
 namespace flair {
-
-int conv_weight_rows_pad(int cout);  // conv_igemm.hip
-bool conv_tile_epilogue_ok(int dtype, const ConvArgs& a);
 
 #define RUN(expr)                         \
   do {                                    \
@@ -46,12 +43,9 @@ int UNet::add_conv(const std::string& name, int cin, int cout, int k, int stride
     tensors.push_back(b);
     n_params += cout;
   }
-  const int kstep = dtype == DT_F32 ? 32 : 64;
-  c.Kg = k * k * c.Cin_p;
-  c.Kpad = (int)round_up(c.Kg, kstep);
+  c.Kpad = conv_kpad(dtype, k * k * c.Cin_p);
   c.rows_f = conv_weight_rows_pad(cout);
-  c.Kgd = k * k * c.Cout_p;
-  c.Kpad_d = (int)round_up(c.Kgd, kstep);
+  c.Kpad_d = conv_kpad(dtype, k * k * c.Cout_p);
   c.rows_d = conv_weight_rows_pad(c.Cin_p);
   convs.push_back(c);
   return (int)convs.size() - 1;
@@ -163,7 +157,7 @@ bool UNet::side_init() {
 // round-2 trace) — and half the workgroups means half the fp32 slabs (75 -> 37 MB written and re-read per launch).
 // Step 13.2 -> 12.4 ms (192 CUs: 12.55, 144: 12.48, 112: 12.56, 96: 12.87; giving the last units of backward, when the
 // caller's stream runs dry, the whole chip again: +0.05 ... +0.3 ms).
-int UNet::side_cus(int) const {
+int UNet::side_cus() const {
   if (!tune("FLAIR_WGRAD_STREAM", 1)) return 0;
   // fp32 mode: everything is matrix-pipe-bound there (fp32 MFMA is 16x slower), the BatchNorm kernels are a small share and
   // halving the weight-gradient kernels' CUs costs more than it frees: 57.4 ms with the whole chip, 58.4 with 192, 62.2 with 128
@@ -219,8 +213,8 @@ void UNet::begin(void* ws, size_t ws_bytes, hipStream_t s, bool dry) {
   }
   for (auto& c : convs) {
     if (!c.parity_dgrad()) continue;
-    for (int cls = 0; cls < 4; ++cls) {
-      parity_class_geom(dtype, c.Cout_p, cls, c.Kg_cls[cls], c.Kpad_cls[cls]);
+    for (int cls = 0, kg; cls < 4; ++cls) {
+      parity_class_geom(dtype, c.Cout_p, cls, kg, c.Kpad_cls[cls]);
       c.wd_cls[cls] = top_; alloc((size_t)c.rows_d * c.Kpad_cls[cls] * dtype_size(dtype));
     }
   }
@@ -230,12 +224,7 @@ void UNet::begin(void* ws, size_t ws_bytes, hipStream_t s, bool dry) {
 void UNet::pack_forward_weights() {
   PackTable tb;
   tb.n = 0;
-  for (auto& c : convs) {
-    PackDesc& d = tb.d[tb.n++];
-    d.w_off = c.w_off; d.dst_off = c.wf; d.Cout = c.Cout; d.Cin = c.Cin; d.R = c.R; d.S = c.S;
-    d.Cin_p = c.Cin_p; d.rows_pad = c.rows_f; d.Kpad = c.Kpad; d.tf = 0;
-    d.Rc = 0; d.r0 = d.rstep = d.s0 = d.sstep = d.Sc = 0;
-  }
+  for (auto& c : convs) tb.d[tb.n++] = pack_desc(c.w_off, c.wf, c.Cout, c.Cin, c.R, c.Cin_p, c.rows_f, c.Kpad, 0);
   RUN(pack_weights_all(dtype, params_, base_, tb, s_));
 }
 
@@ -246,12 +235,8 @@ void UNet::pack_dgrad_weights() {
   tb.n = 0;
   for (size_t i = 1; i < convs.size(); ++i) {  // the stem needs no data gradient
     auto& c = convs[i];
-    PackDesc& d = tb.d[tb.n++];
-    d.w_off = c.w_off; d.dst_off = c.wd; d.Cout = c.Cout; d.Cin = c.Cin; d.R = c.R; d.S = c.S;
-    d.Cin_p = c.Cout_p; d.rows_pad = c.rows_d; d.Kpad = c.Kpad_d; d.tf = 1;
-    d.Rc = 0; d.r0 = d.rstep = d.s0 = d.sstep = d.Sc = 0;
+    const PackDesc full = tb.d[tb.n++] = pack_desc(c.w_off, c.wd, c.Cout, c.Cin, c.R, c.Cout_p, c.rows_d, c.Kpad_d, 1);
     if (c.parity_dgrad()) {
-      const PackDesc full = d;
       for (int cls = 0; cls < 4; ++cls) tb.d[tb.n++] = parity_class_pack(full, cls, c.wd_cls[cls], c.Kpad_cls[cls]);
     }
   }
@@ -277,27 +262,17 @@ void* UNet::grad_peek(const Act& a) {
 }
 
 // ------------------------------------------------------------------------------------------ forward
-static void fill_conv_args(ConvArgs& a, const ConvDesc& c, const Act& in0, const Act& in1, bool up0, const Act& y,
-                           const void* wpacked) {
-  memset(&a, 0, sizeof(a));
-  a.src0 = in0.p; a.src1 = in1.p;
-  a.C0 = in0.C; a.C1 = in1.p ? in1.C : 0;
-  a.up0 = up0 ? 1 : 0;
-  a.N = in0.N;
-  a.Hin = up0 ? in0.H * 2 : in0.H;
-  a.Win = up0 ? in0.W * 2 : in0.W;
-  a.Hout = y.H; a.Wout = y.W;
-  a.R = c.R; a.S = c.S;
-  a.out_mul = c.stride; a.pad = c.pad; a.in_div = 1;
-  a.Cout = c.Cout;
-  a.Kg = c.Kg; a.Kpad = c.Kpad;
-  a.w = wpacked;
-  a.out = y.p; a.out_ld = y.C;
-  a.in_scale = in0.lz_scale; a.in_shift = in0.lz_shift;   // lazy producers never feed a concat partner (in1)
+static ConvInput conv_input(const Act& in0, const Act& in1, bool up0) {
+  return ConvInput{in0.p, in1.p, in0.C, in1.p ? in1.C : 0, up0 ? 1 : 0, in0.N, in0.H, in0.W};
 }
 
-bool wgrad_big_applicable(int dtype, const WgradArgs& a);   // wgrad_hg.hip
-bool conv_hg_applicable(int dtype, const ConvArgs& a);      // conv_hg.hip
+// forward launch of layer `c` over [up2(in0) if up0] ++ in1 into the tensor at `y` with rows of c.Cout_p stored channels
+static void fill_conv_args(ConvArgs& a, int dtype, const ConvDesc& c, const Act& in0, const Act& in1, bool up0, void* y, const void* wpacked) {
+  conv_fwd_args(a, dtype, conv_input(in0, in1, up0), c.R, c.stride, c.pad, c.Cout);
+  a.w = wpacked;
+  a.out = y; a.out_ld = c.Cout_p;
+  a.in_scale = in0.lz_scale; a.in_shift = in0.lz_shift;   // lazy producers never feed a concat partner (in1)
+}
 
 // Can the unit producing `y` (conv + BN + ReLU, no residual) hand its PRE-BatchNorm tensor to its single consumer, the
 // 3x3 convolution `cons` (input = [up2(y) if up0] ++ skip), which then applies BN + ReLU while it stages its halo — in
@@ -306,18 +281,14 @@ bool UNet::lazy_into_hg(const Act& y, int cons, bool up0, const Act& skip) const
   if (!training_ || !tune("FLAIR_LAZY_HG", 1)) return false;
   const ConvDesc& c = convs[cons];
   if (c.R != 3 || c.stride != 1) return false;
-  Act in0 = y, out;
-  in0.p = reinterpret_cast<void*>(16);
-  out.N = y.N; out.H = up0 ? 2 * y.H : y.H; out.W = up0 ? 2 * y.W : y.W; out.C = c.Cout_p; out.p = reinterpret_cast<void*>(16);
+  Act in0 = y;
+  in0.p = reinterpret_cast<void*>(16);   // (the predicates only look at which pointers are set)
   ConvArgs a;
-  fill_conv_args(a, c, in0, skip, up0, out, reinterpret_cast<void*>(16));
+  fill_conv_args(a, dtype, c, in0, skip, up0, in0.p, in0.p);
   a.in_scale = a.in_shift = reinterpret_cast<const float*>(16);
   if (!conv_hg_applicable(dtype, a)) return false;
   WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  w.x0 = in0.p; w.x1 = skip.p; w.C0 = in0.C; w.C1 = skip.p ? skip.C : 0; w.up0 = up0 ? 1 : 0;
-  w.N = y.N; w.Hin = out.H; w.Win = out.W; w.Hout = out.H; w.Wout = out.W; w.R = 3; w.S = 3; w.stride = 1; w.pad = 1;
-  w.dy = in0.p; w.dy_ld = c.Cout_p; w.Cout = c.Cout; w.Cin_real = c.Cin;
+  wgrad_args(w, conv_input(in0, skip, up0), c.R, c.stride, c.pad, in0.p, c.Cout_p, c.Cout, nullptr, c.Cin);
   w.in_scale = w.in_shift = reinterpret_cast<const float*>(16);
   return wgrad_big_applicable(dtype, w);
 }
@@ -328,12 +299,12 @@ int UNet::run_unit(int ci, int bi, const Act& in0, const Act& in1, bool up0, boo
   const BnDesc& b = bns[bi];
   Unit u;
   u.conv = ci; u.bn = bi; u.in0 = in0; u.in1 = in1; u.up0 = up0; u.relu = relu; u.res_unit = res_unit; u.res = res;
-  const int Hin = up0 ? in0.H * 2 : in0.H, Win = up0 ? in0.W * 2 : in0.W;
-  const int Ho = (Hin + 2 * c.pad - c.R) / c.stride + 1, Wo = (Win + 2 * c.pad - c.S) / c.stride + 1;
+  const int Ho = conv_out_extent(up0 ? in0.H * 2 : in0.H, c.R, c.stride, c.pad);
+  const int Wo = conv_out_extent(up0 ? in0.W * 2 : in0.W, c.S, c.stride, c.pad);
   u.y = alloc_act(in0.N, Ho, Wo, c.Cout_p);
   u.scale = alloc_f(b.C); u.shift = alloc_f(b.C); u.mean = alloc_f(b.C); u.invstd = alloc_f(b.C);
   ConvArgs a;
-  fill_conv_args(a, c, in0, in1, up0, u.y, base_ + c.wf);
+  fill_conv_args(a, dtype, c, in0, in1, up0, u.y.p, base_ + c.wf);
   if (!training_) {
     // inference: BatchNorm (running statistics) is a per-channel affine -> folded, together with the residual
     // add and the ReLU, into the conv epilogue; the pre-BN tensor is never written
@@ -348,20 +319,16 @@ int UNet::run_unit(int ci, int bi, const Act& in0, const Act& in1, bool up0, boo
     return (int)units_.size() - 1;
   }
   const int nblk = conv_grid_rows(dtype, a);
-  float* partial = training_ ? alloc_f((long)nblk * 2 * b.C) : nullptr;
+  float* partial = alloc_f((long)nblk * 2 * b.C);
   a.stats = partial;
   RUN(launch_conv(dtype, a, s_));
-  if (training_)
-    RUN(bn_finalize(partial, nblk, b.C, u.y.rows(), params_ + b.g_off, params_ + b.b_off, buffers_ + b.rm_off,
-                    buffers_ + b.rv_off, 0.1f, 1e-5f, u.scale, u.shift, u.mean, u.invstd, s_));
-  else
-    RUN(bn_eval_coeffs(b.C, params_ + b.g_off, params_ + b.b_off, buffers_ + b.rm_off, buffers_ + b.rv_off, 1e-5f,
-                       u.scale, u.shift, s_));
+  RUN(bn_finalize(partial, nblk, b.C, u.y.rows(), params_ + b.g_off, params_ + b.b_off, buffers_ + b.rm_off,
+                  buffers_ + b.rv_off, 0.1f, 1e-5f, u.scale, u.shift, u.mean, u.invstd, s_));
   // The 16-channel decoder units (block 4: 45 % of all BN-apply bytes) feed only small-channel halo kernels,
   // which can apply BN + ReLU while staging their input: skip the activation pass and hand out the pre-BN tensor.
   // The >= 64-channel units whose single consumer is a halo-GEMM convolution do the same (conv1 of every BasicBlock,
   // decoder conv1 / conv2 of the wide blocks): bn_act and the normalised activation tensor vanish for them.
-  const bool plain = lazy_ok_ && training_ && materialize && relu && res_unit < 0 && !res.p;
+  const bool plain = lazy_ok_ && materialize && relu && res_unit < 0 && !res.p;
   bool lazy = plain && c.R == 3 && c.stride == 1 && c.Cout_p <= lazy_max_c_ && (Ho % 8) == 0 && (Wo % 32) == 0;
   if (!lazy && plain && lazy_cons >= 0) {
     Act none_;
@@ -437,10 +404,9 @@ void UNet::decoder_fwd_impl() {
 
 void UNet::head_fwd_impl(float* logits_nchw) {
   const ConvDesc& c = convs.back();
-  Act none, y;
-  y.N = dec_out_.N; y.H = dec_out_.H; y.W = dec_out_.W; y.C = c.Cout_p; y.p = nullptr;
+  Act none;
   ConvArgs a;
-  fill_conv_args(a, c, dec_out_, none, false, y, base_ + c.wf);
+  fill_conv_args(a, dtype, c, dec_out_, none, false, nullptr, base_ + c.wf);
   if (logits_nchw || dry_) {
     a.out = nullptr;
     a.out_nchw = logits_nchw;
@@ -620,7 +586,7 @@ int UNet::residual_producer(const Act& a) const {
 }
 
 void UNet::attach_bn_reduce(ConvArgs& a, const Act& target) {
-  static const int mode = tune("FLAIR_BNR_RES", 1);   // 0: never fuse the reduction of residual units
+  const int mode = tune("FLAIR_BNR_RES", 1);   // 0: never fuse the reduction of residual units
   int p = sole_producer(target);
   bool from_out = false;
   if (p < 0 && a.accumulate && mode) { p = residual_producer(target); from_out = p >= 0; }
@@ -641,7 +607,7 @@ void UNet::attach_bn_reduce(ConvArgs& a, const Act& target) {
   u.bnr_nblk = nblk;
   // the halo-GEMM epilogue has the ReLU mask in hand: it stores dz = gradient * mask, and the unit's own backward needs no mask
   // source, no copy for the identity branch and no separate BatchNorm-backward apply pass (unit_backward)
-  if (bwd_fuse() && conv_hg_applicable(dtype, a)) { a.bnr_mask = 1; u.bnr_masked = true; }
+  if (bwd_fuse() && conv_family(dtype, a) == CONV_HG) { a.bnr_mask = 1; u.bnr_masked = true; }
 }
 
 bool UNet::bwd_fuse() const { return tune("FLAIR_BWD_FUSE", 1) != 0; }
@@ -673,11 +639,7 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   const bool mask_from_y = u.relu && u.res_unit < 0 && !u.res.p;
   // weight gradient (described first: a unit without a data gradient may fold the BatchNorm-backward apply into it)
   WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  w.x0 = u.in0.p; w.x1 = u.in1.p; w.C0 = u.in0.C; w.C1 = u.in1.p ? u.in1.C : 0; w.up0 = u.up0 ? 1 : 0;
-  w.N = u.in0.N; w.Hin = u.up0 ? u.in0.H * 2 : u.in0.H; w.Win = u.up0 ? u.in0.W * 2 : u.in0.W;
-  w.Hout = u.y.H; w.Wout = u.y.W; w.R = c.R; w.S = c.S; w.stride = c.stride; w.pad = c.pad;
-  w.dy = dy; w.dy_ld = u.y.C; w.Cout = c.Cout;
+  wgrad_args(w, conv_input(u.in0, u.in1, u.up0), c.R, c.stride, c.pad, dy, u.y.C, c.Cout, grads_ + c.w_off, c.Cin);
   // the stem: dy feeds nothing but the weight gradient, whose kernel stages it chunk by chunk — it applies the affine itself and
   // the tensor is never written (bn_bwd_apply: 804 MB of traffic for a 268 MB operand read once)
   const bool fuse_apply = !need_dgrad && !dres && mask_from_y && wgrad_bnapply_fusable(dtype, w);
@@ -685,17 +647,11 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   // ---- data gradient, described before anything is launched: gather-form conv over dy with the flipped / transposed pack
   enum { DG_NONE, DG_PLAIN, DG_UPCAT_TILE, DG_UPCAT_SPLIT, DG_PARITY } dg = DG_NONE;
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
   void *dx0 = nullptr, *dsk = nullptr, *dcat = nullptr;
   bool acc0 = false, acc1 = false;
   if (need_dgrad) {
     dg = DG_PLAIN;
-    a.src0 = dy; a.C0 = u.y.C; a.C1 = 0; a.up0 = 0;
-    a.N = u.y.N; a.Hin = u.y.H; a.Win = u.y.W;
-    a.Hout = w.Hin; a.Wout = w.Win;
-    a.R = c.R; a.S = c.S; a.out_mul = 1; a.pad = c.R - 1 - c.pad; a.in_div = c.stride;
-    a.Cout = c.Cin_p;
-    a.Kg = c.Kgd; a.Kpad = c.Kpad_d;
+    conv_dgrad_args(a, dtype, ConvInput{dy, nullptr, u.y.C, 0, 0, u.y.N, u.y.H, u.y.W}, c.R, c.stride, c.pad, w.Hin, w.Win, c.Cin_p);
     a.w = base_ + c.wd;
     a.out_ld = c.Cin_p;
     if (upcat) {
@@ -740,13 +696,10 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
         // stride-2 data gradient by output parity class: stride-1 convolutions over dY, stores interleaved into dX.
         // A 1x1 stride-2 layer only reaches the (even, even) pixels; when accumulating, the other classes add nothing.
         dg = DG_PARITY;
-        a.Hout = u.y.H; a.Wout = u.y.W; a.out_mul = 1; a.pad = 0; a.in_div = 1; a.out_sub = 1;
-        if (c.R == 3) {   // the four classes (1, 2, 2 and 4 taps) ride in one launch, class = blockIdx.z
-          a.ncls = 4;
-          a.R = 2; a.S = 2;
-          a.Kg = (c.Kg_cls[0] + c.Kg_cls[1] + c.Kg_cls[2] + c.Kg_cls[3]) / 4;  // mean over the classes (work accounting only)
-          a.Kpad = c.Kpad_cls[3]; a.w = base_ + c.wd_cls[3];
-          for (int cls = 0; cls < 4; ++cls) { a.cls_w[cls] = base_ + c.wd_cls[cls]; a.cls_kpad[cls] = c.Kpad_cls[cls]; }
+        conv_parity_args(a, dtype, c.R);
+        if (a.ncls) {   // the packs of the four classes (UNet::begin)
+          a.w = base_ + c.wd_cls[3];
+          for (int cls = 0; cls < 4; ++cls) a.cls_w[cls] = base_ + c.wd_cls[cls];
         }
       }
     }
@@ -759,9 +712,8 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
                   dres_acc ? 1 : 0, (mask_from_y && !nomask) ? u.scale : nullptr, (mask_from_y && !nomask) ? u.shift : nullptr,
                   pre_nblk, nomask ? 1 : 0, s_));
   if (fuse_apply) { w.dy = dout; w.fuse_y = u.y.p; w.fuse_coef = coef; w.fuse_msc = u.scale; w.fuse_msh = u.shift; }
-  w.dw = grads_ + c.w_off; w.Cin_real = c.Cin; w.accumulate = 0;
   w.in_scale = u.in0.lz_scale; w.in_shift = u.in0.lz_shift;
-  w.cus = side_cus(ui);
+  w.cus = side_cus();
   w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
   {
     hipStream_t ws = wgrad_stream();   // dy is complete on s_; nothing later on s_ writes what this kernel reads
@@ -780,11 +732,9 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
 
 void UNet::head_bwd_impl(const void* dl) {
   const ConvDesc& c = convs.back();
+  Act none;
   WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  w.x0 = dec_out_.p; w.C0 = dec_out_.C; w.N = dec_out_.N; w.Hin = dec_out_.H; w.Win = dec_out_.W;
-  w.Hout = dec_out_.H; w.Wout = dec_out_.W; w.R = 3; w.S = 3; w.stride = 1; w.pad = 1;
-  w.dy = dl; w.dy_ld = c.Cout_p; w.Cout = c.Cout; w.dw = grads_ + c.w_off; w.Cin_real = c.Cin;
+  wgrad_args(w, conv_input(dec_out_, none, false), c.R, c.stride, c.pad, dl, c.Cout_p, c.Cout, grads_ + c.w_off, c.Cin);
   w.in_scale = dec_out_.lz_scale; w.in_shift = dec_out_.lz_shift;
   w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
   // bias gradient = column sums of dl: inside the weight-gradient kernel where it stages dl anyway, else a pass of its own
@@ -800,10 +750,9 @@ void UNet::head_bwd_impl(const void* dl) {
     RUN(colsum(dtype, dl, rows, c.Cout_p, c.Cout, partial, grads_ + c.b_off, s_));
   }
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src0 = dl; a.C0 = c.Cout_p; a.N = dec_out_.N; a.Hin = dec_out_.H; a.Win = dec_out_.W;
-  a.Hout = dec_out_.H; a.Wout = dec_out_.W; a.R = 3; a.S = 3; a.out_mul = 1; a.pad = 1; a.in_div = 1;
-  a.Cout = c.Cin_p; a.Kg = c.Kgd; a.Kpad = c.Kpad_d; a.w = base_ + c.wd;
+  conv_dgrad_args(a, dtype, ConvInput{dl, nullptr, c.Cout_p, 0, 0, dec_out_.N, dec_out_.H, dec_out_.W}, c.R, c.stride, c.pad, dec_out_.H,
+                  dec_out_.W, c.Cin_p);
+  a.w = base_ + c.wd;
   bool acc = false;
   a.out = grad_of(dec_out_, &acc);
   a.out_ld = c.Cin_p; a.accumulate = acc ? 1 : 0;

@@ -7,6 +7,7 @@
 // slabs are summed in a fixed order by wgrad_reduce_kernel (deterministic, no float atomics),
 // which also permutes [k][(r,s),c] -> PyTorch OIHW.
 #include "common.h"
+#include "conv_route.h"
 #include "prof.h"
 
 namespace flair {
@@ -281,16 +282,6 @@ static void wg_plan(int dtype, const WgradArgs& a, int& bmk, int& bnn, int& spli
   pps = round_up((M + want - 1) / want, 64);
   splits = (int)((M + pps - 1) / pps);
 }
-
-bool wgrad_halo_applicable(const WgradArgs& a);          // wgrad_halo.hip
-size_t wgrad_halo_workspace_bytes(int dtype, const WgradArgs& a);
-int launch_wgrad_halo(int dtype, const WgradArgs& a, hipStream_t s);
-bool wgrad_stem_applicable(int dtype, const WgradArgs& a);  // stem.hip
-size_t wgrad_stem_workspace_bytes(const WgradArgs& a);
-int launch_wgrad_stem(const WgradArgs& a, hipStream_t s);
-bool wgrad_big_applicable(int dtype, const WgradArgs& a);  // wgrad_hg.hip
-size_t wgrad_big_workspace_bytes(int dtype, const WgradArgs& a);
-int launch_wgrad_big(int dtype, const WgradArgs& a, hipStream_t s);
 
 void launch_wgrad_reduce(const float* partial, float* dw, int splits, int Cout, int Cout_pad, int Kpad, int Cin,
                          int Cin_real, int R, int S, int accumulate, hipStream_t s) {

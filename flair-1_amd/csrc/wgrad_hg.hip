@@ -10,6 +10,7 @@
 // groups) x 2 (input-channel halves) so that one A fragment feeds 18 MFMAs.  One fp32 slab per workgroup,
 // summed in a fixed order by wgrad_reduce_kernel.
 #include "common.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "tune.h"
 
