@@ -11,6 +11,8 @@ typedef unsigned short bf16_t;  // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // first-class 16-byte vector (SSA-friendly, unlike HIP's uint4 struct:
+                                                             // keeps staging arrays in registers)
 
 enum { DT_F32 = 0, DT_BF16 = 1 };
 

@@ -5,34 +5,20 @@
 // The implicit-GEMM kernel re-gathers every input pixel 9x through L1/L2, which is what bounds these
 // layers.  Here a workgroup owns an 8x32 output tile, stages its (8+2)x(32+2) input halo ONCE into LDS
 // (16-byte coalesced loads, ~1.3x the algorithmic read), and feeds all 9 taps to the MFMAs from LDS by
-// shifted fragment reads; K is walked tap-major in chunks of CK input channels.  Same operands, epilogue
-// (LDS transpose -> 16-byte NHWC stores / fp32 NCHW logits, BN partial sums) and numerics as conv_igemm.
+// shifted fragment reads; K is walked tap-major in chunks of CK input channels.  Operands and numerics are those of
+// conv_igemm; the halo staging is halo_stage.h (rows of HaloCfg::PSTRIDE bytes per pixel), the epilogues are tile_store.h (LDS
+// transpose -> 16-byte NHWC stores / fp32 NCHW logits, BN partial sums) and tile_direct.h (registers -> HBM).
 #include "common.h"
+#include "halo_stage.h"
+#include "launch.h"
+#include "mma.h"
 #include "ops.h"
-#include "prof.h"
 #include "tile_store.h"
 #include "tile_direct.h"
 #include "tune.h"
 
 namespace flair {
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct HMma;
-template <> struct HMma<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct HMma<float> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-  }
-};
 
 constexpr int TH = 8, TW = 32, HH = TH + 2, HW_ = TW + 2, HPIX = HH * HW_;  // 340 halo pixels
 
@@ -59,6 +45,48 @@ struct HaloCfg {
   static constexpr int WITEMS = (BN * 9 * CPP + 255) / 256;
 };
 
+// ---- what the three kernels below share besides the halo staging
+// zero the padded tail of ROWS weight rows once (K beyond 9*CK contributes nothing)
+template <typename T, int CK, int BN, int ROWS, int NT>
+__device__ __forceinline__ void weights_zero_tail(unsigned char* wl, int t) {
+  using Cfg = HaloCfg<T, CK, BN>;
+  if constexpr (Cfg::KW > 9 * CK) {
+    constexpr int CH = Cfg::CH, PADC = (Cfg::KW - 9 * CK) / CH;
+    for (int it = t; it < ROWS * PADC; it += NT) {
+      const int row = it / PADC, pc = it - row * PADC;
+      *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + (9 * CK + pc * CH) * (int)sizeof(T)) = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+}
+
+// single-chunk layers: all nine taps of ROWS weight rows (the column blocks of a workgroup) to LDS, once per launch
+template <typename T, int CK, int BN, int ROWS, int NT>
+__device__ __forceinline__ void weights_stage(unsigned char* wl, const T* __restrict__ wp, int Kpad, int t) {
+  using Cfg = HaloCfg<T, CK, BN>;
+  constexpr int CH = Cfg::CH, CPP = Cfg::CPP;
+  weights_zero_tail<T, CK, BN, ROWS, NT>(wl, t);
+  for (int it = t; it < ROWS * 9 * CPP; it += NT) {
+    const int row = it / (9 * CPP), rem = it - row * (9 * CPP);
+    const int tap = rem / CPP, ch = rem - tap * CPP;
+    *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + rem * 16) =
+        *reinterpret_cast<const u32x4*>(wp + (long)row * Kpad + tap * CK + ch * CH);
+  }
+}
+
+// one K step of the persistent kernels: the weights are the MFMA's A operand, D = [cout][pixel] (the epilogues of tile_direct.h)
+template <typename T, int TN>
+__device__ __forceinline__ void k_mma(const u32x4 (&af)[4], const u32x4 (&bfr)[TN], f32x4_t (&acc)[4][TN]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int q = 0; q < TN; ++q) Mma<T>::run(bfr[q], af[i], acc[i][q]);
+}
+
+static const char* halo_prof_name(size_t es, int CK) {
+  static const char* names[2][2] = {{"conv3x3_halo_f32_ck16", "conv3x3_halo_f32_ck32"}, {"conv3x3_halo_bf16_ck16", "conv3x3_halo_bf16_ck32"}};
+  return names[es == 2][CK == 32];
+}
+
 // LZ: instantiate the lazy BN + ReLU input transform (ConvArgs::in_scale); kept out of the plain variant
 template <typename T, int CK, int BN, bool LZ>
 __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
@@ -72,9 +100,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
   const int H = a.Hout, W = a.Wout;
   const int tiles_x = W / TW, tiles_y = H / TH;
   const int tile = blockIdx.x;
-  const int n = tile / (tiles_x * tiles_y);
-  const int trem = tile - n * tiles_x * tiles_y;
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  int n, y0, x0;
+  tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
   const int n0 = blockIdx.y * BN;
   const int Cin = a.C0 + a.C1;
   const T* __restrict__ src0 = (const T*)a.src0;
@@ -82,14 +109,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
   const T* __restrict__ wp = (const T*)a.w;
   const int Hs0 = a.up0 ? (H >> 1) : H, Ws0 = a.up0 ? (W >> 1) : W;
 
-  // zero the padded tail of every weight row once (K beyond 9*CK contributes nothing)
-  if constexpr (Cfg::KW > 9 * CK) {
-    constexpr int PADC = (Cfg::KW - 9 * CK) / CH;
-    for (int it = t; it < BN * PADC; it += 256) {
-      const int row = it / PADC, pc = it - row * PADC;
-      *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + (9 * CK + pc * CH) * (int)sizeof(T)) = u32x4{0u, 0u, 0u, 0u};
-    }
-  }
+  weights_zero_tail<T, CK, BN, BN, 256>(wl, t);
 
   f32x4_t acc[TM][TN];
 #pragma unroll
@@ -108,13 +128,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
     const int Hs = use0 ? Hs0 : H, Ws = use0 ? Ws0 : W, Cs = use0 ? a.C0 : a.C1;
     const int sh = (use0 && a.up0) ? 1 : 0;
     const int coff = use0 ? cbase : cbase - a.C0;
-    if (LZ && a.in_scale) {
-#pragma unroll
-      for (int e = 0; e < CH; ++e) {
-        lsc[e] = a.in_scale[cbase + (t % CPP) * CH + e];
-        lsh[e] = a.in_shift[cbase + (t % CPP) * CH + e];
-      }
-    }
+    if (LZ && a.in_scale) lazy_coef_load<T, CPP>(a.in_scale, a.in_shift, cbase, t, lsc, lsh);
     unsigned hb2 = 0;
 #pragma unroll
     for (int k = 0; k < Cfg::HITEMS; ++k) {
@@ -182,11 +196,11 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int q = 0; q < TN; ++q) HMma<T>::run(af[i], bfr[q], acc[i][q]);
+        for (int q = 0; q < TN; ++q) Mma<T>::run(af[i], bfr[q], acc[i][q]);
     }
   }
 
-  // ------------------------------------------------------------------ epilogue (as conv_igemm)
+  // ------------------------------------------------------------------ epilogue (C tile in LDS: tile_store.h)
   __syncthreads();
   unsigned char* ct = smem;
   float* st = reinterpret_cast<float*>(smem + Cfg::MAIN);
@@ -224,13 +238,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
     }
   }
   __syncthreads();
-  if (a.stats && t < BN && (n0 + t) < a.Cout) {
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
-    a.stats[(long)(n0 + t) * gridDim.x + blockIdx.x] = x1;
-    a.stats[((long)a.Cout + n0 + t) * gridDim.x + blockIdx.x] = x2;
-  }
+  if (a.stats) tile_stats_write<4, BN>(st, a.stats, a.Cout, n0, gridDim.x, blockIdx.x, t);
   store_tile<T, TW, TH * TW, BN, 256, Cfg::CLD>(a, ct, n, y0, x0, n0, t);
   if (a.out_nchw) {
     const long HWp = (long)H * W;
@@ -247,28 +255,11 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const ConvArgs a) {
 
 template <typename T, int CK, int BN, bool LZ>
 int launch_halo_cfg_l(const ConvArgs& a, hipStream_t s) {
-  using Cfg = HaloCfg<T, CK, BN>;
-  auto kern = conv3x3_halo_kernel<T, CK, BN, LZ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const long M = (long)a.N * a.Hout * a.Wout;
   dim3 grid((unsigned)(M / (TH * TW)), cdiv(a.Cout, BN));
-  {
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg;
-    const double bytes = ((double)M / (a.up0 ? 4 : 1) * a.C0 + (double)M * a.C1 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
-                         (double)a.Cout * a.Kg * sizeof(T) + (a.out_nchw ? (double)M * a.Cout * 4.0 : 0.0);
-    static const char* names[2][2] = {{"conv3x3_halo_f32_ck16", "conv3x3_halo_f32_ck32"}, {"conv3x3_halo_bf16_ck16", "conv3x3_halo_bf16_ck32"}};
-    ProfScope ps(names[sizeof(T) == 2][CK == 32], flops, bytes, s);
-    hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::SMEM, s, a);
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<conv3x3_halo_kernel<T, CK, BN, LZ>>(halo_prof_name(sizeof(T), CK), conv_prof_cost(a, sizeof(T), true, true), grid,
+                                                           dim3(256), HaloCfg<T, CK, BN>::SMEM, s, a);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // Persistent variant for the single-chunk layers (16 or 32 input channels from one source, one column block): the
@@ -301,31 +292,11 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
   const int tiles_x = W / TW, tiles_y = H / TH;
   const T* __restrict__ src0 = (const T*)a.src0;
   const T* __restrict__ wp = (const T*)a.w;
-  const int Hs = a.up0 ? (H >> 1) : H, Ws = a.up0 ? (W >> 1) : W;
-  const int sh = a.up0 ? 1 : 0;
+  const HaloSrc<T> src{src0, a.up0 ? (H >> 1) : H, a.up0 ? (W >> 1) : W, CK, a.up0 ? 1 : 0, 0};
 
-  // weights: all nine taps of the one chunk, once (+ the zero tail of every row)
-  if constexpr (Cfg::KW > 9 * CK) {
-    constexpr int PADC = (Cfg::KW - 9 * CK) / CH;
-    for (int it = t; it < BN * PADC; it += 256) {
-      const int row = it / PADC, pc = it - row * PADC;
-      *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + (9 * CK + pc * CH) * (int)sizeof(T)) = u32x4{0u, 0u, 0u, 0u};
-    }
-  }
-  for (int it = t; it < BN * 9 * CPP; it += 256) {
-    const int row = it / (9 * CPP), rem = it - row * (9 * CPP);
-    const int tap = rem / CPP, ch = rem - tap * CPP;
-    *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + rem * 16) =
-        *reinterpret_cast<const u32x4*>(wp + (long)row * a.Kpad + tap * CK + ch * CH);
-  }
+  weights_stage<T, CK, BN, BN, 256>(wl, wp, a.Kpad, t);
   float lsc[CH], lsh[CH];   // lazy BN + ReLU of the producing unit: a thread always stages the same chunk column
-  if (LZ && a.in_scale) {
-#pragma unroll
-    for (int e = 0; e < CH; ++e) {
-      lsc[e] = a.in_scale[(t % CPP) * CH + e];
-      lsh[e] = a.in_shift[(t % CPP) * CH + e];
-    }
-  }
+  if (LZ && a.in_scale) lazy_coef_load<T, CPP>(a.in_scale, a.in_shift, 0, t, lsc, lsh);
   DirectCoef<TN> cf;
   cf.load(a, 0, lq);
   float s1[4 * TN], s2[4 * TN];
@@ -343,33 +314,12 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
   auto halo_load = [&](int tile, u32x4 (&hreg)[Cfg::HITEMS], unsigned& hbits) {
     const bool tok = tile < ntiles;
     const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
-    unsigned hb = 0;
-#pragma unroll
-    for (int k = 0; k < Cfg::HITEMS; ++k) {
-      const int it = t + 256 * k;
-      const int hp = it / CPP, ch = it - hp * CPP;
-      const int hy = hp / HW_, hx = hp - hy * HW_;
-      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-      const bool ok = tok && (it < HPIX * CPP) && ((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W);
-      const unsigned off = ok ? (unsigned)(((n * Hs + (iy >> sh)) * Ws + (ix >> sh)) * CK + ch * CH) : 0u;
-      hreg[k] = *reinterpret_cast<const u32x4*>(src0 + off);
-      hb |= (ok ? 1u : 0u) << k;
-    }
-    hbits = hb;
+    int n, y0, x0;
+    tile_decode<TW, TH>(tl, tiles_x, tiles_y, n, y0, x0);
+    halo_gather<T, TW, TH, CPP, 256>(src, tok, n, y0, x0, H, W, t, hreg, hbits);
   };
   auto halo_store = [&](const u32x4 (&hreg)[Cfg::HITEMS], unsigned hbits) {
-#pragma unroll
-    for (int k = 0; k < Cfg::HITEMS; ++k) {
-      const int it = t + 256 * k;
-      if (it < HPIX * CPP) {
-        const int hp = it / CPP, ch = it - hp * CPP;
-        const u32x4 hv = (LZ && a.in_scale) ? chunk_bn_relu<T>(hreg[k], lsc, lsh) : hreg[k];
-        *reinterpret_cast<u32x4*>(halo + hp * Cfg::PSTRIDE + ch * 16) = hv & (0u - ((hbits >> k) & 1u));
-      }
-    }
+    halo_put<T, TW, TH, CPP, 256, Cfg::HITEMS, HaloRows<Cfg::PSTRIDE>, LZ>(halo, t, hreg, hbits, a.in_scale != nullptr, lsc, lsh);
   };
 
   halo_load(blockIdx.x, hregA, hbitsA);
@@ -401,12 +351,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
       for (int q = 0; q < TN; ++q)
         bfr[q] = *reinterpret_cast<const u32x4*>(wl + direct_row_channel<TN>(q, lr) * Cfg::WROW + k0 * (int)sizeof(T));
     };
-    auto mmk = [&](const u32x4 (&af)[TM], const u32x4 (&bfr)[TN]) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int q = 0; q < TN; ++q) HMma<T>::run(bfr[q], af[i], acc[i][q]);   // weights as A: D = [cout][pixel]
-    };
+    auto mmk = [&](const u32x4 (&af)[TM], const u32x4 (&bfr)[TN]) { k_mma<T, TN>(af, bfr, acc); };
     constexpr int NK = Cfg::KW / KF;
     if constexpr (CK == 16) {
       // 16-channel layers: fragment reads one K step ahead of the MFMAs in two register sets pinned by scheduling fences (hipcc's
@@ -437,9 +382,8 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
       }
     }
     {
-      const int n = tile / (tiles_x * tiles_y);
-      const int trem = tile - n * tiles_x * tiles_y;
-      const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+      int n, y0, x0;
+      tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
       if constexpr (CE) direct_store<T, TW, TN, true, false, true>(a, acc, n, y0, x0, 0, wave, lane, cf, s1, s2, nullptr, &ce);
       else direct_store<T, TW, TN, !BNR, BNR>(a, acc, n, y0, x0, 0, wave, lane, cf, s1, s2, &bn);   // (a data gradient has no affine / statistics)
     }
@@ -455,25 +399,13 @@ __global__ __launch_bounds__(256) void conv3x3_halo_p_kernel(const ConvArgs a, i
   if constexpr (BNR) {   // one partial per workgroup and channel, like the statistics: [2][bnr_C][gridDim.x]
     direct_stats_wave<TN>(bn.r1, bn.r2, st, BN, 0, wave, lane);
     __syncthreads();
-    if (t < BN && t < a.bnr_C) {
-      float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
-      a.bnr_partial[(long)t * gridDim.x + blockIdx.x] = x1;
-      a.bnr_partial[((long)a.bnr_C + t) * gridDim.x + blockIdx.x] = x2;
-    }
+    tile_stats_write<4, BN>(st, a.bnr_partial, a.bnr_C, 0, gridDim.x, blockIdx.x, t);
     return;
   }
   if (a.stats) {
     direct_stats_wave<TN>(s1, s2, st, BN, 0, wave, lane);
     __syncthreads();
-    if (t < BN && t < a.Cout) {
-      float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
-      a.stats[(long)t * gridDim.x + blockIdx.x] = x1;
-      a.stats[((long)a.Cout + t) * gridDim.x + blockIdx.x] = x2;
-    }
+    tile_stats_write<4, BN>(st, a.stats, a.Cout, 0, gridDim.x, blockIdx.x, t);
   }
 }
 
@@ -491,18 +423,8 @@ static bool conv_halo_bnr_ok(const ConvArgs& a) {
 // 3 that fit).  Without a device (planning on a CPU-only host) the LDS bound stands in.
 template <typename T, int CK, int BN, bool LZ, bool BNR = false, bool CE = false>
 int halo_p_per_cu() {
-  static const int per_cu = [] {
-    int lds = (160 * 1024) / HaloPCfg<T, CK, BN, CE>::SMEM;
-    lds = lds > 4 ? 4 : (lds < 1 ? 1 : lds);
-    int nb = 0;
-    auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloPCfg<T, CK, BN, CE>::SMEM) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, HaloPCfg<T, CK, BN, CE>::SMEM) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      return lds;
-    }
-    return nb > 8 ? 8 : nb;
-  }();
+  constexpr int SMEM = HaloPCfg<T, CK, BN, CE>::SMEM, LDS = (160 * 1024) / SMEM;
+  const int per_cu = resident_per_cu<conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>>(256, SMEM, LDS > 4 ? 4 : (LDS < 1 ? 1 : LDS), 8);
   const int cap = tune("FLAIR_HALO_P_WGS", 0);
   return cap > 0 && cap < per_cu ? cap : per_cu;
 }
@@ -520,25 +442,10 @@ int halo_p_blocks(const ConvArgs& a) {
 
 template <typename T, int CK, int BN, bool LZ, bool BNR = false, bool CE = false>
 int launch_halo_p_l(const ConvArgs& a, hipStream_t s) {
-  using PC = HaloPCfg<T, CK, BN, CE>;
-  auto kern = conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PC::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const long M = (long)a.N * a.Hout * a.Wout;
-  {
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg;
-    const double bytes = ((double)M / (a.up0 ? 4 : 1) * a.C0 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
-                         (double)a.Cout * a.Kg * sizeof(T) + (a.out_nchw ? (double)M * a.Cout * 4.0 : 0.0);
-    static const char* names[2][2] = {{"conv3x3_halo_f32_ck16", "conv3x3_halo_f32_ck32"}, {"conv3x3_halo_bf16_ck16", "conv3x3_halo_bf16_ck32"}};
-    ProfScope ps(names[sizeof(T) == 2][CK == 32], flops, bytes, s);
-    hipLaunchKernelGGL(kern, dim3(halo_p_blocks<T, CK, BN>(a)), dim3(256), PC::SMEM, s, a, (int)(M / (TH * TW)));
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<conv3x3_halo_p_kernel<T, CK, BN, LZ, BNR, CE>>(halo_prof_name(sizeof(T), CK), conv_prof_cost(a, sizeof(T), false, true),
+                                                                      dim3(halo_p_blocks<T, CK, BN>(a)), dim3(256),
+                                                                      HaloPCfg<T, CK, BN, CE>::SMEM, s, a, (int)(M / (TH * TW)));
 }
 
 template <typename T, int CK, int BN>
@@ -550,7 +457,6 @@ int launch_halo_p(const ConvArgs& a, hipStream_t s) {
   if (a.bnr_partial) return conv_halo_bnr_ok(a) ? launch_halo_p_l<T, CK, BN, false, true>(a, s) : -6;
   return a.in_scale ? launch_halo_p_l<T, CK, BN, true>(a, s) : launch_halo_p_l<T, CK, BN, false>(a, s);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // Persistent variant with SEVERAL column blocks per workgroup (32 -> 128 at 256^2: the data gradient of decoder block 3's
@@ -581,32 +487,11 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_pm_kernel(const ConvArgs a, i
   const int lr = lane & 15, lq = lane >> 4;
   const int H = a.Hout, W = a.Wout;
   const int tiles_x = W / TW, tiles_y = H / TH;
-  const T* __restrict__ src0 = (const T*)a.src0;
-  const T* __restrict__ wp = (const T*)a.w;
-  const int Hs = a.up0 ? (H >> 1) : H, Ws = a.up0 ? (W >> 1) : W;
-  const int sh = a.up0 ? 1 : 0;
+  const HaloSrc<T> src{(const T*)a.src0, a.up0 ? (H >> 1) : H, a.up0 ? (W >> 1) : W, CK, a.up0 ? 1 : 0, 0};
 
-  if constexpr (Cfg::KW > 9 * CK) {
-    constexpr int PADC = (Cfg::KW - 9 * CK) / CH;
-    for (int it = t; it < NB * BN * PADC; it += NT) {
-      const int row = it / PADC, pc = it - row * PADC;
-      *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + (9 * CK + pc * CH) * (int)sizeof(T)) = u32x4{0u, 0u, 0u, 0u};
-    }
-  }
-  for (int it = t; it < NB * BN * 9 * CPP; it += NT) {
-    const int row = it / (9 * CPP), rem = it - row * (9 * CPP);
-    const int tap = rem / CPP, ch = rem - tap * CPP;
-    *reinterpret_cast<u32x4*>(wl + row * Cfg::WROW + rem * 16) =
-        *reinterpret_cast<const u32x4*>(wp + (long)row * a.Kpad + tap * CK + ch * CH);
-  }
+  weights_stage<T, CK, BN, NB * BN, NT>(wl, (const T*)a.w, a.Kpad, t);
   float lsc[CH], lsh[CH];
-  if (LZ && a.in_scale) {
-#pragma unroll
-    for (int e = 0; e < CH; ++e) {
-      lsc[e] = a.in_scale[(t % CPP) * CH + e];
-      lsh[e] = a.in_shift[(t % CPP) * CH + e];
-    }
-  }
+  if (LZ && a.in_scale) lazy_coef_load<T, CPP>(a.in_scale, a.in_shift, 0, t, lsc, lsh);
   DirectCoef<TN> cf;              // unused: plain results only (no per-channel affine, no statistics: halo_persistent_multi)
   float s1[4 * TN], s2[4 * TN];
 
@@ -614,34 +499,12 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_pm_kernel(const ConvArgs a, i
   unsigned hbitsA = 0, hbitsB = 0;
   auto halo_load = [&](int tile, u32x4 (&hreg)[HIT], unsigned& hbits) {
     const bool tok = tile < ntiles;
-    const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
-    unsigned hb = 0;
-#pragma unroll
-    for (int k = 0; k < HIT; ++k) {
-      const int it = t + NT * k;
-      const int hp = it / CPP, ch = it - hp * CPP;
-      const int hy = hp / HW_, hx = hp - hy * HW_;
-      const int iy = y0 - 1 + hy, ix = x0 - 1 + hx;
-      const bool ok = tok && (it < HPIX * CPP) && ((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W);
-      const unsigned off = ok ? (unsigned)(((n * Hs + (iy >> sh)) * Ws + (ix >> sh)) * CK + ch * CH) : 0u;
-      hreg[k] = *reinterpret_cast<const u32x4*>(src0 + off);
-      hb |= (ok ? 1u : 0u) << k;
-    }
-    hbits = hb;
+    int n, y0, x0;
+    tile_decode<TW, TH>(tok ? tile : 0, tiles_x, tiles_y, n, y0, x0);
+    halo_gather<T, TW, TH, CPP, NT>(src, tok, n, y0, x0, H, W, t, hreg, hbits);
   };
   auto halo_store = [&](const u32x4 (&hreg)[HIT], unsigned hbits) {
-#pragma unroll
-    for (int k = 0; k < HIT; ++k) {
-      const int it = t + NT * k;
-      if (it < HPIX * CPP) {
-        const int hp = it / CPP, ch = it - hp * CPP;
-        const u32x4 hv = (LZ && a.in_scale) ? chunk_bn_relu<T>(hreg[k], lsc, lsh) : hreg[k];
-        *reinterpret_cast<u32x4*>(halo + hp * Cfg::PSTRIDE + ch * 16) = hv & (0u - ((hbits >> k) & 1u));
-      }
-    }
+    halo_put<T, TW, TH, CPP, NT, HIT, HaloRows<Cfg::PSTRIDE>, LZ>(halo, t, hreg, hbits, a.in_scale != nullptr, lsc, lsh);
   };
 
   halo_load(blockIdx.x, hregA, hbitsA);
@@ -651,9 +514,8 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_pm_kernel(const ConvArgs a, i
   auto do_tile = [&](int tile, u32x4 (&ld)[HIT], unsigned& ldbits, const u32x4 (&stg)[HIT], const unsigned& stbits) {
     halo_load(tile + 2 * gridDim.x, ld, ldbits);
     __builtin_amdgcn_sched_barrier(0);
-    const int n = tile / (tiles_x * tiles_y);
-    const int trem = tile - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    int n, y0, x0;
+    tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
 #pragma unroll
     for (int jb = 0; jb < NBG; ++jb) {
       const int nb = wgrp * NBG + jb;
@@ -678,10 +540,7 @@ __global__ __launch_bounds__(NT) void conv3x3_halo_pm_kernel(const ConvArgs a, i
 #pragma unroll
         for (int q = 0; q < TN; ++q)
           bfr[q] = *reinterpret_cast<const u32x4*>(wl + (nb * BN + direct_row_channel<TN>(q, lr)) * Cfg::WROW + k0 * (int)sizeof(T));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int q = 0; q < TN; ++q) HMma<T>::run(bfr[q], af[i], acc[i][q]);
+        k_mma<T, TN>(af, bfr, acc);
       }
       direct_store<T, TW, TN, false>(a, acc, n, y0, x0, nb * BN, wave, lane, cf, s1, s2);   // registers -> HBM, no barrier
     }
@@ -699,17 +558,7 @@ constexpr int PM_NT = 512;
 
 template <typename T, int CK, int BN, int NB, bool LZ>
 int halo_pm_per_cu() {
-  static const int per_cu = [] {
-    int nb = 0;
-    auto kern = conv3x3_halo_pm_kernel<T, CK, BN, NB, LZ, PM_NT>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HaloPMCfg<T, CK, BN, NB>::SMEM) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, PM_NT, HaloPMCfg<T, CK, BN, NB>::SMEM) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      return 1;
-    }
-    return nb > 4 ? 4 : nb;
-  }();
-  return per_cu;
+  return resident_per_cu<conv3x3_halo_pm_kernel<T, CK, BN, NB, LZ, PM_NT>>(PM_NT, HaloPMCfg<T, CK, BN, NB>::SMEM, 1, 4);
 }
 
 template <typename T, int CK, int BN, int NB>
@@ -721,23 +570,11 @@ int halo_pm_blocks(const ConvArgs& a) {
 
 template <typename T, int CK, int BN, int NB, bool LZ>
 int launch_halo_pm_l(const ConvArgs& a, hipStream_t s) {
-  using PC = HaloPMCfg<T, CK, BN, NB>;
-  auto kern = conv3x3_halo_pm_kernel<T, CK, BN, NB, LZ, PM_NT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, PC::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static_assert(sizeof(T) == 2, "bf16 only (halo_persistent_multi)");
   const long M = (long)a.N * a.Hout * a.Wout;
-  {
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg;
-    const double bytes = ((double)M / (a.up0 ? 4 : 1) * a.C0 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) + (double)a.Cout * a.Kg * sizeof(T);
-    ProfScope ps(CK == 32 ? "conv3x3_halo_bf16_ck32" : "conv3x3_halo_bf16_ck16", flops, bytes, s);
-    hipLaunchKernelGGL(kern, dim3(halo_pm_blocks<T, CK, BN, NB>(a)), dim3(PM_NT), PC::SMEM, s, a, (int)(M / (TH * TW)));
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<conv3x3_halo_pm_kernel<T, CK, BN, NB, LZ, PM_NT>>(halo_prof_name(sizeof(T), CK), conv_prof_cost(a, sizeof(T), false, false),
+                                                                         dim3(halo_pm_blocks<T, CK, BN, NB>(a)), dim3(PM_NT),
+                                                                         HaloPMCfg<T, CK, BN, NB>::SMEM, s, a, (int)(M / (TH * TW)));
 }
 
 // bf16, 32 input channels from one source, 128 output channels (four 32-wide blocks), no fp32 NCHW copy
@@ -771,12 +608,19 @@ bool conv_halo_applicable(const ConvArgs& a) {
   return Cin <= 128 && a.Cout <= 128 && (a.Cout <= 32 || Cin <= 32);
 }
 
-template <typename T>
-static int halo_rows_t(const ConvArgs& a) {
-  const int Cin = a.C0 + a.C1;
-  const bool n16 = a.Cout <= 16;
-  if (Cin == 16) return n16 ? halo_p_blocks<T, 16, 16>(a) : halo_p_blocks<T, 16, 32>(a);
-  return n16 ? halo_p_blocks<T, 32, 16>(a) : halo_p_blocks<T, 32, 32>(a);
+// The instantiations of the single-block kernels: dtype x input chunk (16 channels, else 32) x column block (16 | 32); f gets the
+// choice as a HaloPick value
+template <typename T_, int CK_, int BN_>
+struct HaloPick { using T = T_; static constexpr int CK = CK_, BN = BN_; };
+template <typename F>
+static int halo_pick(int dtype, const ConvArgs& a, F f) {
+  const bool c16 = a.C0 + a.C1 == 16, n16 = a.Cout <= 16;
+  if (dtype == DT_F32) {
+    if (c16) return n16 ? f(HaloPick<float, 16, 16>()) : f(HaloPick<float, 16, 32>());
+    return n16 ? f(HaloPick<float, 32, 16>()) : f(HaloPick<float, 32, 32>());
+  }
+  if (c16) return n16 ? f(HaloPick<bf16_t, 16, 16>()) : f(HaloPick<bf16_t, 16, 32>());
+  return n16 ? f(HaloPick<bf16_t, 32, 16>()) : f(HaloPick<bf16_t, 32, 32>());
 }
 
 bool conv_halo_bnr_applicable(const ConvArgs& a) { return conv_halo_applicable(a) && conv_halo_bnr_ok(a); }
@@ -789,7 +633,8 @@ bool conv_halo_preds_ok(int dtype, const ConvArgs& a) {
 
 int conv_halo_grid_rows(int dtype, const ConvArgs& a) {
   if (halo_persistent_multi(dtype, a)) return halo_pm_blocks<bf16_t, 32, 32, 4>(a);
-  if (halo_persistent(a)) return dtype == DT_F32 ? halo_rows_t<float>(a) : halo_rows_t<bf16_t>(a);
+  if (halo_persistent(a))
+    return halo_pick(dtype, a, [&](auto p) { using P = decltype(p); return halo_p_blocks<typename P::T, P::CK, P::BN>(a); });
   return (int)((long)a.N * a.Hout * a.Wout / (TH * TW));
 }
 
@@ -801,26 +646,15 @@ bool conv_halo_ce_ok(int dtype, const ConvArgs& a) {
 }
 
 int launch_conv_halo(int dtype, const ConvArgs& a, hipStream_t s) {
-  const int Cin = a.C0 + a.C1;
-  const bool n16 = a.Cout <= 16;
   if (a.preds_u8 && !conv_halo_preds_ok(dtype, a)) return -6;
   if (a.ce_lab8 && !conv_halo_ce_ok(dtype, a)) return -6;
   if (halo_persistent_multi(dtype, a))
     return a.in_scale ? launch_halo_pm_l<bf16_t, 32, 32, 4, true>(a, s) : launch_halo_pm_l<bf16_t, 32, 32, 4, false>(a, s);
-  if (halo_persistent(a)) {
-    if (dtype == DT_F32) {
-      if (Cin == 16) return n16 ? launch_halo_p<float, 16, 16>(a, s) : launch_halo_p<float, 16, 32>(a, s);
-      return n16 ? launch_halo_p<float, 32, 16>(a, s) : launch_halo_p<float, 32, 32>(a, s);
-    }
-    if (Cin == 16) return n16 ? launch_halo_p<bf16_t, 16, 16>(a, s) : launch_halo_p<bf16_t, 16, 32>(a, s);
-    return n16 ? launch_halo_p<bf16_t, 32, 16>(a, s) : launch_halo_p<bf16_t, 32, 32>(a, s);
-  }
-  if (dtype == DT_F32) {
-    if (Cin == 16) return n16 ? launch_halo_cfg<float, 16, 16>(a, s) : launch_halo_cfg<float, 16, 32>(a, s);
-    return n16 ? launch_halo_cfg<float, 32, 16>(a, s) : launch_halo_cfg<float, 32, 32>(a, s);
-  }
-  if (Cin == 16) return n16 ? launch_halo_cfg<bf16_t, 16, 16>(a, s) : launch_halo_cfg<bf16_t, 16, 32>(a, s);
-  return n16 ? launch_halo_cfg<bf16_t, 32, 16>(a, s) : launch_halo_cfg<bf16_t, 32, 32>(a, s);
+  const bool persist = halo_persistent(a);
+  return halo_pick(dtype, a, [&](auto p) {
+    using P = decltype(p);
+    return persist ? launch_halo_p<typename P::T, P::CK, P::BN>(a, s) : launch_halo_cfg<typename P::T, P::CK, P::BN>(a, s);
+  });
 }
 
 }  // namespace flair

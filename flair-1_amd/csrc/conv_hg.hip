@@ -7,35 +7,21 @@
 // (prefetched in registers across the 9 tap steps of the previous chunk); all nine taps read their A
 // fragments from that halo with shifted addresses.  Only the weight tile [BN][128 B] per (tap, chunk) is
 // streamed (register-staged, double-buffered LDS).  Every wave owns a 64x64 accumulator tile.
-// Numerics, operand packing and epilogue (LDS transpose -> 16-byte NHWC stores, BN partial sums) are those
-// of conv_igemm.  Tile / buffering variants are template parameters; launch_conv_hg picks per layer.
+// Numerics and operand packing are those of conv_igemm; the halo goes to LDS through halo_stage.h (128-byte pixels, XOR-swizzled
+// chunks), the epilogue is tile_store.h (LDS transpose -> 16-byte NHWC stores, BN partial sums).  Tile / buffering variants are
+// template parameters; launch_conv_hg picks per layer.
 #include <stdlib.h>
 
 #include "common.h"
 #include "conv_route.h"
-#include "prof.h"
+#include "halo_stage.h"
+#include "launch.h"
+#include "mma.h"
 #include "tile_store.h"
 #include "tune.h"
 
 namespace flair {
 namespace {
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-template <typename T> struct GMma;
-template <> struct GMma<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct GMma<float> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-  }
-};
 
 __device__ __forceinline__ int sw_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
@@ -91,9 +77,8 @@ __global__ __launch_bounds__(TW * TH * BN / (16 * TMv), 2) void conv3x3_hg_kerne
   }
   const int tile = w / NB;
   const int ntiles = nwork / NB;
-  const int n = tile / (tiles_x * tiles_y);
-  const int trem = tile - n * tiles_x * tiles_y;
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  int n, y0, x0;
+  tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
   const int n0 = (w - tile * NB) * BN;
   const int Cin = a.C0 + a.C1;
   const T* __restrict__ src0 = (const T*)a.src0;
@@ -128,14 +113,7 @@ __global__ __launch_bounds__(TW * TH * BN / (16 * TMv), 2) void conv3x3_hg_kerne
   };
   auto halo_store = [&](int buf) {
     unsigned char* hb = halo0 + buf * Cfg::HALO;
-#pragma unroll
-    for (int k = 0; k < Cfg::HITEMS; ++k) {
-      const int it = t + NT * k;
-      if (it < HPIX * 8) {
-        const int hp = it >> 3, hx = hp % HW_;
-        *reinterpret_cast<u32x4*>(hb + hp * 128 + (((it & 7) ^ (hx & 7)) << 4)) = hreg[k] & (0u - ((hbits >> k) & 1u));
-      }
-    }
+    halo_put<T, TW, TH, 8, NT, Cfg::HITEMS, HaloSwizzle<HW_>, false>(hb, t, hreg, hbits, false, nullptr, nullptr);
   };
   // ---- weight tile of (chunk, tap): [BN][128 B]
   u32x4 breg[Cfg::BITEMS];
@@ -219,7 +197,7 @@ __global__ __launch_bounds__(TW * TH * BN / (16 * TMv), 2) void conv3x3_hg_kerne
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) GMma<T>::run(af[i], bfr[j], acc[i0 + i][j]);
+            for (int j = 0; j < TN; ++j) Mma<T>::run(af[i], bfr[j], acc[i0 + i][j]);
         }
       }
       b_store(cur ^ 1);
@@ -237,7 +215,7 @@ __global__ __launch_bounds__(TW * TH * BN / (16 * TMv), 2) void conv3x3_hg_kerne
     }
   }
 
-  // ------------------------------------------------------------------ epilogue (as conv_igemm)
+  // ------------------------------------------------------------------ epilogue (C tile in LDS: tile_store.h)
   unsigned char* ct = smem;
   float* st = reinterpret_cast<float*>(smem + Cfg::MAIN);
   float s1[TN], s2[TN];
@@ -275,16 +253,9 @@ __global__ __launch_bounds__(TW * TH * BN / (16 * TMv), 2) void conv3x3_hg_kerne
     }
   }
   __syncthreads();
-  if (a.stats && t < BN && (n0 + t) < a.Cout) {
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < Cfg::WMN; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
-    a.stats[(long)(n0 + t) * ntiles + tile] = x1;
-    a.stats[((long)a.Cout + n0 + t) * ntiles + tile] = x2;
-  }
+  if (a.stats) tile_stats_write<Cfg::WMN, BN>(st, a.stats, a.Cout, n0, ntiles, tile, t);
   store_tile<T, TW, TPIX, BN, NT, Cfg::CLD, BNR>(a, ct, n, y0, x0, n0, t, tile, ntiles);
 }
-
 
 // ------------------------------------------------------------------------------------------------------------------
 // Round-2 structure: the weight tile never passes through registers.  Each wave streams its share of the [BN][128 B]
@@ -370,9 +341,8 @@ __global__ __launch_bounds__(TW * TH * (BN >= 64 ? BN : 64) / 64, 2) void conv3x
   }
   const int tile = w / NB;
   const int ntiles = nwork / NB;
-  const int n = tile / (tiles_x * tiles_y);
-  const int trem = tile - n * tiles_x * tiles_y;
-  const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+  int n, y0, x0;
+  tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
   const int n0 = (w - tile * NB) * BN;
   const int Cin = a.C0 + a.C1;
   const T* __restrict__ src0 = (const T*)a.src0;
@@ -496,7 +466,7 @@ __global__ __launch_bounds__(TW * TH * (BN >= 64 ? BN : 64) / 64, 2) void conv3x
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j) GMma<T>::run(bf[j], af[i], acc[i][j]);
+      for (int j = 0; j < TN; ++j) Mma<T>::run(bf[j], af[i], acc[i][j]);
   };
   // ---- prologue: halo 0, weight tiles of steps 0 .. D-1, halo 1 into registers
   halo_load(0);
@@ -648,8 +618,8 @@ __global__ __launch_bounds__(TW * TH * (BN >= 64 ? BN : 64) / 64, 2) void conv3x
           xf.z = (unsigned)(unsigned short)x1[0] | ((unsigned)(unsigned short)x1[1] << 16);
           xf.w = (unsigned)(unsigned short)x1[2] | ((unsigned)(unsigned short)x1[3] << 16);
           const u32x4 ones = u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-          GMma<T>::run(ones, xf, m1);
-          GMma<T>::run(xf, xf, m2);
+          Mma<T>::run(ones, xf, m1);
+          Mma<T>::run(xf, xf, m2);
         }
       } else {
 #pragma unroll
@@ -660,8 +630,8 @@ __global__ __launch_bounds__(TW * TH * (BN >= 64 ? BN : 64) / 64, 2) void conv3x
           xf.z = *reinterpret_cast<const unsigned*>(cw + ((kk + 2) * 4 + lq) * Cfg::CLD + (q * 16 + lr) * 4);
           xf.w = *reinterpret_cast<const unsigned*>(cw + ((kk + 3) * 4 + lq) * Cfg::CLD + (q * 16 + lr) * 4);
           const u32x4 ones = u32x4{0x3F800000u, 0x3F800000u, 0x3F800000u, 0x3F800000u};
-          GMma<T>::run(ones, xf, m1);
-          GMma<T>::run(xf, xf, m2);
+          Mma<T>::run(ones, xf, m1);
+          Mma<T>::run(xf, xf, m2);
         }
       }
       // m1: every row holds the column sums -> row 0 = lanes with lq == 0, register 0.  m2: the diagonal element of
@@ -673,45 +643,29 @@ __global__ __launch_bounds__(TW * TH * (BN >= 64 ? BN : 64) / 64, 2) void conv3x
     }
   }
   __syncthreads();
-  if (a.stats && t < BN && (n0 + t) < a.Cout) {
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w2 = 0; w2 < Cfg::WMN; ++w2) { x1 += st[(w2 * BN + t) * 2]; x2 += st[(w2 * BN + t) * 2 + 1]; }
-    a.stats[(long)(n0 + t) * ntiles + tile] = x1;
-    a.stats[((long)a.Cout + n0 + t) * ntiles + tile] = x2;
-  }
+  if (a.stats) tile_stats_write<Cfg::WMN, BN>(st, a.stats, a.Cout, n0, ntiles, tile, t);
   stamp(3);
   store_tile<T, TW, TPIX, BN, NT, Cfg::CLD, BNR>(a, ct, n, y0, x0, n0, t, tile, ntiles);
   stamp(4);
   stamp(6);
 }
 
+static const char* hg_prof_name(size_t es, int BN) {
+  static const char* names[2][3] = {{"conv3x3_hg_f32_n32", "conv3x3_hg_f32_n64", "conv3x3_hg_f32_n128"},
+                                    {"conv3x3_hg_bf16_n32", "conv3x3_hg_bf16_n64", "conv3x3_hg_bf16_n128"}};
+  return names[es == 2][BN == 128 ? 2 : BN == 64 ? 1 : 0];
+}
+
 template <typename T, int TW, int TH, int BN, int HB, int NS, bool BNR, int XF>
 int launch_hgd_cfg_b(const ConvArgs& a, hipStream_t s) {
   using Cfg = HgdCfg<T, TW, TH, BN, HB, NS>;
-  auto kern = conv3x3_hgd_kernel<T, TW, TH, BN, HB, NS, BNR, XF>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const long M = (long)a.N * a.Hout * a.Wout;
   dim3 grid((unsigned)(M / Cfg::TPIX) * (a.Cout / BN));
   ConvArgs b = a;
   b.xcd_remap = tune("FLAIR_XCD_REMAP", 1);
   b.dbg = (unsigned long long*)g_debug_buffer;
-  {
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg;
-    const double bytes = ((double)M / (a.up0 ? 4 : 1) * a.C0 + (double)M * a.C1 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
-                         (double)a.Cout * a.Kg * sizeof(T);
-    static const char* names[2][3] = {{"conv3x3_hg_f32_n32", "conv3x3_hg_f32_n64", "conv3x3_hg_f32_n128"},
-                                      {"conv3x3_hg_bf16_n32", "conv3x3_hg_bf16_n64", "conv3x3_hg_bf16_n128"}};
-    ProfScope ps(names[sizeof(T) == 2][BN == 128 ? 2 : BN == 64 ? 1 : 0], flops, bytes, s);
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::SMEM, s, b);
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<conv3x3_hgd_kernel<T, TW, TH, BN, HB, NS, BNR, XF>>(hg_prof_name(sizeof(T), BN), conv_prof_cost(a, sizeof(T), true, false), grid,
+                                                                           dim3(Cfg::NT), Cfg::SMEM, s, b);
 }
 
 template <typename T, int TW, int TH, int BN, int HB, int NS>
@@ -734,29 +688,12 @@ int g_hg_variant = -1;  // tuning override (FLAIR_HG_VARIANT): 0 = 256 px x 8 wa
 template <typename T, int TW, int TH, int BN, int HB, bool BNR, int TMv = 4>
 int launch_hg_cfg_b(const ConvArgs& a, hipStream_t s) {
   using Cfg = HgCfg<T, TW, TH, BN, HB, TMv>;
-  auto kern = conv3x3_hg_kernel<T, TW, TH, BN, HB, BNR, TMv>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const long M = (long)a.N * a.Hout * a.Wout;
   dim3 grid((unsigned)(M / Cfg::TPIX) * (a.Cout / BN));
   ConvArgs b = a;
-  {
-    b.xcd_remap = tune("FLAIR_XCD_REMAP", 1);
-  }
-  {
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg;
-    const double bytes = ((double)M / (a.up0 ? 4 : 1) * a.C0 + (double)M * a.C1 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
-                         (double)a.Cout * a.Kg * sizeof(T);
-    static const char* names[2][2] = {{"conv3x3_hg_f32_n64", "conv3x3_hg_f32_n128"}, {"conv3x3_hg_bf16_n64", "conv3x3_hg_bf16_n128"}};
-    ProfScope ps(names[sizeof(T) == 2][BN == 128], flops, bytes, s);
-    hipLaunchKernelGGL(kern, grid, dim3(Cfg::NT), Cfg::SMEM, s, b);
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  b.xcd_remap = tune("FLAIR_XCD_REMAP", 1);
+  return launch_kernel<conv3x3_hg_kernel<T, TW, TH, BN, HB, BNR, TMv>>(hg_prof_name(sizeof(T), BN), conv_prof_cost(a, sizeof(T), true, false), grid,
+                                                                       dim3(Cfg::NT), Cfg::SMEM, s, b);
 }
 
 template <typename T, int TW, int TH, int BN, int HB, int TMv = 4>

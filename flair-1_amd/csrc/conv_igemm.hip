@@ -11,29 +11,14 @@
 // plus per-row-block partial BatchNorm sums (deterministic: no atomics).
 #include "common.h"
 #include "conv_route.h"
-#include "prof.h"
+#include "launch.h"
+#include "mma.h"
+#include "tile_store.h"
 #include "tune.h"
 
 namespace flair {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // first-class 16-byte vector (SSA-friendly, unlike HIP's uint4 struct)
-
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma<float> {
-  __device__ static __forceinline__ void run(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
-  }
-};
 
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N>
 struct ConvCfg {
@@ -240,14 +225,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvArgs a) {
     }
   }
   __syncthreads();
-  if (a.stats && t < BN && (n0 + t) < a.Cout) {
-    float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < WAVES_M; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
-    // channel-major partials [2][Cout][gridDim.x]: the finalize kernel reads them coalesced
-    a.stats[(long)(n0 + t) * gridDim.x + blockIdx.x] = x1;
-    a.stats[((long)a.Cout + n0 + t) * gridDim.x + blockIdx.x] = x2;
-  }
+  if (a.stats) tile_stats_write<WAVES_M, BN>(st, a.stats, a.Cout, n0, gridDim.x, blockIdx.x, t);
   if (a.out) {
     constexpr int CPR = BN / CH;
     T* __restrict__ out = (T*)a.out;
@@ -317,27 +295,16 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
   using Cfg = ConvCfg<T, BM, BN, WAVES_M, WAVES_N>;
   const long M = (long)a.N * a.Hout * a.Wout;
   dim3 grid(cdiv(M, BM), cdiv(a.Cout, BN), a.ncls ? a.ncls : 1);
-  auto kern = conv_igemm_kernel<T, BM, BN, WAVES_M, WAVES_N>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  {
-    // algorithmic work: 2*M*Cout*K real MACs (a data gradient with in_div = 2 only touches 1/4 of the taps)
-    const double flops = 2.0 * (double)M * a.Cout * a.Kg / (a.in_div * a.in_div);
-    const double bytes = ((double)a.N * a.Hin * a.Win / (a.in_div * a.in_div) / (a.up0 ? 4 : 1) * a.C0 +
-                          (double)a.N * a.Hin * a.Win * a.C1 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
-                         (double)a.Cout * a.Kg * sizeof(T);
-    static const char* names[2][4] = {{"conv_igemm_f32_128x128", "conv_igemm_f32_128x64", "conv_igemm_f32_256x32", "conv_igemm_f32_256x16"},
-                                      {"conv_igemm_bf16_128x128", "conv_igemm_bf16_128x64", "conv_igemm_bf16_256x32", "conv_igemm_bf16_256x16"}};
-    const int ci = BN == 128 ? 0 : BN == 64 ? 1 : BN == 32 ? 2 : 3;
-    ProfScope ps(names[sizeof(T) == 2][ci], flops, bytes, s);
-    hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::SMEM, s, a);
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  // algorithmic work: 2*M*Cout*K real MACs (a data gradient with in_div = 2 only touches 1/4 of the taps).  Not conv_prof_cost:
+  // this kernel alone serves strides and in_div, so its input is counted by Hin x Win and the live taps, not by the output pixels
+  const double flops = 2.0 * (double)M * a.Cout * a.Kg / (a.in_div * a.in_div);
+  const double bytes = ((double)a.N * a.Hin * a.Win / (a.in_div * a.in_div) / (a.up0 ? 4 : 1) * a.C0 +
+                        (double)a.N * a.Hin * a.Win * a.C1 + (double)M * a.Cout * (a.accumulate ? 2 : 1)) * sizeof(T) +
+                       (double)a.Cout * a.Kg * sizeof(T);
+  static const char* names[2][4] = {{"conv_igemm_f32_128x128", "conv_igemm_f32_128x64", "conv_igemm_f32_256x32", "conv_igemm_f32_256x16"},
+                                    {"conv_igemm_bf16_128x128", "conv_igemm_bf16_128x64", "conv_igemm_bf16_256x32", "conv_igemm_bf16_256x16"}};
+  const int ci = BN == 128 ? 0 : BN == 64 ? 1 : BN == 32 ? 2 : 3;
+  return launch_kernel<conv_igemm_kernel<T, BM, BN, WAVES_M, WAVES_N>>(names[sizeof(T) == 2][ci], ProfCost{flops, bytes}, grid, dim3(256), Cfg::SMEM, s, a);
 }
 
 static inline int pick_bn(int cout) { return cout >= 128 ? 128 : cout >= 64 ? 64 : cout >= 32 ? 32 : 16; }

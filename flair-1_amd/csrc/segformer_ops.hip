@@ -15,8 +15,6 @@
 namespace flair {
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------------------ LayerNorm
 // One group of G lanes (a power of two <= 64) per row, up to two 16-byte chunks per lane in registers; mean, then the
 // biased variance of the centred values (two passes over registers, fp32), eps inside the square root — nn.LayerNorm.

@@ -10,7 +10,9 @@
 // bf16 only; fp32 (the parity mode) stays on the generic kernel.
 #include "common.h"
 #include "conv_route.h"
-#include "prof.h"
+#include "halo_stage.h"
+#include "launch.h"
+#include "mma.h"
 #include "tune.h"
 
 namespace flair {
@@ -20,7 +22,6 @@ void launch_wgrad_reduce(const float* partial, float* dw, int splits, int Cout, 
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TH = 8, TW = 16, TPIX = TH * TW;            // output tile
 constexpr int HH = 2 * TH + 5, HWD = 2 * TW + 5, HPIX = HH * HWD;  // 21 x 37 input halo
 constexpr int XSTRIDE = 16, DSTRIDE = 128 + 16;           // bytes per halo pixel / per dY pixel (64 bf16 + pad)
@@ -75,10 +76,8 @@ __global__ __launch_bounds__(NT) void wgrad_stem_kernel(const StemWgArgs a) {
   auto load_tile = [&](int tile) {
     const bool tok = tile < a.ntiles;
     dr_tok = tok ? 1u : 0u;
-    const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    int n, y0, x0;
+    tile_decode<TW, TH>(tok ? tile : 0, tiles_x, tiles_y, n, y0, x0);
 #pragma unroll
     for (int k = 0; k < XITEMS; ++k) {
       const int it = t + NT * k;
@@ -169,8 +168,7 @@ __global__ __launch_bounds__(NT) void wgrad_stem_kernel(const StemWgArgs a) {
         const u32x4 bf = tr2(xrow + xoff[n], 8 * XSTRIDE);   // pixel + 4 of the step = halo column + 8
 #pragma unroll
         for (int m = 0; m < 4; ++m)
-          acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[m]), __builtin_bit_cast(bf16x8_t, bf),
-                                                              acc[m][n], 0, 0, 0);
+          Mma<bf16_t>::run(af[m], bf, acc[m][n]);
       }
     }
     store_tile((it + 1) & 1);
@@ -216,20 +214,11 @@ int launch_wgrad_stem(const WgradArgs& a, hipStream_t s) {
   h.y = (const bf16_t*)a.fuse_y; h.coef = a.fuse_coef; h.msc = a.fuse_msc; h.msh = a.fuse_msh;
   if (h.y && (!h.coef || !h.msc || !h.msh)) return -2;
   const int nsplit = stem_splits(a);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_stem_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_stem_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  {
-    const double M = (double)a.N * a.Hout * a.Wout;
-    ProfScope ps("wgrad_stem_bf16", 2.0 * M * 64 * TAPS * 8, (M * 64 * (h.y ? 2 : 1) + 4.0 * M * 8) * 2.0, s);
-    if (h.y) hipLaunchKernelGGL(wgrad_stem_kernel<true>, dim3(nsplit), dim3(NT), SMEM, s, h);
-    else hipLaunchKernelGGL(wgrad_stem_kernel<false>, dim3(nsplit), dim3(NT), SMEM, s, h);
-  }
-  FLAIR_CHECK_LAUNCH();
+  const double M = (double)a.N * a.Hout * a.Wout;
+  const ProfCost cost{2.0 * M * 64 * TAPS * 8, (M * 64 * (h.y ? 2 : 1) + 4.0 * M * 8) * 2.0};   // the 2x2 larger input once, dY (and y) once
+  const int rc = h.y ? launch_kernel<wgrad_stem_kernel<true>>("wgrad_stem_bf16", cost, dim3(nsplit), dim3(NT), SMEM, s, h)
+                     : launch_kernel<wgrad_stem_kernel<false>>("wgrad_stem_bf16", cost, dim3(nsplit), dim3(NT), SMEM, s, h);
+  if (rc) return rc;
   launch_wgrad_reduce(a.partial, a.dw, nsplit, 64, 64, TAPS * 8, 8, a.Cin_real, 7, 7, a.accumulate, s);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : (int)e;
@@ -291,10 +280,8 @@ __global__ __launch_bounds__(NT) void conv_stem_kernel(const ConvArgs a, int nti
   u32x4 xr[XITEMS];
   auto load_tile = [&](int tile) {
     const bool tok = tile < ntiles;
-    const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+    int n, y0, x0;
+    tile_decode<TW, TH>(tok ? tile : 0, tiles_x, tiles_y, n, y0, x0);
 #pragma unroll
     for (int k = 0; k < XITEMS; ++k) {
       const int it = t + NT * k;
@@ -340,8 +327,7 @@ __global__ __launch_bounds__(NT) void conv_stem_kernel(const ConvArgs a, int nti
       for (int m = 0; m < 4; ++m)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, af[m]), __builtin_bit_cast(bf16x8_t, bw[j][ks]),
-                                                              acc[m][j], 0, 0, 0);
+          Mma<bf16_t>::run(af[m], bw[j][ks], acc[m][j]);
     }
     // accumulators -> bf16 tile in LDS (+ running BatchNorm statistics of the ROUNDED values, like the other kernels)
 #pragma unroll
@@ -364,9 +350,8 @@ __global__ __launch_bounds__(NT) void conv_stem_kernel(const ConvArgs a, int nti
     store_halo((it + 1) & 1);
     __syncthreads();
     {
-      const int n = tile / (tiles_x * tiles_y);
-      const int trem = tile - n * tiles_x * tiles_y;
-      const int y0 = (trem / tiles_x) * TH, x0 = (trem % tiles_x) * TW;
+      int n, y0, x0;
+      tile_decode<TW, TH>(tile, tiles_x, tiles_y, n, y0, x0);
 #pragma unroll
       for (int k = 0; k < TPIX * 8 / NT; ++k) {
         const int idx = t + NT * k;
@@ -418,19 +403,9 @@ bool conv_stem_applicable(int dtype, const ConvArgs& a) {
 int conv_stem_grid_rows(const ConvArgs& a) { return stem_fwd_blocks(a); }
 
 int launch_conv_stem(const ConvArgs& a, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FSMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   const long M = (long)a.N * a.Hout * a.Wout;
-  {
-    ProfScope ps("conv_stem_bf16", 2.0 * (double)M * 64 * TAPS * 8, ((double)M * 64 + 4.0 * M * 8) * 2.0, s);
-    hipLaunchKernelGGL(conv_stem_kernel, dim3(stem_fwd_blocks(a)), dim3(NT), FSMEM, s, a, (int)(M / TPIX));
-  }
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<conv_stem_kernel>("conv_stem_bf16", ProfCost{2.0 * (double)M * 64 * TAPS * 8, ((double)M * 64 + 4.0 * M * 8) * 2.0},
+                                         dim3(stem_fwd_blocks(a)), dim3(NT), FSMEM, s, a, (int)(M / TPIX));
 }
 
 }  // namespace flair

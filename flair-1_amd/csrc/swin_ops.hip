@@ -10,8 +10,6 @@
 namespace flair {
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------ shifted-window attention
 // One wave per (window, head, image).  A window is 49 tokens, padded to 64 slots (four 16-row tiles); slots 49 .. 63 only fill
 // the tiles: as keys they get -inf, as queries they are never stored.  Slot j < 49 is position (j / 7, j % 7) of the window on
@@ -307,7 +305,6 @@ __global__ __launch_bounds__(256) void swin_avgpool_kernel(const T* __restrict__
     *reinterpret_cast<uint4*>(y + p * C + (long)c * CH) = f_to_chunk<T>(acc);
   }
 }
-
 
 // y += bilinear(x), both dense NHWC; the sum in fp32, rounded once
 template <typename T>

@@ -38,6 +38,21 @@ __device__ __forceinline__ void tile_bnr_prefetch(const ConvArgs& a, int n, int 
   }
 }
 
+// Tail of every per-channel partial reduction (BatchNorm batch statistics, ConvArgs::stats; fused BatchNorm-backward sums,
+// ConvArgs::bnr_partial): st holds [NW waves][BN columns][2] sums in LDS, already published by a barrier; thread t < BN adds the
+// waves in ascending order, the first sum and then the second, and writes column n0 + t of the channel-major partials
+// dst[2][C][ntiles] at `tile` (the finalize kernels read them coalesced).
+template <int NW, int BN>
+__device__ __forceinline__ void tile_stats_write(const float* st, float* dst, int C, int n0, int ntiles, int tile, int t) {
+  if (t < BN && n0 + t < C) {
+    float x1 = 0.f, x2 = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { x1 += st[(w * BN + t) * 2]; x2 += st[(w * BN + t) * 2 + 1]; }
+    dst[(long)(n0 + t) * ntiles + tile] = x1;
+    dst[((long)C + n0 + t) * ntiles + tile] = x2;
+  }
+}
+
 // tile_id / ntiles index the per-tile partial sums of the fused BN-backward reduction (default: the launch grid's x)
 template <typename T, int TW, int TPIX, int BN, int NT, int CLD, bool BNR = false>
 __device__ __forceinline__ void store_tile(const ConvArgs& a, const unsigned char* ct, int n, int y0, int x0, int n0, int t,
@@ -93,13 +108,7 @@ __device__ __forceinline__ void store_tile(const ConvArgs& a, const unsigned cha
       }
     }
     __syncthreads();
-    if (t < BN && n0 + t < a.bnr_C) {
-      float x1 = 0.f, x2 = 0.f;
-#pragma unroll
-      for (int w = 0; w < NT / 64; ++w) { x1 += red[(w * BN + t) * 2]; x2 += red[(w * BN + t) * 2 + 1]; }
-      a.bnr_partial[(long)(n0 + t) * ntiles + tile_id] = x1;
-      a.bnr_partial[((long)a.bnr_C + n0 + t) * ntiles + tile_id] = x2;
-    }
+    tile_stats_write<NT / 64, BN>(red, a.bnr_partial, a.bnr_C, n0, ntiles, tile_id, t);
   };
   if (a.pool_c0 > 0 && n0 < a.pool_c0) {
     // ---- 2x2 sum-pool into the half-resolution gradient of the upsampled source

@@ -8,13 +8,13 @@
 // which also permutes [k][(r,s),c] -> PyTorch OIHW.
 #include "common.h"
 #include "conv_route.h"
-#include "prof.h"
+#include "launch.h"
+#include "mma.h"
 
 namespace flair {
 
 // LDS panel = [rows = pixels][128 bytes of channels]; XOR on byte bits 5,6 keeps the 8 rows a
 // half-wave touches in one transposed read on distinct bank groups.
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // first-class 16-byte vector (keeps staging arrays in registers)
 
 __device__ __forceinline__ int wg_off(int row, int byte_in_row) {
   const int f = ((row >> 1) & 1) | (((row >> 3) & 1) << 1);
@@ -49,9 +49,6 @@ template <> struct WgFrag<bf16_t> {
     r.w = (unsigned)(unsigned short)hi[2] | ((unsigned)(unsigned short)hi[3] << 16);
     return r;
   }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
 };
 template <> struct WgFrag<float> {
   static constexpr int KSTEP = 16;  // 4 MFMAs of k=4
@@ -63,12 +60,6 @@ template <> struct WgFrag<float> {
     r.z = *reinterpret_cast<const unsigned*>(panel + wg_off(kb + 8 + g, cb + 4 * i));
     r.w = *reinterpret_cast<const unsigned*>(panel + wg_off(kb + 12 + g, cb + 4 * i));
     return r;
-  }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
   }
 };
 
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgKArgs ka) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) WgFrag<T>::mma(af[i], bfr[j], acc[i][j]);
+        for (int j = 0; j < TN; ++j) Mma<T>::run(af[i], bfr[j], acc[i][j]);
     }
     write_lds(cur ^ 1);
     __syncthreads();
@@ -314,21 +305,12 @@ size_t wgrad_workspace_bytes(int dtype, const WgradArgs& a) {
 template <typename T, int BMK, int BNN>
 static int wg_launch(const WgKArgs& ka, int splits, hipStream_t s) {
   using Cfg = WgCfg<T, BMK, BNN>;
-  auto kern = wgrad_kernel<T, BMK, BNN>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   dim3 grid(ka.Cout_pad / BMK, ka.Kpad / BNN, splits);
   const double M = (double)ka.a.N * ka.a.Hout * ka.a.Wout;
   const double flops = 2.0 * M * ka.a.Cout * ka.Kg;
   const double bytes = (M * ka.a.dy_ld + (double)ka.a.N * ka.a.Hin * ka.a.Win * (ka.a.C0 / (ka.a.up0 ? 4.0 : 1.0) + ka.a.C1)) * sizeof(T);
-  ProfScope ps(sizeof(T) == 2 ? (BMK == 128 ? "wgrad_bf16_128x128" : "wgrad_bf16_64x64") : "wgrad_f32_64x64", flops, bytes, s);
-  hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::SMEM, s, ka);
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<wgrad_kernel<T, BMK, BNN>>(sizeof(T) == 2 ? (BMK == 128 ? "wgrad_bf16_128x128" : "wgrad_bf16_64x64") : "wgrad_f32_64x64",
+                                                  ProfCost{flops, bytes}, grid, dim3(256), Cfg::SMEM, s, ka);
 }
 
 int launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s) {

@@ -5,10 +5,13 @@
 // X halo (10x34 pixels x CK channels) and the dY tile (256 pixels x CO channels) in LDS, and accumulates ALL
 // nine taps for its (CO x CK) block of the gradient in registers; the reduction index (pixels) is the MFMA K
 // dimension, fetched from the pixel-major LDS images with ds_read_b64_tr_b16 (f32: dword reads).
+// The halo goes to LDS through halo_stage.h (rows of WgHaloCfg::XSTRIDE bytes per pixel).
 // Each wave owns two tile rows (K split), partial accumulators are merged through LDS once per workgroup and
 // written as one fp32 slab per workgroup; wgrad_reduce_kernel (wgrad.hip) sums the slabs in a fixed order.
 #include "common.h"
-#include "prof.h"
+#include "halo_stage.h"
+#include "launch.h"
+#include "mma.h"
 #include "tune.h"
 #include "ops.h"
 
@@ -19,7 +22,6 @@ void launch_wgrad_reduce(const float* partial, float* dw, int splits, int Cout, 
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TH = 8, TW = 32, HH = TH + 2, HW_ = TW + 2, HPIX = HH * HW_;
 
 template <typename T> struct HFrag;
@@ -43,9 +45,6 @@ template <> struct HFrag<bf16_t> {
     r.w = (unsigned)(unsigned short)hi[2] | ((unsigned)(unsigned short)hi[3] << 16);
     return r;
   }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
 };
 template <> struct HFrag<float> {
   static constexpr int KSTEP = 16;
@@ -58,12 +57,6 @@ template <> struct HFrag<float> {
     r.z = *reinterpret_cast<const unsigned*>(img + (row0 + 8 + g) * STRIDE + cb + 4 * i);
     r.w = *reinterpret_cast<const unsigned*>(img + (row0 + 12 + g) * STRIDE + cb + 4 * i);
     return r;
-  }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
   }
 };
 
@@ -128,13 +121,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const WgHaloArgs a) 
 #pragma unroll
   for (int tp = 0; tp < 9; ++tp) acc[tp] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float lsc[CH], lsh[CH];   // this thread's chunk column of the lazy transform (256 % CPP == 0)
-  if (LZ && a.in_scale) {
-#pragma unroll
-    for (int e = 0; e < CH; ++e) {
-      lsc[e] = a.in_scale[cbase + (t % CPP) * CH + e];
-      lsh[e] = a.in_shift[cbase + (t % CPP) * CH + e];
-    }
-  }
+  if (LZ && a.in_scale) lazy_coef_load<T, CPP>(a.in_scale, a.in_shift, cbase, t, lsc, lsh);
 
   // The next tile's X halo and dY tile ride in registers while the current tile is multiplied (round 1 issued the loads
   // of a tile, waited for them and only then computed: with ~3 workgroups per CU the HBM latency of every tile was
@@ -145,10 +132,8 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const WgHaloArgs a) 
   unsigned xbitsA = 0, dbitsA = 0, xbitsB = 0, dbitsB = 0;
   auto load_tile = [&](int tile, u32x4 (&xr)[Cfg::XITEMS], u32x4 (&dr)[Cfg::DITEMS], unsigned& xbits, unsigned& dbits) {
     const bool tok = tile < a.ntiles;
-    const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0p = (trem % tiles_x) * TW;
+    int n, y0, x0p;
+    tile_decode<TW, TH>(tok ? tile : 0, tiles_x, tiles_y, n, y0, x0p);
     unsigned xb2 = 0, db2 = 0;
 #pragma unroll
     for (int k = 0; k < Cfg::XITEMS; ++k) {
@@ -184,15 +169,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const WgHaloArgs a) 
   }
   auto do_tile = [&](int tile, u32x4 (&xr)[Cfg::XITEMS], u32x4 (&dr)[Cfg::DITEMS], unsigned& xbits, unsigned& dbits) {
     __syncthreads();  // the previous tile's fragment reads are done
-#pragma unroll
-    for (int k = 0; k < Cfg::XITEMS; ++k) {
-      const int it = t + 256 * k;
-      if (it < HPIX * CPP) {
-        const int hp = it / CPP, ch = it - hp * CPP;
-        const u32x4 xv = (LZ && a.in_scale) ? chunk_bn_relu<T>(xr[k], lsc, lsh) : xr[k];
-        *reinterpret_cast<u32x4*>(xh + hp * Cfg::XSTRIDE + ch * 16) = xv & (0u - ((xbits >> k) & 1u));
-      }
-    }
+    halo_put<T, TW, TH, CPP, 256, Cfg::XITEMS, HaloRows<Cfg::XSTRIDE>, LZ>(xh, t, xr, xbits, a.in_scale != nullptr, lsc, lsh);
 #pragma unroll
     for (int k = 0; k < Cfg::DITEMS; ++k) {
       const int it = t + 256 * k;
@@ -222,7 +199,7 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const WgHaloArgs a) 
         for (int tp = 0; tp < 9; ++tp) {
           const int r = tp / 3, s = tp - 3 * r;
           const u32x4 bf = HFrag<T>::template load<Cfg::XSTRIDE>(xh, (y + r) * HW_ + xs + s, ci * 16 * (int)sizeof(T), lane);
-          HFrag<T>::mma(af, bf, acc[tp]);
+          Mma<T>::run(af, bf, acc[tp]);
         }
       }
     }
@@ -281,38 +258,16 @@ __global__ __launch_bounds__(256) void wgrad3x3_halo_kernel(const WgHaloArgs a) 
 
 template <typename T, int CK, int CO, bool LZ, bool DB = false>
 int launch_wg_halo_l(const WgHaloArgs& a, int nsplit, hipStream_t s) {
-  using Cfg = WgHaloCfg<T, CK, CO>;
-  auto kern = wgrad3x3_halo_kernel<T, CK, CO, LZ, DB>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  const int Cin = a.C0 + a.C1;
-  dim3 grid(nsplit, Cin / CK, a.Cout_pad / CO);
-  const double M = (double)a.N * a.H * a.W;
-  ProfScope ps(sizeof(T) == 2 ? (CK == 32 ? "wgrad3x3_halo_bf16_ck32" : "wgrad3x3_halo_bf16_ck16") : "wgrad3x3_halo_f32",
-               2.0 * M * a.Cout * 9.0 * Cin, (M * a.dy_ld + M * (a.C0 / (a.up0 ? 4.0 : 1.0) + a.C1)) * sizeof(T), s);
-  hipLaunchKernelGGL(kern, grid, dim3(256), Cfg::SMEM, s, a);
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  dim3 grid(nsplit, (a.C0 + a.C1) / CK, a.Cout_pad / CO);
+  return launch_kernel<wgrad3x3_halo_kernel<T, CK, CO, LZ, DB>>(
+      sizeof(T) == 2 ? (CK == 32 ? "wgrad3x3_halo_bf16_ck32" : "wgrad3x3_halo_bf16_ck16") : "wgrad3x3_halo_f32", wgrad3x3_prof_cost(a, sizeof(T)),
+      grid, dim3(256), WgHaloCfg<T, CK, CO>::SMEM, s, a);
 }
 
 // resident workgroups per CU of a variant (registers and LDS), asked from the runtime once; 3 without a device
 template <typename T, int CK, int CO, bool LZ>
 int wg_halo_per_cu() {
-  static const int per_cu = [] {
-    int nb = 0;
-    auto kern = wgrad3x3_halo_kernel<T, CK, CO, LZ>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, WgHaloCfg<T, CK, CO>::SMEM) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, WgHaloCfg<T, CK, CO>::SMEM) != hipSuccess || nb < 1) {
-      (void)hipGetLastError();
-      return 3;
-    }
-    return nb > 4 ? 4 : nb;
-  }();
-  return per_cu;
+  return resident_per_cu<wgrad3x3_halo_kernel<T, CK, CO, LZ>>(256, WgHaloCfg<T, CK, CO>::SMEM, 3, 4);
 }
 
 template <typename T>

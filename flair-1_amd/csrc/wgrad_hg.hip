@@ -11,7 +11,9 @@
 // summed in a fixed order by wgrad_reduce_kernel.
 #include "common.h"
 #include "conv_route.h"
-#include "prof.h"
+#include "halo_stage.h"
+#include "launch.h"
+#include "mma.h"
 #include "tune.h"
 
 namespace flair {
@@ -21,7 +23,6 @@ void launch_wgrad_reduce(const float* partial, float* dw, int splits, int Cout, 
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TW = 16, TH = 8, HW_ = TW + 2, HH = TH + 2, HPIX = HW_ * HH, TPIX = TW * TH;  // 180 halo / 128 tile pixels
 constexpr int NT = 512;   // 8 waves: 4 (output-channel groups) x 2 (input-channel halves) at 128 output channels per workgroup;
                           // 2 x 2 x 2 (tile-row halves, each with its own slab) at 64
@@ -42,9 +43,6 @@ template <> struct BFrag<bf16_t> {
     r.w = (unsigned)(unsigned short)hi[2] | ((unsigned)(unsigned short)hi[3] << 16);
     return r;
   }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
 };
 template <> struct BFrag<float> {
   static constexpr int KSTEP = 16;
@@ -57,12 +55,6 @@ template <> struct BFrag<float> {
     r.z = *reinterpret_cast<const unsigned*>(img + (row0 + 8 + g) * STRIDE + cb + 4 * i);
     r.w = *reinterpret_cast<const unsigned*>(img + (row0 + 12 + g) * STRIDE + cb + 4 * i);
     return r;
-  }
-  __device__ static __forceinline__ void mma(const u32x4& a, const u32x4& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.x), __uint_as_float(b.x), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.y), __uint_as_float(b.y), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.z), __uint_as_float(b.z), c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a.w), __uint_as_float(b.w), c, 0, 0, 0);
   }
 };
 
@@ -108,14 +100,9 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
   const int H = a.H, W = a.W;
   const int tiles_x = W / TW, tiles_y = H / TH;
   const int cbase = blockIdx.y * CK, kbase = blockIdx.z * CO;
-  const T* __restrict__ x0 = (const T*)a.x0;
-  const T* __restrict__ x1 = (const T*)a.x1;
   const T* __restrict__ dy = (const T*)a.dy;
   const bool use0 = cbase < a.C0;
-  const T* __restrict__ xb = use0 ? x0 : x1;
-  const int Hs = (use0 && a.up0) ? (H >> 1) : H, Ws = (use0 && a.up0) ? (W >> 1) : W, Cs = use0 ? a.C0 : a.C1;
-  const int sh = (use0 && a.up0) ? 1 : 0;
-  const int coff = use0 ? cbase : cbase - a.C0;
+  const HaloSrc<T> src = halo_src<T>(a.x0, a.x1, a.C0, a.C1, a.up0, H, W, cbase, use0);   // the X chunk of this workgroup
 
   f32x4_t acc[COT][CIT][9];
 #pragma unroll
@@ -131,14 +118,12 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
   const bool lz = LZ && use0 && a.in_scale != nullptr;
   // (the lazy transform's coefficients are re-read from L1 when a halo is staged: held in registers for the whole kernel they
   // were the 16 registers the pipelined multiply phase then spilled)
-  const float* __restrict__ lzs = lz ? a.in_scale + coff + (t & 7) * CH : nullptr;
-  const float* __restrict__ lzh = lz ? a.in_shift + coff + (t & 7) * CH : nullptr;
+  const float* __restrict__ lzs = lz ? a.in_scale + src.coff + (t & 7) * CH : nullptr;
+  const float* __restrict__ lzh = lz ? a.in_shift + src.coff + (t & 7) * CH : nullptr;
   auto load_tile = [&](int tile) {
     const bool tok = tile < a.ntiles;
-    const int tl = tok ? tile : 0;
-    const int n = tl / (tiles_x * tiles_y);
-    const int trem = tl - n * tiles_x * tiles_y;
-    const int y0 = (trem / tiles_x) * TH, x0p = (trem % tiles_x) * TW;
+    int n, y0, x0p;
+    tile_decode<TW, TH>(tok ? tile : 0, tiles_x, tiles_y, n, y0, x0p);
 #pragma unroll
     for (int k = 0; k < Cfg::XITEMS; ++k) {
       const int it = t + NT * k;
@@ -146,8 +131,8 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
       const int hy = hp / HW_, hx = hp - hy * HW_;
       const int iy = y0 - 1 + hy, ix = x0p - 1 + hx;
       const bool ok = tok && (it < HPIX * 8) && ((unsigned)iy < (unsigned)H) && ((unsigned)ix < (unsigned)W);
-      const unsigned off = ok ? (unsigned)(((n * Hs + (iy >> sh)) * Ws + (ix >> sh)) * Cs + coff + ch * CH) : 0u;
-      xr[k] = *reinterpret_cast<const u32x4*>(xb + off);
+      const unsigned off = ok ? (unsigned)(((n * src.Hs + (iy >> src.sh)) * src.Ws + (ix >> src.sh)) * src.Cs + src.coff + ch * CH) : 0u;
+      xr[k] = *reinterpret_cast<const u32x4*>(src.base + off);
       xm[k] = ok ? 0xffffffffu : 0u;
     }
 #pragma unroll
@@ -249,7 +234,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
 #pragma unroll
           for (int ci = 0; ci < CIT; ++ci)
 #pragma unroll
-            for (int co = 0; co < COT; ++co) BFrag<T>::mma(af[co], bfA[ci], acc[co][ci][tp]);
+            for (int co = 0; co < COT; ++co) Mma<T>::run(af[co], bfA[ci], acc[co][ci][tp]);
           __builtin_amdgcn_sched_barrier(0);
           if (tp + 1 < 9) {
             if (tp + 2 < 9) rdb(bfA, y, tp + 2);
@@ -257,7 +242,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
 #pragma unroll
             for (int ci = 0; ci < CIT; ++ci)
 #pragma unroll
-              for (int co = 0; co < COT; ++co) BFrag<T>::mma(af[co], bfB[ci], acc[co][ci][tp + 1]);
+              for (int co = 0; co < COT; ++co) Mma<T>::run(af[co], bfB[ci], acc[co][ci][tp + 1]);
             __builtin_amdgcn_sched_barrier(0);
           }
         }
@@ -291,7 +276,7 @@ __global__ __launch_bounds__(512) void wgrad3x3_big_kernel(const WgBigArgs a) {
           for (int ci = 0; ci < CIT; ++ci) {
             const u32x4 bf = BFrag<T>::template load<Cfg::XSTRIDE>(xh, (y + r) * HW_ + s, (wc * CIT + ci) * 16 * (int)sizeof(T), lane);
 #pragma unroll
-            for (int co = 0; co < COT; ++co) BFrag<T>::mma(af[co], bf, acc[co][ci][tp]);
+            for (int co = 0; co < COT; ++co) Mma<T>::run(af[co], bf, acc[co][ci][tp]);
           }
         }
       }
@@ -461,20 +446,9 @@ size_t wgrad_big_workspace_bytes(int dtype, const WgradArgs& a) {
 template <typename T, int KG, bool LZ>
 static int launch_big_l(const WgBigArgs& h, int nsplit, int Cin, hipStream_t s) {
   using Cfg = WgBigCfg<T, KG>;
-  auto kern = wgrad3x3_big_kernel<T, KG, LZ>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
   dim3 grid(nsplit, Cin / Cfg::CK, h.Cout / Cfg::CO);
-  const double M = (double)h.N * h.H * h.W;
-  ProfScope ps(sizeof(T) == 2 ? (KG == 1 ? "wgrad3x3_big_bf16" : "wgrad3x3_big_bf16_co64") : "wgrad3x3_big_f32", 2.0 * M * h.Cout * 9.0 * Cin,
-               (M * h.dy_ld + M * (h.C0 / (h.up0 ? 4.0 : 1.0) + h.C1)) * sizeof(T), s);
-  hipLaunchKernelGGL(kern, grid, dim3(NT), Cfg::SMEM, s, h);
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  return launch_kernel<wgrad3x3_big_kernel<T, KG, LZ>>(sizeof(T) == 2 ? (KG == 1 ? "wgrad3x3_big_bf16" : "wgrad3x3_big_bf16_co64") : "wgrad3x3_big_f32",
+                                                       wgrad3x3_prof_cost(h, sizeof(T)), grid, dim3(NT), Cfg::SMEM, s, h);
 }
 
 template <typename T, int KG>

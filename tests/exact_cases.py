@@ -505,6 +505,8 @@ FUSED_CASES = [
     FusedCase("lazy_p32to32_640tiles", "lazy", 5, 128, 256, 32, 32, density=0.25, tune=_CAP, kernel="halo_p", loops=True),
     FusedCase("lazy_hg64to64_nwork9", "lazy", 1, 24, 96, 64, 64, density=0.25, kernel="hg_n64"),
     FusedCase("lazy_hg128to128_nwork15", "lazy", 1, 40, 48, 128, 128, density=0.25, kernel="hg_n128"),
+    # two chunks of 32 channels into one 32-wide block: the plain small-channel kernel (the halo-GEMM has no lazy 32-wide flavour)
+    FusedCase("lazy_halo64to32_1tile", "lazy", 1, 8, 32, 64, 32, density=0.25, kernel="halo"),
     FusedCase("wlazy_p16to16_small", "wgrad_lazy", 1, 16, 64, 16, 16, kernel="halo"),
     FusedCase("wlazy_p32to16_23tiles", "wgrad_lazy", 1, 184, 32, 32, 16, tune=(("FLAIR_WGH_WGS", 10),), kernel="halo", loops=True),
     FusedCase("wlazy_big64to64_15tiles", "wgrad_lazy", 1, 40, 48, 64, 64, tune=(("FLAIR_WG_CUS_OP", 4),),
