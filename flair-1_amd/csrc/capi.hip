@@ -56,6 +56,7 @@ const char* flair_strerror(int code) {
     case -13: return "internal side stream: event record / wait failed";
     case -14: return "UperNet-Swin tile size: height and width must be multiples of 32 from 64 to 2048";
     case -15: return "flair_unet_want_ce: needs an eval-mode forward without fp32 logits and without a flair_unet_want_preds request";
+    case -16: return "flair_unet_want_rowvec: the bottleneck row vector is added in eval-mode forwards only (training takes the split path)";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -103,6 +104,11 @@ int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, cons
   r.labels = labels; r.kind = label_kind; r.weight = class_weight; r.loss = loss; r.preds = preds_u8;
   r.confmat = (long long*)confmat; r.ws = (float*)ce_workspace;
   h->net.want_ce(r);
+  return 0;
+}
+int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32) {
+  if (!h || !rows_f32) return -1;
+  h->net.want_rowvec(rows_f32);
   return 0;
 }
 int flair_unet_reuse_constants(flair_unet_t* h, int on) {
@@ -336,6 +342,11 @@ int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void*
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream) {
   if (!x || !v) return -1;
   return add_rowvec_nchw(x, v, N, C, H, W, (hipStream_t)stream);
+}
+int flair_add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, void* stream) {
+  if (!x || !v) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return add_rowvec_nhwc(dtype, x, v, N, H, W, C, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------ operators

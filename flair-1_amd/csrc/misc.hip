@@ -468,6 +468,22 @@ __global__ void add_rowvec_kernel(float* __restrict__ x, const float* __restrict
   }
 }
 
+// The same add on the network's own NHWC tensor, in place: x[n][h][w][c] += v[n][h].  A row (n, h) is W * C contiguous elements,
+// so the value of a 16-byte chunk is v[chunk / chunks per row].  The sum is taken in fp32 and rounded to T once, by the conversion
+// nchw_to_nhwc_kernel uses — bit for bit what the split path's fp32 NCHW export, add_rowvec_kernel and re-import leave.
+template <typename T>
+__global__ void add_rowvec_nhwc_kernel(T* __restrict__ x, const float* __restrict__ v, long nchunks, int row_chunks) {
+  constexpr int CH = Elem<T>::CH;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nchunks; i += (long)gridDim.x * blockDim.x) {
+    const float a = v[i / row_chunks];
+    float f[CH];
+    chunk_to_f<T>(*reinterpret_cast<const uint4*>(x + i * CH), f);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) f[e] += a;
+    *reinterpret_cast<uint4*>(x + i * CH) = f_to_chunk<T>(f);
+  }
+}
+
 template <typename T>
 __global__ void ew_add_kernel(T* __restrict__ dst, const T* __restrict__ src, long nchunks) {
   constexpr int CH = Elem<T>::CH;
@@ -590,6 +606,21 @@ int sgd_step(float* params, const float* grads, long n, float lr, hipStream_t s)
 
 int add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, hipStream_t s) {
   hipLaunchKernelGGL(add_rowvec_kernel, dim3(ew_blocks((long)N * C * H * W)), dim3(256), 0, s, x, v, N, C, H, W);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+int add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, hipStream_t s) {
+  if (N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || ((uintptr_t)x & 15) || ((uintptr_t)v & 3)) return -2;
+  const int ch = dtype == DT_F32 ? 4 : 8;
+  const long row_chunks = (long)W * (C / ch);
+  if (row_chunks > 0x7fffffffL) return -2;
+  const long nchunks = (long)N * H * row_chunks;
+  ProfScope ps("add_rowvec_nhwc", 0.0, (double)nchunks * 32.0, s);
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(add_rowvec_nhwc_kernel<float>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (float*)x, v, nchunks, (int)row_chunks);
+  else
+    hipLaunchKernelGGL(add_rowvec_nhwc_kernel<bf16_t>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (bf16_t*)x, v, nchunks, (int)row_chunks);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }

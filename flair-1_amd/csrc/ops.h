@@ -62,6 +62,8 @@ struct PackTable {
 int pack_weights_all(int dtype, const float* params, void* base, const PackTable& tb, hipStream_t s);
 int sgd_step(float* params, const float* grads, long n, float lr, hipStream_t s);
 int add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, hipStream_t s);
+// x[n][h][w][c] += v[n*H + h] on an NHWC tensor of the compute dtype, in place (C a multiple of 8, x 16-byte aligned)
+int add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, hipStream_t s);
 int ew_add(int dtype, void* dst, const void* src, long n, hipStream_t s);
 int fill_zero(void* p, size_t bytes, hipStream_t s);
 int fill_f32(float* p, long n, float v, hipStream_t s);

@@ -114,7 +114,9 @@ class UNet {
   // every entry point other than forward() lays the arena out differently (the split path re-imports five feature tensors
   // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone, and so are pending
   // one-shot requests
-  void invalidate_reuse() { last_valid_ = false; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); }
+  void invalidate_reuse() {
+    last_valid_ = false; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); rowvec_req_ = nullptr;
+  }
   // the next forward without fp32 logits writes argmax predictions [B][H][W] uint8 here (one-shot, like reuse_constants)
   void want_preds(unsigned char* p, float* maxprob) { preds_req_ = p; maxprob_req_ = maxprob; }
   // the next eval-mode forward without fp32 logits evaluates the per-pixel head of step() on its logits (one-shot): weighted CE
@@ -124,6 +126,10 @@ class UNet {
     float* loss = nullptr; unsigned char* preds = nullptr; long long* confmat = nullptr; float* ws = nullptr;
   };
   void want_ce(const CeReq& r) { ce_req_ = r; }
+  // the next eval-mode forward adds v (fp32 [B][H/32], device) to the bottleneck feature f_[5] between the encoder and the decoder
+  // (one-shot): element [b][h][w][c] += v[b][h], the metadata fusion of model.py:59-60.  In eval mode every unit materialises its
+  // output and f_[5] is read by decoder block 0 alone, so the add happens in place; the arena layout does not change
+  void want_rowvec(const float* v) { rowvec_req_ = v; }
   void* last_dlogits_nhwc() const { return dl_nhwc_; }
   const void* logits_nhwc() const { return logits_nhwc_; }
   int head_ld() const { return convs.back().Cout_p; }
@@ -166,6 +172,7 @@ class UNet {
   unsigned char* preds_req_ = nullptr;
   float* maxprob_req_ = nullptr;
   CeReq ce_req_;
+  const float* rowvec_req_ = nullptr;
   bool side_init();
   hipStream_t wgrad_stream();     // forks the side stream behind everything queued on s_ so far
   int side_cus() const;           // WgradArgs::cus of a launch on the side stream

@@ -474,9 +474,12 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   float* const maxprob_now = maxprob_req_;
   const bool reuse_now = reuse_req_;
   const CeReq ce_now = ce_req_;
-  preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false; ce_req_ = CeReq();
+  const float* const rowvec_now = rowvec_req_;
+  preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false; ce_req_ = CeReq(); rowvec_req_ = nullptr;
   // two heads asked of one forward, or the CE head of a forward that is not an eval-mode one without fp32 logits
   if (ce_now.labels && (preds_now || training || logits_nchw)) return -15;
+  // the bottleneck row vector of a training forward: its backward is not built (the gradient that reaches f_[5] is stored masked)
+  if (rowvec_now && training) return -16;
   if ((H % 32) || (W % 32)) return -10;
   reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && B == last_B_ && H == last_H_ && W == last_W_;
   preds_req_ = preds_now; maxprob_req_ = maxprob_now; ce_req_ = ce_now;   // consumed by head_fwd_impl below
@@ -487,6 +490,8 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   lazy_max_c_ = lazy_env >= 2 ? 32 : 16;
   if (!reuse_) pack_forward_weights();
   encoder_fwd_impl(x_nchw);
+  // metadata fusion (model.py:59-60): f_[5] is the materialised output of layer4's last block, read by decoder block 0 only
+  if (rowvec_now) RUN(add_rowvec_nhwc(dtype, f_[5].p, rowvec_now, f_[5].N, f_[5].H, f_[5].W, f_[5].C, s_));
   decoder_fwd_impl();
   head_fwd_impl(logits_nchw);
   fwd_top_ = top_;

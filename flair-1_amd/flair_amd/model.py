@@ -6,16 +6,22 @@ Same constructor argument (the YAML config dict), same attributes (``seg_model``
   * the reference's ``NameError`` at model.py:32 (bare ``model_provider``) is fixed to ``self.model_provider``;
   * the metadata broadcast ``x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16)`` + ``torch.add``
     (model.py:59-60; element [b,c,h,w] += x_enc[b,h]) runs as one in-place HIP kernel on a copy of feats[-1]
-    instead of materialising the (B,512,16,16) repeat;
+    instead of materialising the (B,512,16,16) repeat; with an eval-mode ``seg_model`` the add happens inside ONE native forward
+    (``Unet.eval_logits(x, bottleneck_rows=x_enc)``, flair_unet_want_rowvec) on the executor's own NHWC bottleneck — no fp32 NCHW
+    round trip of the features, constants reused, HIP-graph replay at small batches; FLAIR_META_FUSE=0 (read per call) keeps the
+    three-call split path, which a training-mode ``seg_model`` always takes;
   * the HuggingFace provider branch (model.py:43-50,66-68) builds SegFormer-MiT and 3-channel UperNet-Swin natively
     (inference only); other names raise.
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import ops
 from .unet import create_model
 
 
@@ -143,13 +149,24 @@ class FLAIR_ModelFactory(nn.Module):
                 self.seg_model = SegformerForSemanticSegmentation(num_channels=n_channels, num_labels=n_classes,
                                                                   compute_dtype=compute_dtype, **kw)
 
+    _Q4 = "metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)"
+
+    def _meta_fused(self):
+        """Metadata branch of an eval-mode U-Net: the add rides inside the single native forward (FLAIR_META_FUSE=0: split path)."""
+        return not self.seg_model.training and os.environ.get("FLAIR_META_FUSE", "1") != "0"
+
     def forward(self, x, met=None):
         if self.use_metadata == True and self.model_provider == "SegmentationModelsPytorch":  # noqa: E712
+            if self._meta_fused():
+                x_enc = self.enc(met)
+                if tuple(x.shape[-2:]) != (512, 512):   # (quirk Q4, as below)
+                    raise RuntimeError(self._Q4)
+                return self.seg_model.eval_logits(x, bottleneck_rows=x_enc)
             feats = self.seg_model.encoder(x)
             x_enc = self.enc(met)
             if feats[-1].shape[1:] != (512, 16, 16):
                 # the reference hard-codes repeat(1,512,1,16): only 512x512 tiles are valid (quirk Q4)
-                raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+                raise RuntimeError(self._Q4)
             feats[-1] = _AddRowVec.apply(feats[-1], x_enc)
             output = self.seg_model.decoder(*feats)
             output = self.seg_model.segmentation_head(output)
@@ -158,3 +175,23 @@ class FLAIR_ModelFactory(nn.Module):
         else:
             output = self.seg_model(x)
         return output
+
+    @torch.no_grad()
+    def predict_classes(self, x, met=None, want_prob=False):
+        """argmax(softmax(forward(x, met))) as uint8 (B,H,W) and, with ``want_prob``, the winner's fp32 probability — what
+        ``predict_step`` (task_module.py:206-213) and zone_detect's 'argmax' output compute.  The U-Net takes both out of its head
+        convolution's epilogue (``Unet.predict_classes``), with metadata through the same single native call; the MetadataMLP
+        runs without dropout, as Lightning's ``model.eval()`` makes the reference's.  Other models: the separate kernel over
+        the logits."""
+        if self.model_provider == "SegmentationModelsPytorch":
+            if self.use_metadata != True:  # noqa: E712
+                return self.seg_model.predict_classes(x, want_prob=want_prob)
+            if met is None:
+                raise ValueError("this model was built with use_metadata: predict_classes needs the (B,45) metadata vectors")
+            if os.environ.get("FLAIR_META_FUSE", "1") != "0":
+                x_enc = self.enc(met, masks=None)
+                if tuple(x.shape[-2:]) != (512, 512):
+                    raise RuntimeError(self._Q4)
+                return self.seg_model.predict_classes(x, want_prob=want_prob, bottleneck_rows=x_enc)
+        logits = self.forward(x, met)
+        return ops.softmax_argmax(logits.detach().float().contiguous(), want="u8", want_maxprob=want_prob)

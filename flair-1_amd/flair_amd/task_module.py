@@ -179,6 +179,14 @@ class segmentation_task_predict(_Base):
         return preds.flatten(start_dim=1), tg.flatten(start_dim=1)
 
     def predict_step(self, batch, batch_idx, dataloader_idx=0):
+        fast = getattr(self.model, "predict_classes", None)
+        if fast is not None and not getattr(self.model, "training", True):
+            # an eval-mode model that hands out argmax(softmax(logits)) itself (the U-Net: from its head convolution's epilogue,
+            # the logits are never written; with metadata in the same native call)
+            with torch.no_grad():
+                preds = fast(batch["img"], batch["mtd"]) if self.use_metadata == True else fast(batch["img"])  # noqa: E712
+            batch["preds"] = preds.to(torch.int64)
+            return batch
         if self.use_metadata == True:  # noqa: E712
             logits = self.forward(batch["img"], batch["mtd"])
         else:

@@ -83,8 +83,10 @@ class SegTrainer:
     """Owns the flat gradient buffer, the fused head outputs and the RCCL exchange for one rank."""
 
     def __init__(self, model, lr, class_weight=None, group=None, overlap=True, min_bucket_elems=1 << 18,
-                 force_exchange=False, broadcast_buffers=True, class_names=None):
+                 force_exchange=False, broadcast_buffers=True, class_names=None, metadata_encoder=None):
         self.model = model
+        # a MetadataMLP (BASELINE config 4): validate_step / predict add its encoding to the bottleneck inside their one native call
+        self.metadata_encoder = metadata_encoder
         self.class_names = None if class_names is None else [str(n) for n in class_names]
         self.sync_buffers = bool(broadcast_buffers)   # torch DDP's broadcast_buffers (tasks.py:83-88 keeps the default, True)
         self._src0 = 0 if group is None else dist.get_global_rank(group, 0)
@@ -180,32 +182,46 @@ class SegTrainer:
         m._native_writes = m.__dict__.get("_native_writes", 0) + 1   # parameters changed behind torch's version counter
         return self.loss
 
+    def _meta_rows(self, img, mtd):
+        """x_enc of model.py:58 for an eval-mode forward: the MetadataMLP without dropout (masks=None), as Lightning's
+        ``model.eval()`` makes the reference's; None without metadata."""
+        if mtd is None:
+            return None
+        if self.metadata_encoder is None:
+            raise ValueError("SegTrainer was built without a metadata_encoder: pass the MetadataMLP to take metadata")
+        if tuple(img.shape[-2:]) != (512, 512):   # the reference hard-codes repeat(1,512,1,16) (quirk Q4)
+            raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+        return self.metadata_encoder(mtd.to(self.grads.device), masks=None).detach()
+
     @torch.no_grad()
-    def predict(self, img):
-        """predict_step of the reference (task_module.py:206-213): (B,H,W) uint8 argmax(softmax(logits))."""
+    def predict(self, img, mtd=None):
+        """predict_step of the reference (task_module.py:206-213): (B,H,W) uint8 argmax(softmax(logits)); with ``mtd`` ((B,45)
+        metadata vectors) the logits of the metadata branch (model.py:57-62)."""
         m = self.model
         B, _, H, W = img.shape
         with torch.cuda.device(self.grads.device):
-            return self._predict(m, img, B, H, W)
+            return self._predict(m, img, B, H, W, self._meta_rows(img, mtd))
 
-    def _predict(self, m, img, B, H, W):
+    def _predict(self, m, img, B, H, W, rows=None):
         preds = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)
         # the argmax comes out of the head convolution's epilogue (or, for shapes its persistent kernel does not take, from the
         # separate pass over the NHWC logits inside the same native call): the logits never reach HBM
-        m._c_forward(img, training=False, want_logits=False, preds=preds)
+        m._c_forward(img, training=False, want_logits=False, preds=preds, rows=rows)
         return preds
 
     @torch.no_grad()
-    def validate_step(self, img, labels):
+    def validate_step(self, img, labels, mtd=None):
         """validation_step of the reference (task_module.py:104-109) on the eval handle and the eval workspace, with the
         running statistics whatever ``model.training`` says: one native call, the loss term, the argmax and the confusion
         matrix increment come out of the head convolution's epilogue (flair_unet_want_ce).  img / labels as for train_step.
         Returns this batch's device scalar loss (no host sync), adds it to the running mean and the batch's confusion matrix to
-        ``val_confmat``; the predictions stay in ``_val_preds``.  No parameter, buffer or training activation is touched."""
+        ``val_confmat``; the predictions stay in ``_val_preds``.  No parameter, buffer or training activation is touched.
+        ``mtd``: (B,45) metadata vectors, encoded by ``metadata_encoder`` without dropout and added to the bottleneck inside the
+        same native call (flair_unet_want_rowvec)."""
         with torch.cuda.device(self.grads.device):
-            return self._validate_step(img, labels)
+            return self._validate_step(img, labels, self._meta_rows(img, mtd))
 
-    def _validate_step(self, img, labels):
+    def _validate_step(self, img, labels, rows=None):
         m = self.model
         B, _, H, W = img.shape
         dev = self.grads.device
@@ -217,7 +233,7 @@ class SegTrainer:
         loss = torch.empty((), dtype=torch.float32, device=dev)   # (a tensor of its own: the caller may keep every batch's)
         m._c_forward(img, training=False, want_logits=False,
                      ce=(L.ptr(labels), kind, L.ptr(self.class_weight), L.ptr(loss), L.ptr(self._val_preds),
-                         L.ptr(self.val_confmat), L.ptr(self._val_ws)))
+                         L.ptr(self.val_confmat), L.ptr(self._val_ws)), rows=rows)
         self.val_loss_sum += loss
         self.val_count += 1
         return loss

@@ -437,23 +437,28 @@ class Unet(nn.Module):
     # shape, workspace and requested outputs — is captured into a HIP graph and replayed from then on (FLAIR_EVAL_GRAPH=0: never)
     _GRAPH_MAX_PIXELS = 4 * 512 * 512
 
-    def _eval_graph(self, gkey, x, want_logits, preds, prob, ws, h):
+    def _eval_graph(self, gkey, x, want_logits, preds, prob, ws, h, rows=None):
         ent = self._eval_graphs.get(gkey)
         if ent is None:
             B, _, H, W = x.shape
             ent = {"x": x.clone(), "logits": torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None,
-                   "preds": None if preds is None else torch.empty_like(preds), "prob": None if prob is None else torch.empty_like(prob)}
+                   "preds": None if preds is None else torch.empty_like(preds), "prob": None if prob is None else torch.empty_like(prob),
+                   "rows": None if rows is None else rows.clone()}
             g = torch.cuda.CUDAGraph()
             l = L.lib()
             with torch.cuda.graph(g):
                 L.check(l.flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
                 if preds is not None:
                     L.check(l.flair_unet_want_preds(h, L.ptr(ent["preds"]), L.ptr(ent["prob"])), "flair_unet_want_preds")
+                if rows is not None:
+                    L.check(l.flair_unet_want_rowvec(h, L.ptr(ent["rows"])), "flair_unet_want_rowvec")
                 L.check(l.flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(ent["x"]), L.ptr(ent["logits"]), B, H, W, 0,
                                              L.ptr(ws), ws.numel(), L.stream()), "flair_unet_forward")
             ent["graph"] = g
             self._eval_graphs[gkey] = ent
         ent["x"].copy_(x)       # (capture records, it does not run: the first use replays too)
+        if rows is not None:
+            ent["rows"].copy_(rows)
         ent["graph"].replay()
         if preds is not None:
             preds.copy_(ent["preds"])
@@ -462,14 +467,25 @@ class Unet(nn.Module):
         return None if ent["logits"] is None else ent["logits"].clone()
 
     @_on_model_device
-    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None):
+    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None, rows=None):
         """want_logits=False (fused trainer): the head's output stays in the workspace as NHWC rows of the compute dtype
         (flair_unet_logits_nhwc) and no fp32 NCHW tensor is produced; returns None.  preds / prob (eval mode, no logits): uint8
         argmax and its fp32 probability from the head convolution's epilogue (flair_unet_want_preds).  ce (eval mode, no
         logits): the arguments of flair_unet_want_ce behind the handle — the validation head in the same call; such a forward
-        always runs eagerly (never captured, not counted towards the captures of the plain paths)."""
+        always runs eagerly (never captured, not counted towards the captures of the plain paths).  rows (eval mode only): fp32
+        (B, H/32) added to the bottleneck feature between encoder and decoder, element [b,c,h,w] += rows[b,h]
+        (flair_unet_want_rowvec) — the metadata fusion of model.py:57-62 inside the one native call; combines with all of the above."""
         x = self._prep(x)
         B, _, H, W = x.shape
+        if rows is not None:
+            if training:
+                raise RuntimeError("flair_amd.Unet: bottleneck rows are added in eval-mode forwards only; a training-mode model "
+                                   "takes the split path (encoder, add, decoder, segmentation_head)")
+            if not rows.is_cuda or rows.device != x.device:
+                raise L.FlairHipError("flair_amd.Unet: bottleneck rows must live on the input's HIP device")
+            if tuple(rows.shape) != (B, H // 32):
+                raise RuntimeError(f"bottleneck rows must be (B, H/32) = ({B}, {H // 32}), got {tuple(rows.shape)}")
+            rows = rows.detach().to(torch.float32).contiguous()
         ws = self._workspace(B, H, W, training)
         h = self._hh(training)
         if not training:
@@ -481,16 +497,18 @@ class Unet(nn.Module):
                 self._eval_hits = {}
             elif (ce is None and os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0" and B * H * W <= self._GRAPH_MAX_PIXELS
                   and not torch.cuda.is_current_stream_capturing()):
-                gkey = (want_logits, preds is not None, prob is not None)
+                gkey = (want_logits, preds is not None, prob is not None, rows is not None)
                 hits = self.__dict__.setdefault("_eval_hits", {})
                 hits[gkey] = hits.get(gkey, 0) + 1
                 if gkey in graphs or hits[gkey] >= 2:   # (the first repeat ran eagerly with reuse: every kernel's one-time set-up is done)
-                    return self._eval_graph(gkey, x, want_logits, preds, prob, ws, h)
+                    return self._eval_graph(gkey, x, want_logits, preds, prob, ws, h, rows)
         logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
         if preds is not None:
             L.check(L.lib().flair_unet_want_preds(h, L.ptr(preds), L.ptr(prob)), "flair_unet_want_preds")
         if ce is not None:
             L.check(L.lib().flair_unet_want_ce(h, *ce), "flair_unet_want_ce")
+        if rows is not None:
+            L.check(L.lib().flair_unet_want_rowvec(h, L.ptr(rows)), "flair_unet_want_rowvec")
         if not training:
             # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
             # BatchNorm-coefficient launches.  torch bumps a tensor's _version on every in-place write (optimizers,
@@ -665,16 +683,26 @@ class Unet(nn.Module):
 
     @torch.no_grad()
     @_on_model_device
-    def predict_classes(self, x, want_prob=False):
+    def predict_classes(self, x, want_prob=False, bottleneck_rows=None):
         """Eval-mode forward whose head convolution returns the argmax class per pixel (uint8 (B,H,W)) and, with ``want_prob``,
         that class's softmax probability (fp32 (B,H,W)) from its epilogue — what ``convert(softmax(model(x)), 'argmax')`` of
-        zone_detect (dataset.py:23-30) and ``predict_step`` (task_module.py:206-213) compute — without writing the logits."""
-        x = self._prep(x)
-        B, _, H, W = x.shape
+        zone_detect (dataset.py:23-30) and ``predict_step`` (task_module.py:206-213) compute — without writing the logits.
+        ``bottleneck_rows``: fp32 (B, H/32), added to the bottleneck feature as ``feats[-1][b,c,h,w] += rows[b,h]`` (the
+        metadata fusion of model.py:57-62) inside the same native call."""
+        if not x.is_cuda:
+            raise L.FlairHipError("flair_amd.Unet needs HIP tensors (no CPU fallback)")
+        B, H, W = x.shape[0], x.shape[-2], x.shape[-1]   # (_c_forward checks and prepares the input: once per call, it is host time)
         preds = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
         prob = torch.empty(B, H, W, dtype=torch.float32, device=x.device) if want_prob else None
-        self._c_forward(x, training=False, want_logits=False, preds=preds, prob=prob)
+        self._c_forward(x, training=False, want_logits=False, preds=preds, prob=prob, rows=bottleneck_rows)
         return (preds, prob) if want_prob else preds
+
+    @torch.no_grad()
+    def eval_logits(self, x, bottleneck_rows=None):
+        """Eval-mode forward (running statistics, whatever ``self.training`` says) -> fp32 (B,classes,H,W) logits, with
+        ``bottleneck_rows`` as for ``predict_classes``: encoder, metadata add, decoder and head of model.py:57-62 in one native
+        call.  Builds no autograd graph."""
+        return self._c_forward(x, training=False, rows=bottleneck_rows)
 
     def __del__(self):
         try:

@@ -78,6 +78,12 @@ int flair_unet_want_preds(flair_unet_t* h, uint8_t* preds_u8, float* maxprob_f32
 int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, const float* class_weight, float* loss,
                        uint8_t* preds_u8 /* optional */, int64_t* confmat /* optional */,
                        void* ce_workspace /* flair_ce_workspace_bytes(B, H, W) */);
+/* One-shot: the next flair_unet_forward with training = 0 adds rows_f32 (device, fp32 (B, H/32)) to the bottleneck feature between the
+ * encoder and the decoder, element [b][c][h][w] += rows[b][h] — the metadata fusion of model.py:57-62 (x_enc of MetadataMLP; at 512 x 512
+ * tiles H/32 = 16 = its width) without leaving the fused forward.  Combines with flair_unet_reuse_constants, fp32 logits,
+ * flair_unet_want_preds and flair_unet_want_ce.  A training forward that meets the request is refused (-16); the request is dropped by
+ * any forward. */
+int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32);
 
 /* seg_model.encoder(x) / .decoder(*feats) / .segmentation_head(t) — the metadata path model.py:57-62.
  * feats[i] = feature i+1 of the encoder, NCHW fp32: (B,64,H/2,W/2) ... (B,512,H/32,W/32). */
@@ -248,6 +254,9 @@ int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raste
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream);
+/* The same add, in place, on an NHWC tensor of the compute dtype (the layout the executor keeps its features in):
+ * x (N,H,W,C) += v (N,H) fp32, summed in fp32 and rounded to `dtype` once.  C must be a multiple of 8 and x 16-byte aligned (-2). */
+int flair_add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Operator-level entry points (unit parity tests; same kernels the model object launches).
