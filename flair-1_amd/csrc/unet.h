@@ -108,14 +108,14 @@ class UNet {
                        size_t ws_bytes, hipStream_t s);
 
   // Inference with constant weights: when the caller vouches that parameters and buffers are unchanged since the previous
-  // eval-mode forward on this handle, the next eval-mode forward with the same arena and shape skips the weight pack and
+  // eval-mode forward on this handle, the next eval-mode forward with the same arena, shape, params and buffers addresses skips the weight pack and
   // the 46 BatchNorm-coefficient launches (both still sit in the arena at the same offsets).  One-shot: cleared by forward.
   void reuse_constants(bool on) { reuse_req_ = on; }
   // every entry point other than forward() lays the arena out differently (the split path re-imports five feature tensors
   // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone, and so are pending
   // one-shot requests
   void invalidate_reuse() {
-    last_valid_ = false; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); rowvec_req_ = nullptr;
+    last_valid_ = false; last_params_ = nullptr; last_buffers_ = nullptr; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); rowvec_req_ = nullptr;
   }
   // the next forward without fp32 logits writes argmax predictions [B][H][W] uint8 here (one-shot, like reuse_constants)
   void want_preds(unsigned char* p, float* maxprob) { preds_req_ = p; maxprob_req_ = maxprob; }
@@ -158,6 +158,8 @@ class UNet {
   bool packed_d_ = false;
   bool reuse_req_ = false, reuse_ = false, last_valid_ = false;
   const void* last_ws_ = nullptr;
+  const void* last_params_ = nullptr;   // the flat buffers the packed weights / BatchNorm coefficients in the arena came from
+  const void* last_buffers_ = nullptr;
   int last_B_ = 0, last_H_ = 0, last_W_ = 0;
   bool lazy_ok_ = false;
   int lazy_max_c_ = 16;    // widest unit that hands out a lazy activation (FLAIR_LAZY_BN=2: 32)

@@ -481,7 +481,9 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   // the bottleneck row vector of a training forward: its backward is not built (the gradient that reaches f_[5] is stored masked)
   if (rowvec_now && training) return -16;
   if ((H % 32) || (W % 32)) return -10;
-  reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && B == last_B_ && H == last_H_ && W == last_W_;
+  // (the caller vouches for the CONTENTS of params / buffers; other addresses are other tensors, whatever it believes)
+  reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && params == last_params_ && buffers == last_buffers_ &&
+           B == last_B_ && H == last_H_ && W == last_W_;
   preds_req_ = preds_now; maxprob_req_ = maxprob_now; ce_req_ = ce_now;   // consumed by head_fwd_impl below
   begin(ws, ws_bytes, s, false);
   fwd_common_begin(params, buffers, B, H, W, training);
@@ -497,7 +499,7 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   fwd_top_ = top_;
   reuse_ = false;
   last_valid_ = !training && !err_;   // (a training forward lays the arena out differently)
-  last_ws_ = ws; last_B_ = B; last_H_ = H; last_W_ = W;
+  last_ws_ = ws; last_params_ = params; last_buffers_ = buffers; last_B_ = B; last_H_ = H; last_W_ = W;
   return err_;
 }
 

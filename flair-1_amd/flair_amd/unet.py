@@ -18,6 +18,7 @@ bucketed RCCL all-reduce of ``flair_amd.train`` possible.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 import os
@@ -353,6 +354,34 @@ class Unet(nn.Module):
                 flat_n[i] = m.num_batches_tracked.to(dev)
                 m.num_batches_tracked.data = flat_n[i]
         self._flat_p, self._flat_b, self._flat_n = flat_p, flat_b, flat_n
+        # new buffers repeat the version counters of the ones they replace (one copy_ per tensor) and `.data =` moves none:
+        # what was packed from, or captured with, the old addresses goes here, not by a key that may compare equal
+        self._drop_eval_cache()
+
+    def _drop_eval_cache(self):
+        """Forget what eval forwards keep between calls: the key that vouches for the packed weights and BatchNorm coefficients
+        in the eval workspace (no key: the next eval forward packs again) and every HIP graph captured under it."""
+        self._eval_key = None
+        self._eval_graphs = {}
+        self._eval_hits = {}
+        self._eval_nocapture = set()
+
+    def weights_changed(self):
+        """Announce a change of parameters or running statistics that torch's version counters cannot see — an in-place write
+        through ``.data`` (``p.data.mul_(...)``) or through a raw pointer: the next eval forward packs the weights again and
+        captures no graph before its third identical call.  Every other writer (in-place torch ops, ``load_state_dict``,
+        ``.data =`` / ``.to()`` / ``.cpu()`` rebinds, training forwards, the fused trainer) is noticed without it."""
+        self._drop_eval_cache()
+
+    def _eval_cache_key(self, B, H, W, ws):
+        """What must be unchanged for the constants in the eval workspace, and a graph captured over them, to be still valid.
+        Versions: torch bumps a tensor's _version on every in-place write (optimizers, load_state_dict); the parameters and
+        buffers are .data views of the flat buffers and each carries its own counter.  _native_writes: native writers (training
+        forwards: running statistics; the fused trainer's SGD).  Addresses of the flat buffers: a rebuilt buffer repeats its
+        predecessor's versions, and a captured graph has the addresses baked in."""
+        ver = sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers())
+        return (ver, self._flat_p._version, self._flat_b._version, self._flat_p.data_ptr(), self._flat_b.data_ptr(),
+                self.__dict__.get("_native_writes", 0), B, H, W, ws.data_ptr())
 
     def flat_parameters(self):
         self.flatten_()
@@ -436,6 +465,7 @@ class Unet(nn.Module):
     # batch size 1, data_module.py:100, ran at 870 tiles/s against 10 000 at batch 32): the third identical call — same weights,
     # shape, workspace and requested outputs — is captured into a HIP graph and replayed from then on (FLAIR_EVAL_GRAPH=0: never)
     _GRAPH_MAX_PIXELS = 4 * 512 * 512
+    _NOT_CAPTURED = object()
 
     def _eval_graph(self, gkey, x, want_logits, preds, prob, ws, h, rows=None):
         ent = self._eval_graphs.get(gkey)
@@ -446,14 +476,23 @@ class Unet(nn.Module):
                    "rows": None if rows is None else rows.clone()}
             g = torch.cuda.CUDAGraph()
             l = L.lib()
-            with torch.cuda.graph(g):
-                L.check(l.flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
-                if preds is not None:
-                    L.check(l.flair_unet_want_preds(h, L.ptr(ent["preds"]), L.ptr(ent["prob"])), "flair_unet_want_preds")
-                if rows is not None:
-                    L.check(l.flair_unet_want_rowvec(h, L.ptr(ent["rows"])), "flair_unet_want_rowvec")
-                L.check(l.flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(ent["x"]), L.ptr(ent["logits"]), B, H, W, 0,
-                                             L.ptr(ws), ws.numel(), L.stream()), "flair_unet_forward")
+            try:
+                # thread_local: another thread of the process (a DataLoader's pin-memory thread allocating page-locked memory)
+                # may call the runtime while this one captures; under the default mode that call fails and the capture with it
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    L.check(l.flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
+                    if preds is not None:
+                        L.check(l.flair_unet_want_preds(h, L.ptr(ent["preds"]), L.ptr(ent["prob"])), "flair_unet_want_preds")
+                    if rows is not None:
+                        L.check(l.flair_unet_want_rowvec(h, L.ptr(ent["rows"])), "flair_unet_want_rowvec")
+                    L.check(l.flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(ent["x"]), L.ptr(ent["logits"]), B, H, W, 0,
+                                                 L.ptr(ws), ws.numel(), L.stream()), "flair_unet_forward")
+            except Exception as e:
+                # nothing ran (capture records); the caller runs this same call eagerly, and this kind of call stays eager until
+                # the key changes
+                warnings.warn(f"flair_amd.Unet: HIP graph capture of the eval forward failed ({type(e).__name__}: {e}); running eagerly")
+                self._eval_nocapture.add(gkey)
+                return self._NOT_CAPTURED
             ent["graph"] = g
             self._eval_graphs[gkey] = ent
         ent["x"].copy_(x)       # (capture records, it does not run: the first use replays too)
@@ -488,20 +527,25 @@ class Unet(nn.Module):
             rows = rows.detach().to(torch.float32).contiguous()
         ws = self._workspace(B, H, W, training)
         h = self._hh(training)
+        key, repack = None, False
         if not training:
-            ver = sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers())
-            key = (ver, self._flat_p._version, self._flat_b._version, self.__dict__.get("_native_writes", 0), B, H, W, ws.data_ptr())
-            graphs = self.__dict__.setdefault("_eval_graphs", {})
+            key = self._eval_cache_key(B, H, W, ws)
             if self.__dict__.get("_eval_key") != key:
-                graphs.clear()
-                self._eval_hits = {}
+                self._drop_eval_cache()
             elif (ce is None and os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0" and B * H * W <= self._GRAPH_MAX_PIXELS
                   and not torch.cuda.is_current_stream_capturing()):
                 gkey = (want_logits, preds is not None, prob is not None, rows is not None)
-                hits = self.__dict__.setdefault("_eval_hits", {})
+                hits = self._eval_hits
                 hits[gkey] = hits.get(gkey, 0) + 1
-                if gkey in graphs or hits[gkey] >= 2:   # (the first repeat ran eagerly with reuse: every kernel's one-time set-up is done)
-                    return self._eval_graph(gkey, x, want_logits, preds, prob, ws, h, rows)
+                # (the first repeat ran eagerly with reuse: every kernel's one-time set-up is done)
+                if gkey not in self._eval_nocapture and (gkey in self._eval_graphs or hits[gkey] >= 2):
+                    out = self._eval_graph(gkey, x, want_logits, preds, prob, ws, h, rows)
+                    if out is not self._NOT_CAPTURED:
+                        return out
+                    # a capture that broke inside the native call has advanced the executor's host state without running a kernel:
+                    # withdraw the reuse request and pack again (the output requests below replace the capture's own)
+                    L.check(L.lib().flair_unet_reuse_constants(h, 0), "flair_unet_reuse_constants")
+                    repack = True
         logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
         if preds is not None:
             L.check(L.lib().flair_unet_want_preds(h, L.ptr(preds), L.ptr(prob)), "flair_unet_want_preds")
@@ -511,13 +555,9 @@ class Unet(nn.Module):
             L.check(L.lib().flair_unet_want_rowvec(h, L.ptr(rows)), "flair_unet_want_rowvec")
         if not training:
             # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
-            # BatchNorm-coefficient launches.  torch bumps a tensor's _version on every in-place write (optimizers,
-            # load_state_dict; writes through .data are invisible to it, as they are to autograd); native writers (training forwards: running statistics; the fused
-            # trainer's SGD) bump _native_writes.
-            # (the parameters / buffers are .data views of the flat buffers: each carries its own version counter)
-            ver = sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers())
-            key = (ver, self._flat_p._version, self._flat_b._version, self.__dict__.get("_native_writes", 0), B, H, W, ws.data_ptr())
-            if self.__dict__.get("_eval_key") == key:
+            # BatchNorm-coefficient launches while the key (_eval_cache_key) stands.  Writes through .data are invisible to it,
+            # as they are to autograd: weights_changed() is the call for those.
+            if self.__dict__.get("_eval_key") == key and not repack:
                 L.check(L.lib().flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
             self._eval_key = key
         else:
@@ -713,12 +753,17 @@ class Unet(nn.Module):
         except Exception:
             pass
 
-    _NATIVE_STATE = ("_h", "_h_eval", "_eval_key", "_eval_graphs", "_eval_hits", "_ws_need", "_split", "_ws", "_flat_p", "_flat_b", "_flat_n", "_grads", "_live_ws", "_split_ws")
+    _NATIVE_STATE = ("_h", "_h_eval", "_eval_key", "_eval_graphs", "_eval_hits", "_eval_nocapture", "_ws_need", "_split", "_ws", "_flat_p", "_flat_b", "_flat_n", "_grads", "_live_ws", "_split_ws")
 
     def __getstate__(self):
         d = dict(self.__dict__)
         for k in self._NATIVE_STATE:
             d.pop(k, None)
+        if self.__dict__.get("_flat_p") is not None:
+            # every parameter is a view of the flat buffer and pickle writes a view's WHOLE storage, once per tensor (some hundred
+            # times 85 MB): hand out compact clones instead.  (The sub-modules' _owner, this object, is not copied along:
+            # __setstate__ sets it.)
+            d["_modules"] = copy.deepcopy(d["_modules"], {id(self): None})
         return d
 
     def __setstate__(self, d):

@@ -59,8 +59,9 @@ int flair_unet_backward(flair_unet_t* h, const float* params, const float* dlogi
 int flair_unet_head_ld(const flair_unet_t* h);
 /* Inference with constant weights (zone_detect's window loop, predict): a one-shot promise that `params` and `buffers` are
  * bit-identical to those of the previous eval-mode flair_unet_forward on this handle.  If the next eval-mode forward also
- * uses the same workspace and shape, it skips re-packing the weights and re-deriving the 46 BatchNorm affine pairs (both
- * are still in the workspace); any other call clears the promise.  The reference has no counterpart: PyTorch modules keep
+ * uses the same workspace, shape and `params` / `buffers` pointers, it skips re-packing the weights and re-deriving the 46
+ * BatchNorm affine pairs (both are still in the workspace); with other pointers the promise cannot be about what was packed
+ * and the forward packs again; any other call clears the promise.  The reference has no counterpart: PyTorch modules keep
  * their weights in the layout they compute in. */
 int flair_unet_reuse_constants(flair_unet_t* h, int on);
 /* One-shot: the next flair_unet_forward with training = 0 and logits = NULL writes uint8 argmax predictions [B][H][W] to preds_u8

@@ -344,3 +344,41 @@ def test_softmax_argmax_and_confmat_past_the_block_cap(dev, shape, Cc):
     p = torch.randint(0, Cc, (B * H * W,), generator=g)
     cm = ops.confmat_update(torch.zeros(Cc, Cc, dtype=torch.int64, device=dev), t.to(dev), p.to(dev))
     assert np.array_equal(cm.cpu().numpy(), seg_step.confusion_matrix_np(t.numpy(), p.numpy(), Cc))
+
+
+# ------------------------------------------------------------------------------------------------ the trainer's SGD
+# p in [-64, 64], g in [-8, 8], lr = 0.25: lr * g is a multiple of 1/4 within +-2 and p - lr * g one within +-66, both exact in fp32
+# whether or not the compiler contracts them into an FMA.  4 096 blocks of 256 threads take 4 floats each per pass: 4 194 304 elements;
+# the last length makes three passes, the third over 777 float4s, and leaves a 3-element tail.
+SGD_LENGTHS = [1, 2, 3, 4, 7, 4097, 2 * 4096 * 256 * 4 + 4 * 777 + 3]
+SGD_PAD = 8          # floats after the n updated ones, in the same allocation
+
+
+@pytest.mark.parametrize("n", SGD_LENGTHS)
+def test_sgd_step_exact_over_loop_passes_tails_and_padding(dev, n):
+    from flair_amd import _lib as L
+    assert SGD_LENGTHS[-1] == 8388608 + 4 * 777 + 3
+    g = torch.Generator().manual_seed(n % 1000)
+    p = torch.randint(-64, 65, (n + SGD_PAD,), generator=g).float()
+    gr = torch.randint(-8, 9, (n + SGD_PAD,), generator=g).float()
+    want = p.double()
+    want[:n] -= 0.25 * gr[:n].double()
+    assert torch.equal(want.float().double(), want)      # the expectation is an fp32 number
+    pd, gd = p.to(dev), gr.to(dev)
+    assert L.lib().flair_sgd_step(L.ptr(pd), L.ptr(gd), n, 0.25, L.stream()) == 0
+    got = pd.cpu()
+    bad = int((got[:n].double() != want[:n]).sum())
+    assert bad == 0, f"n={n}: {bad} elements differ"
+    assert torch.equal(got[n:], p[n:])                   # nothing past n is written, whatever n is modulo 4
+    assert torch.equal(gd.cpu(), gr)
+
+
+def test_sgd_step_refuses_a_pointer_that_is_not_16_byte_aligned(dev):
+    from flair_amd import _lib as L
+    p = torch.arange(16, dtype=torch.float32, device=dev)
+    g = torch.ones(16, dtype=torch.float32, device=dev)
+    before = p.clone()
+    assert L.lib().flair_sgd_step(p.data_ptr() + 4, L.ptr(g), 8, 0.25, L.stream()) == -2
+    assert L.lib().flair_sgd_step(L.ptr(p), g.data_ptr() + 4, 8, 0.25, L.stream()) == -2
+    assert L.lib().flair_sgd_step(None, L.ptr(g), 8, 0.25, L.stream()) == -1
+    assert torch.equal(p, before)
