@@ -57,6 +57,8 @@ const char* flair_strerror(int code) {
     case -14: return "UperNet-Swin tile size: height and width must be multiples of 32 from 64 to 2048";
     case -15: return "flair_unet_want_ce: needs an eval-mode forward without fp32 logits and without a flair_unet_want_preds request";
     case -16: return "flair_unet_want_rowvec: the bottleneck row vector is added in eval-mode forwards only (training takes the split path)";
+    case -17: return "flair_unet_want_rowvec_train: the request is for a training forward (an eval-mode forward takes flair_unet_want_rowvec)";
+    case -18: return "flair_unet_want_rowvec_train: the gradient that reaches the bottleneck tensor was stored masked, its row sums would be wrong";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -109,6 +111,11 @@ int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, cons
 int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32) {
   if (!h || !rows_f32) return -1;
   h->net.want_rowvec(rows_f32);
+  return 0;
+}
+int flair_unet_want_rowvec_train(flair_unet_t* h, const float* rows_f32, float* drows_f32) {
+  if (!h || !rows_f32 || !drows_f32) return -1;
+  h->net.want_rowvec_train(rows_f32, drows_f32);
   return 0;
 }
 int flair_unet_reuse_constants(flair_unet_t* h, int on) {
@@ -347,6 +354,16 @@ int flair_add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int 
   if (!x || !v) return -1;
   if (dtype != DT_F32 && dtype != DT_BF16) return -2;
   return add_rowvec_nhwc(dtype, x, v, N, H, W, C, (hipStream_t)stream);
+}
+int flair_add_rowvec_nhwc_to(int dtype, const void* x, const float* v, void* y, int N, int H, int W, int C, void* stream) {
+  if (!x || !v || !y) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return add_rowvec_nhwc_to(dtype, x, v, y, N, H, W, C, (hipStream_t)stream);
+}
+int flair_rowvec_grad_nhwc(int dtype, const void* dx, float* dv, int N, int H, int W, int C, void* stream) {
+  if (!dx || !dv) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  return rowvec_grad_nhwc(dtype, dx, dv, N, H, W, C, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------ operators

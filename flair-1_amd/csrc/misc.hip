@@ -484,6 +484,46 @@ __global__ void add_rowvec_nhwc_kernel(T* __restrict__ x, const float* __restric
   }
 }
 
+// The out-of-place form for a training forward: y = T(float(x) + v[row]).  x stays as it is — in the backward it is the ReLU mask
+// source of the unit that produced it — and the decoder reads y.  Same arithmetic and chunking as add_rowvec_nhwc_kernel; x == y
+// is that kernel.
+template <typename T>
+__global__ void add_rowvec_nhwc_to_kernel(const T* x, const float* __restrict__ v, T* y, long nchunks, int row_chunks) {
+  constexpr int CH = Elem<T>::CH;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nchunks; i += (long)gridDim.x * blockDim.x) {
+    const float a = v[i / row_chunks];
+    float f[CH];
+    chunk_to_f<T>(*reinterpret_cast<const uint4*>(x + i * CH), f);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) f[e] += a;
+    *reinterpret_cast<uint4*>(y + i * CH) = f_to_chunk<T>(f);
+  }
+}
+
+// Its gradient with respect to v: dv[n][h] = sum over w, c of dx[n][h][w][c].  One workgroup per row (n, h) of W * C contiguous
+// elements: lane t takes chunks t, t + 256, ... in that order, sums a chunk's elements left to right, then a butterfly over the
+// wave and the four wave sums from LDS in wave order — one fixed order in fp32, no atomics, the same bits on every call.
+template <typename T>
+__global__ __launch_bounds__(256) void rowvec_grad_nhwc_kernel(const T* __restrict__ dx, float* __restrict__ dv, int row_chunks) {
+  constexpr int CH = Elem<T>::CH;
+  __shared__ float sh[4];
+  const T* row = dx + (long)blockIdx.x * row_chunks * CH;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < row_chunks; i += 256) {
+    float f[CH];
+    chunk_to_f<T>(*reinterpret_cast<const uint4*>(row + (long)i * CH), f);
+    float c = f[0];
+#pragma unroll
+    for (int e = 1; e < CH; ++e) c += f[e];
+    s += c;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) dv[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+}
+
 template <typename T>
 __global__ void ew_add_kernel(T* __restrict__ dst, const T* __restrict__ src, long nchunks) {
   constexpr int CH = Elem<T>::CH;
@@ -621,6 +661,36 @@ int add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int
     hipLaunchKernelGGL(add_rowvec_nhwc_kernel<float>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (float*)x, v, nchunks, (int)row_chunks);
   else
     hipLaunchKernelGGL(add_rowvec_nhwc_kernel<bf16_t>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (bf16_t*)x, v, nchunks, (int)row_chunks);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+int add_rowvec_nhwc_to(int dtype, const void* x, const float* v, void* y, int N, int H, int W, int C, hipStream_t s) {
+  if (N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || (((uintptr_t)x | (uintptr_t)y) & 15) || ((uintptr_t)v & 3)) return -2;
+  const int ch = dtype == DT_F32 ? 4 : 8;
+  const long row_chunks = (long)W * (C / ch);
+  if (row_chunks > 0x7fffffffL) return -2;
+  const long nchunks = (long)N * H * row_chunks;
+  ProfScope ps("add_rowvec_nhwc_to", 0.0, (double)nchunks * 32.0, s);
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(add_rowvec_nhwc_to_kernel<float>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (const float*)x, v, (float*)y, nchunks, (int)row_chunks);
+  else
+    hipLaunchKernelGGL(add_rowvec_nhwc_to_kernel<bf16_t>, dim3(ew_blocks(nchunks)), dim3(256), 0, s, (const bf16_t*)x, v, (bf16_t*)y, nchunks, (int)row_chunks);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+int rowvec_grad_nhwc(int dtype, const void* dx, float* dv, int N, int H, int W, int C, hipStream_t s) {
+  if (N < 1 || H < 1 || W < 1 || C < 8 || (C & 7) || ((uintptr_t)dx & 15) || ((uintptr_t)dv & 3)) return -2;
+  const int ch = dtype == DT_F32 ? 4 : 8;
+  const long row_chunks = (long)W * (C / ch);
+  const long rows = (long)N * H;
+  if (row_chunks > 0x7fffffffL || rows > 0x7fffffffL) return -2;
+  ProfScope ps("rowvec_grad_nhwc", 0.0, (double)rows * row_chunks * 16.0, s);
+  if (dtype == DT_F32)
+    hipLaunchKernelGGL(rowvec_grad_nhwc_kernel<float>, dim3((unsigned)rows), dim3(256), 0, s, (const float*)dx, dv, (int)row_chunks);
+  else
+    hipLaunchKernelGGL(rowvec_grad_nhwc_kernel<bf16_t>, dim3((unsigned)rows), dim3(256), 0, s, (const bf16_t*)dx, dv, (int)row_chunks);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }

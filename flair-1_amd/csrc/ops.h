@@ -64,6 +64,11 @@ int sgd_step(float* params, const float* grads, long n, float lr, hipStream_t s)
 int add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, hipStream_t s);
 // x[n][h][w][c] += v[n*H + h] on an NHWC tensor of the compute dtype, in place (C a multiple of 8, x 16-byte aligned)
 int add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, hipStream_t s);
+// y[n][h][w][c] = T(float(x[n][h][w][c]) + v[n*H + h]): the same add out of place (x == y allowed), for a training forward, where x
+// is still needed as it is
+int add_rowvec_nhwc_to(int dtype, const void* x, const float* v, void* y, int N, int H, int W, int C, hipStream_t s);
+// dv[n*H + h] = sum over w, c of dx[n][h][w][c]: the gradient of either add with respect to v; fp32, fixed order, no atomics
+int rowvec_grad_nhwc(int dtype, const void* dx, float* dv, int N, int H, int W, int C, hipStream_t s);
 int ew_add(int dtype, void* dst, const void* src, long n, hipStream_t s);
 int fill_zero(void* p, size_t bytes, hipStream_t s);
 int fill_f32(float* p, long n, float v, hipStream_t s);

@@ -116,6 +116,7 @@ class UNet {
   // one-shot requests
   void invalidate_reuse() {
     last_valid_ = false; last_params_ = nullptr; last_buffers_ = nullptr; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); rowvec_req_ = nullptr;
+    rowvec_train_req_ = nullptr; drows_req_ = nullptr;
   }
   // the next forward without fp32 logits writes argmax predictions [B][H][W] uint8 here (one-shot, like reuse_constants)
   void want_preds(unsigned char* p, float* maxprob) { preds_req_ = p; maxprob_req_ = maxprob; }
@@ -130,6 +131,12 @@ class UNet {
   // (one-shot): element [b][h][w][c] += v[b][h], the metadata fusion of model.py:59-60.  In eval mode every unit materialises its
   // output and f_[5] is read by decoder block 0 alone, so the add happens in place; the arena layout does not change
   void want_rowvec(const float* v) { rowvec_req_ = v; }
+  // the training form (one-shot): the next training forward hands the decoder a SECOND tensor, f5m = T(float(f_[5]) + v), and leaves
+  // f_[5] alone — it is the ReLU mask source of layer4's last block in the backward (bn_backward, the bnr_out of a residual producer),
+  // and out + v reads as "ReLU on" wherever out == 0 < v.  The backward of that forward writes dv[b][h] = sum over w, c of the gradient
+  // that reaches f5m (complete and unmasked after the decoder's backward: nothing produces f5m, so no data-gradient epilogue masks
+  // it) and hands that buffer to the encoder as the gradient of f_[5] (d f5m / d f_[5] is the identity)
+  void want_rowvec_train(const float* v, float* dv) { rowvec_train_req_ = v; drows_req_ = dv; }
   void* last_dlogits_nhwc() const { return dl_nhwc_; }
   const void* logits_nhwc() const { return logits_nhwc_; }
   int head_ld() const { return convs.back().Cout_p; }
@@ -175,6 +182,10 @@ class UNet {
   float* maxprob_req_ = nullptr;
   CeReq ce_req_;
   const float* rowvec_req_ = nullptr;
+  const float* rowvec_train_req_ = nullptr;
+  float* drows_req_ = nullptr;
+  Act f5m_;                         // the decoder's bottleneck input of the last training forward with rows, for its backward
+  float* drows_pending_ = nullptr;  // where that backward writes the row sums; cleared once written and by every later forward
   bool side_init();
   hipStream_t wgrad_stream();     // forks the side stream behind everything queued on s_ so far
   int side_cus() const;           // WgradArgs::cus of a launch on the side stream

@@ -475,11 +475,17 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   const bool reuse_now = reuse_req_;
   const CeReq ce_now = ce_req_;
   const float* const rowvec_now = rowvec_req_;
+  const float* const rows_train_now = rowvec_train_req_;
+  float* const drows_now = drows_req_;
   preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false; ce_req_ = CeReq(); rowvec_req_ = nullptr;
+  rowvec_train_req_ = nullptr; drows_req_ = nullptr;
+  f5m_ = Act(); drows_pending_ = nullptr;   // (a backward belongs to the forward just before it)
   // two heads asked of one forward, or the CE head of a forward that is not an eval-mode one without fp32 logits
   if (ce_now.labels && (preds_now || training || logits_nchw)) return -15;
-  // the bottleneck row vector of a training forward: its backward is not built (the gradient that reaches f_[5] is stored masked)
+  // the in-place add is for eval-mode forwards: in a training forward f_[5] is still needed as it is (the ReLU mask source of the
+  // unit that produced it), which is what the training request below is for
   if (rowvec_now && training) return -16;
+  if (rows_train_now && !training) return -17;
   if ((H % 32) || (W % 32)) return -10;
   // (the caller vouches for the CONTENTS of params / buffers; other addresses are other tensors, whatever it believes)
   reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && params == last_params_ && buffers == last_buffers_ &&
@@ -494,7 +500,16 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   encoder_fwd_impl(x_nchw);
   // metadata fusion (model.py:59-60): f_[5] is the materialised output of layer4's last block, read by decoder block 0 only
   if (rowvec_now) RUN(add_rowvec_nhwc(dtype, f_[5].p, rowvec_now, f_[5].N, f_[5].H, f_[5].W, f_[5].C, s_));
+  const Act f5 = f_[5];
+  if (rows_train_now) {
+    // training: the decoder reads a second tensor (the swap decoder_forward does with dec_in_), f_[5] stays for the backward
+    f5m_ = alloc_act(f5.N, f5.H, f5.W, f5.C);
+    RUN(add_rowvec_nhwc_to(dtype, f5.p, rows_train_now, f5m_.p, f5.N, f5.H, f5.W, f5.C, s_));
+    f_[5] = f5m_;
+    drows_pending_ = drows_now;
+  }
   decoder_fwd_impl();
+  f_[5] = f5;
   head_fwd_impl(logits_nchw);
   fwd_top_ = top_;
   reuse_ = false;
@@ -506,6 +521,7 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
 int UNet::encoder_forward(const float* params, float* buffers, const float* x_nchw, float* const feats[5], int B, int H,
                           int W, int training, void* ws, size_t ws_bytes, hipStream_t s) {
   invalidate_reuse();
+  f5m_ = Act(); drows_pending_ = nullptr;
   if ((H % 32) || (W % 32)) return -10;
   begin(ws, ws_bytes, s, false);
   fwd_common_begin(params, buffers, B, H, W, training);
@@ -672,6 +688,9 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
       if (conv_tile_epilogue_ok(dtype, a)) {
         dg = DG_UPCAT_TILE;
         attach_bn_reduce(a, u.in0);   // the pooled half is the whole gradient of the previous block's output
+        // ... or of f5m_, which no unit produces: the row sums need it complete and UNMASKED, so a fused reduction / mask on it
+        // (there is none today: attach_bn_reduce finds no producer) is an error, never silently wrong sums
+        if (drows_pending_ && u.in0.p == f5m_.p && (a.bnr_partial || a.bnr_mask) && !err_) err_ = -18;
       } else {
         dg = DG_UPCAT_SPLIT;
         dcat = alloc((size_t)u.y.rows() * (C0 + C1) * dtype_size(dtype));
@@ -886,7 +905,20 @@ int UNet::backward(const float* params, const float* dlogits_nchw, const void* d
   head_bwd_impl(dl);
   stage_done(6);
   decoder_bwd_impl();
-  stage_done(5);
+  stage_done(5);   // (bucket 5 is the decoder's weights; the row sums below belong to no bucket and stay behind its event)
+  if (drows_pending_) {
+    // decoder block 0's conv1 wrote its pooled half into the buffer keyed by f5m_: the complete gradient of the row add's output.
+    // Its row sums are d rows; the values are also the gradient of f_[5], which the encoder walk asks for under that key
+    float* const drows = drows_pending_;
+    drows_pending_ = nullptr;
+    void* g = grad_peek(f5m_);
+    if (!g) { if (!err_) err_ = -11; }
+    else {
+      RUN(rowvec_grad_nhwc(dtype, g, drows, f5m_.N, f5m_.H, f5m_.W, f5m_.C, s_));
+      for (auto& gb : gbufs_)
+        if (gb.act == f5m_.p) gb.act = f_[5].p;
+    }
+  }
   encoder_bwd_impl();
   stage_events_ = nullptr;
   return err_;

@@ -57,6 +57,8 @@ PROTOTYPES = {
     "flair_sgd_step": (i32, [vp, vp, i64, f32, vp]),
     "flair_add_rowvec_nchw": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "flair_add_rowvec_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, vp]),
+    "flair_add_rowvec_nhwc_to": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "flair_rowvec_grad_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, vp]),
     "flair_conv2d_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32]),
     "flair_conv2d_forward": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp,
                                    vp, sz, vp]),
@@ -111,6 +113,7 @@ PROTOTYPES = {
     "flair_unet_want_preds": (i32, [vp, vp, vp]),
     "flair_unet_want_ce": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
     "flair_unet_want_rowvec": (i32, [vp, vp]),
+    "flair_unet_want_rowvec_train": (i32, [vp, vp, vp]),
     "flair_detect_stitch_preds": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp]),
     "flair_detect_blend_accum": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_detect_blend_flush": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),

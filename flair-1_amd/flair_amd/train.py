@@ -85,8 +85,12 @@ class SegTrainer:
     def __init__(self, model, lr, class_weight=None, group=None, overlap=True, min_bucket_elems=1 << 18,
                  force_exchange=False, broadcast_buffers=True, class_names=None, metadata_encoder=None):
         self.model = model
-        # a MetadataMLP (BASELINE config 4): validate_step / predict add its encoding to the bottleneck inside their one native call
+        # a MetadataMLP (BASELINE config 4): train_step / validate_step / predict add its encoding to the bottleneck inside their one
+        # native call; train_step(..., mtd) also trains it
         self.metadata_encoder = metadata_encoder
+        self._drows = None
+        self._mlp_synced = False
+        self.mlp_grads = None
         self.class_names = None if class_names is None else [str(n) for n in class_names]
         self.sync_buffers = bool(broadcast_buffers)   # torch DDP's broadcast_buffers (tasks.py:83-88 keeps the default, True)
         self._src0 = 0 if group is None else dist.get_global_rank(group, 0)
@@ -140,17 +144,71 @@ class SegTrainer:
             self._ce_ws = torch.empty(L.lib().flair_ce_workspace_bytes(B, H, W) + 256, dtype=torch.uint8, device=dev)
         return ld
 
-    def train_step(self, img, labels):
+    def train_step(self, img, labels, mtd=None, mtd_masks="auto"):
         """img (B,Cin,H,W) fp32 HIP tensor; labels (B,H,W) uint8/int or fp32 one-hot (B,C,H,W).  Returns the
-        device scalar loss (no host sync)."""
-        with torch.cuda.device(self.grads.device):   # every native call below launches on the current device's stream
-            return self._train_step(img, labels)
+        device scalar loss (no host sync).
 
-    def _train_step(self, img, labels):
+        ``mtd``: (B,45) metadata vectors (BASELINE config 4, model.py:57-62).  ``metadata_encoder`` encodes them in whatever mode it
+        is in — the trainer never switches it — and the encoding is added to the bottleneck inside the one native training forward
+        (flair_unet_want_rowvec_train); the native backward returns its gradient, which goes through the MetadataMLP's own backward
+        kernel, and the MLP's six tensors take the same SGD step as the U-Net's (tasks_utils.py:95 hands the optimizer
+        ``model.parameters()``, the MLP included); their ``.grad`` is None afterwards.  ``mtd_masks``: the three dropout masks of
+        MetadataMLP.forward — "auto" draws them from torch's generator when the encoder is in training mode (none in eval mode),
+        a list is taken as it is, None means no dropout.  With a process group rank 0's MLP parameters are broadcast once, at the
+        first such step, and each step sums the MLP's gradients over the ranks in one flat all-reduce behind the backward.
+        Without ``mtd`` the step is the plain one, whether an encoder was given or not."""
+        with torch.cuda.device(self.grads.device):   # every native call below launches on the current device's stream
+            return self._train_step(img, labels, mtd, mtd_masks)
+
+    def _meta_rows_train(self, img, mtd, masks):
+        """x_enc of model.py:58 with its autograd graph (a leaf-to-rows graph of one _MlpFn node per 256 samples)."""
+        enc = self.metadata_encoder
+        if enc is None:
+            raise ValueError("SegTrainer was built without a metadata_encoder: pass the MetadataMLP to take metadata")
+        if tuple(img.shape[-2:]) != (512, 512):   # the reference hard-codes repeat(1,512,1,16) (quirk Q4)
+            raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+        dev = self.grads.device
+        if self.exchange and not self._mlp_synced:
+            # DDP's initial broadcast covers the whole module (SURVEY.md C2): rank 0's MLP, once
+            ps = [p.data for p in enc.parameters()]
+            flat = torch.cat([p.reshape(-1) for p in ps])
+            dist.broadcast(flat, src=self._src0, group=self.group)
+            for p, v in zip(ps, flat.split([p.numel() for p in ps])):
+                p.copy_(v.view_as(p))
+        self._mlp_synced = True
+        with torch.enable_grad():
+            rows = enc(mtd.to(dev), masks=masks)
+        B = img.shape[0]
+        if self._drows is None or self._drows.shape != (B, 16):
+            self._drows = torch.empty(B, 16, dtype=torch.float32, device=dev)
+        return rows
+
+    def _mlp_step(self, rows):
+        """Backward of the MetadataMLP from the row gradient the native backward left in ``_drows``, the exchange of its
+        gradients and its SGD step (the U-Net's rule and kernel: p -= (lr / world) * sum over ranks of g)."""
+        ps = [p for p in self.metadata_encoder.parameters() if p.requires_grad]
+        if not ps:
+            return
+        for p in ps:
+            p.grad = None
+        rows.backward(self._drows)
+        # one flat buffer (every tensor's size is a multiple of 4 floats: whole 16-byte chunks for the SGD kernel)
+        flat = torch.cat([p.grad.reshape(-1) for p in ps])
+        if self.exchange and not self._no_collective:
+            # after the backward, outside the overlapped buckets: some 22 KB, nothing to overlap
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+        self.mlp_grads = flat   # like ``grads``: the (summed) gradient of the last step, in parameters() order
+        for p, g in zip(ps, flat.split([p.numel() for p in ps])):
+            ops.sgd_step_(p.data, g, self.lr / self.world)
+            p.grad = None
+
+    def _train_step(self, img, labels, mtd=None, mtd_masks="auto"):
         m = self.model
         B, _, H, W = img.shape
         ld = self._buffers(B, H, W)
-        m._c_forward(img, training=True, want_logits=False)   # logits stay in the workspace, NHWC of the compute dtype
+        rows = None if mtd is None else self._meta_rows_train(img, mtd, mtd_masks)
+        # logits stay in the workspace, NHWC of the compute dtype
+        m._c_forward(img, training=True, want_logits=False, train_rows=None if rows is None else (rows.detach(), self._drows))
         kind = 3 if labels.dtype == torch.float32 else ops._LABEL_KIND[labels.dtype]
         l = L.lib()
         L.check(l.flair_ce_head_nhwc(l.flair_unet_logits_nhwc(m._h), m._dt, ld, L.ptr(labels.contiguous()), kind,
@@ -177,6 +235,8 @@ class SegTrainer:
                 allreduce_buckets(self.grads, self.buckets, self.group)
                 if self.sync_buffers:
                     dist.broadcast(m.flat_buffers(), src=self._src0, group=self.group)
+        if rows is not None:
+            self._mlp_step(rows)
         # DDP averages: fold 1/world into the step size
         ops.sgd_step_(m._flat_p, self.grads, self.lr / self.world)
         m._native_writes = m.__dict__.get("_native_writes", 0) + 1   # parameters changed behind torch's version counter

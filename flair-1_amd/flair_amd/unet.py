@@ -506,16 +506,32 @@ class Unet(nn.Module):
         return None if ent["logits"] is None else ent["logits"].clone()
 
     @_on_model_device
-    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None, rows=None):
+    def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None, rows=None, train_rows=None):
         """want_logits=False (fused trainer): the head's output stays in the workspace as NHWC rows of the compute dtype
         (flair_unet_logits_nhwc) and no fp32 NCHW tensor is produced; returns None.  preds / prob (eval mode, no logits): uint8
         argmax and its fp32 probability from the head convolution's epilogue (flair_unet_want_preds).  ce (eval mode, no
         logits): the arguments of flair_unet_want_ce behind the handle — the validation head in the same call; such a forward
         always runs eagerly (never captured, not counted towards the captures of the plain paths).  rows (eval mode only): fp32
         (B, H/32) added to the bottleneck feature between encoder and decoder, element [b,c,h,w] += rows[b,h]
-        (flair_unet_want_rowvec) — the metadata fusion of model.py:57-62 inside the one native call; combines with all of the above."""
+        (flair_unet_want_rowvec) — the metadata fusion of model.py:57-62 inside the one native call; combines with all of the above.
+        train_rows (training mode only, excludes rows): a pair (rows, drows) of fp32 (B, H/32) tensors — the same add in a training
+        forward, out of place (flair_unet_want_rowvec_train); the _c_backward of this forward writes d loss / d rows into drows."""
         x = self._prep(x)
         B, _, H, W = x.shape
+        if train_rows is not None:
+            if rows is not None:
+                raise RuntimeError("flair_amd.Unet: rows= (eval mode) and train_rows= (training mode) exclude each other")
+            if not training:
+                raise RuntimeError("flair_amd.Unet: train_rows= is for training-mode forwards; an eval-mode forward takes rows=")
+            t_rows, t_drows = train_rows
+            for t in (t_rows, t_drows):
+                if not t.is_cuda or t.device != x.device:
+                    raise L.FlairHipError("flair_amd.Unet: bottleneck rows must live on the input's HIP device")
+                if tuple(t.shape) != (B, H // 32):
+                    raise RuntimeError(f"bottleneck rows must be (B, H/32) = ({B}, {H // 32}), got {tuple(t.shape)}")
+            if t_drows.dtype != torch.float32 or not t_drows.is_contiguous():
+                raise RuntimeError("flair_amd.Unet: the gradient tensor of train_rows must be contiguous fp32 (the backward writes it)")
+            train_rows = (t_rows.detach().to(torch.float32).contiguous(), t_drows.detach())
         if rows is not None:
             if training:
                 raise RuntimeError("flair_amd.Unet: bottleneck rows are added in eval-mode forwards only; a training-mode model "
@@ -553,6 +569,8 @@ class Unet(nn.Module):
             L.check(L.lib().flair_unet_want_ce(h, *ce), "flair_unet_want_ce")
         if rows is not None:
             L.check(L.lib().flair_unet_want_rowvec(h, L.ptr(rows)), "flair_unet_want_rowvec")
+        if train_rows is not None:
+            L.check(L.lib().flair_unet_want_rowvec_train(h, L.ptr(train_rows[0]), L.ptr(train_rows[1])), "flair_unet_want_rowvec_train")
         if not training:
             # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
             # BatchNorm-coefficient launches while the key (_eval_cache_key) stands.  Writes through .data are invisible to it,
@@ -568,6 +586,7 @@ class Unet(nn.Module):
             self._fwd_id += 1
             self._live_id = self._fwd_id
             self._live_ws = ws
+            self._live_rows = train_rows   # (the native side holds raw pointers until the backward of this forward)
             self._bump_bn()
         return logits
 
@@ -589,6 +608,7 @@ class Unet(nn.Module):
             ev = (C.c_void_p * 7)(*[e.cuda_event for e in stage_events])
         L.check(L.lib().flair_unet_backward(self._h, L.ptr(self._flat_p), L.ptr(dlogits), L.ptr(dlogits_nhwc), L.ptr(grads),
                                             L.ptr(ws), ws.numel(), L.stream(), ev), "flair_unet_backward")
+        self._live_rows = None
         return grads
 
     # ---- split path (model.py:57-62)
@@ -753,7 +773,7 @@ class Unet(nn.Module):
         except Exception:
             pass
 
-    _NATIVE_STATE = ("_h", "_h_eval", "_eval_key", "_eval_graphs", "_eval_hits", "_eval_nocapture", "_ws_need", "_split", "_ws", "_flat_p", "_flat_b", "_flat_n", "_grads", "_live_ws", "_split_ws")
+    _NATIVE_STATE = ("_h", "_h_eval", "_eval_key", "_eval_graphs", "_eval_hits", "_eval_nocapture", "_ws_need", "_split", "_ws", "_flat_p", "_flat_b", "_flat_n", "_grads", "_live_ws", "_split_ws", "_live_rows")
 
     def __getstate__(self):
         d = dict(self.__dict__)

@@ -85,6 +85,13 @@ int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, cons
  * flair_unet_want_preds and flair_unet_want_ce.  A training forward that meets the request is refused (-16); the request is dropped by
  * any forward. */
 int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32);
+/* The training form, one-shot like the others: the next flair_unet_forward with training = 1 feeds the decoder a second bottleneck
+ * tensor, dtype(float(f5) + rows[b][h]) (flair_add_rowvec_nhwc_to; f5 itself stays, it is the ReLU mask source of layer4's last block),
+ * and the flair_unet_backward of that forward writes drows_f32[b][h] = sum over c, w of the gradient reaching that tensor
+ * (flair_rowvec_grad_nhwc) before it walks the encoder.  Both are device fp32 (B, H/32) and must stay valid until that backward has
+ * run.  The workspace size and layout bound of flair_unet_workspace_bytes hold.  An eval-mode forward that meets the request is
+ * refused (-17) and runs nothing; the request is dropped by any forward, a pending drows by any later forward. */
+int flair_unet_want_rowvec_train(flair_unet_t* h, const float* rows_f32, float* drows_f32);
 
 /* seg_model.encoder(x) / .decoder(*feats) / .segmentation_head(t) — the metadata path model.py:57-62.
  * feats[i] = feature i+1 of the encoder, NCHW fp32: (B,64,H/2,W/2) ... (B,512,H/32,W/32). */
@@ -258,6 +265,13 @@ int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, 
 /* The same add, in place, on an NHWC tensor of the compute dtype (the layout the executor keeps its features in):
  * x (N,H,W,C) += v (N,H) fp32, summed in fp32 and rounded to `dtype` once.  C must be a multiple of 8 and x 16-byte aligned (-2). */
 int flair_add_rowvec_nhwc(int dtype, void* x, const float* v, int N, int H, int W, int C, void* stream);
+/* The same add out of place: y (N,H,W,C) = dtype(float(x) + v (N,H)).  What a training forward needs, where x — the ReLU output of the
+ * unit that produced it, the mask source of that unit's backward — must stay as it is.  Same arithmetic, chunking and refusals as
+ * flair_add_rowvec_nhwc (both tensors 16-byte aligned); x == y is allowed and is that function. */
+int flair_add_rowvec_nhwc_to(int dtype, const void* x, const float* v, void* y, int N, int H, int W, int C, void* stream);
+/* The gradient of either add with respect to v: dv (N,H) fp32 = sum over w and c of dx (N,H,W,C).  Accumulated in fp32 in one fixed
+ * order (one workgroup per row, no atomics): the same bits on every call.  Same refusals as flair_add_rowvec_nhwc. */
+int flair_rowvec_grad_nhwc(int dtype, const void* dx, float* dv, int N, int H, int W, int C, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Operator-level entry points (unit parity tests; same kernels the model object launches).
