@@ -43,7 +43,8 @@ const char* flair_strerror(int code) {
   if (code == 0) return "ok";
   if (code > 0) return hipGetErrorString((hipError_t)code);
   switch (code) {
-    case -1: return "null or invalid handle";
+    case -1: return "null or invalid handle or argument (flair_unet_fwd_opts_t: maxprob_f32 needs preds_u8; ce_labels needs ce_loss, "
+                    "ce_workspace and a ce_label_kind in 0..3; drows_f32 needs rows_f32)";
     case -2: return "channel count / pointer alignment not supported by the kernel";
     case -3: return "output rows too short for whole 16-byte chunks (channel count / row stride)";
     case -4: return "fused upsample needs even extents";
@@ -55,10 +56,10 @@ const char* flair_strerror(int code) {
     case -12: return "gradient buffer already initialised";
     case -13: return "internal side stream: event record / wait failed";
     case -14: return "UperNet-Swin tile size: height and width must be multiples of 32 from 64 to 2048";
-    case -15: return "flair_unet_want_ce: needs an eval-mode forward without fp32 logits and without a flair_unet_want_preds request";
-    case -16: return "flair_unet_want_rowvec: the bottleneck row vector is added in eval-mode forwards only (training takes the split path)";
-    case -17: return "flair_unet_want_rowvec_train: the request is for a training forward (an eval-mode forward takes flair_unet_want_rowvec)";
-    case -18: return "flair_unet_want_rowvec_train: the gradient that reaches the bottleneck tensor was stored masked, its row sums would be wrong";
+    case -15: return "flair_unet_fwd_opts_t: ce_labels needs an eval-mode forward without fp32 logits and without preds_u8";
+    case -16: return "flair_unet_fwd_opts_t: rows_f32 in a training forward needs drows_f32 (the in-place add is for eval-mode forwards)";
+    case -17: return "flair_unet_fwd_opts_t: drows_f32 is for a training forward (an eval-mode forward takes rows_f32 alone)";
+    case -18: return "flair_unet_fwd_opts_t: the gradient that reaches the bottleneck tensor was stored masked, its sums into drows_f32 would be wrong";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -94,40 +95,18 @@ int64_t flair_unet_workspace_bytes(flair_unet_t* h, int B, int H, int W, int tra
   return (int64_t)h->net.workspace_bytes(B, H, W, training);
 }
 int flair_unet_head_ld(const flair_unet_t* h) { return h ? h->net.convs.back().Cout_p : -1; }
-int flair_unet_want_preds(flair_unet_t* h, uint8_t* preds_u8, float* maxprob_f32) {
-  if (!h || (maxprob_f32 && !preds_u8)) return -1;
-  h->net.want_preds(preds_u8, maxprob_f32);
-  return 0;
-}
-int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, const float* class_weight, float* loss,
-                       uint8_t* preds_u8, int64_t* confmat, void* ce_workspace) {
-  if (!h || !labels || !loss || !ce_workspace || label_kind < 0 || label_kind > 3) return -1;
-  UNet::CeReq r;
-  r.labels = labels; r.kind = label_kind; r.weight = class_weight; r.loss = loss; r.preds = preds_u8;
-  r.confmat = (long long*)confmat; r.ws = (float*)ce_workspace;
-  h->net.want_ce(r);
-  return 0;
-}
-int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32) {
-  if (!h || !rows_f32) return -1;
-  h->net.want_rowvec(rows_f32);
-  return 0;
-}
-int flair_unet_want_rowvec_train(flair_unet_t* h, const float* rows_f32, float* drows_f32) {
-  if (!h || !rows_f32 || !drows_f32) return -1;
-  h->net.want_rowvec_train(rows_f32, drows_f32);
-  return 0;
-}
-int flair_unet_reuse_constants(flair_unet_t* h, int on) {
-  if (!h) return -1;
-  h->net.reuse_constants(on != 0);
-  return 0;
-}
-
 int flair_unet_forward(flair_unet_t* h, const float* params, float* buffers, const float* x, float* logits, int B, int H,
-                       int W, int training, void* ws, size_t wsb, void* stream) {
+                       int W, int training, void* ws, size_t wsb, void* stream, const flair_unet_fwd_opts_t* opts) {
   if (!h) return -1;
-  return h->net.forward(params, buffers, x, logits, B, H, W, training, ws, wsb, (hipStream_t)stream);
+  FwdOpts o;
+  if (opts) {
+    o.reuse_constants = opts->reuse_constants != 0;
+    o.preds = opts->preds_u8; o.maxprob = opts->maxprob_f32;
+    o.ce.labels = opts->ce_labels; o.ce.kind = opts->ce_label_kind; o.ce.weight = opts->ce_class_weight; o.ce.loss = opts->ce_loss;
+    o.ce.preds = opts->ce_preds_u8; o.ce.confmat = (long long*)opts->ce_confmat; o.ce.ws = (float*)opts->ce_workspace;
+    o.rows = opts->rows_f32; o.drows = opts->drows_f32;
+  }
+  return h->net.forward(params, buffers, x, logits, B, H, W, training, ws, wsb, (hipStream_t)stream, o);
 }
 int flair_unet_backward(flair_unet_t* h, const float* params, const float* dl_nchw, const void* dl_nhwc, float* grads,
                         void* ws, size_t wsb, void* stream, void* const* stage_events) {

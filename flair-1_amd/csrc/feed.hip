@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void detect_convert_kernel(const float* __rest
   }
 }
 
-// convert('argmax') from per-window (class, probability) maps that the head convolution left (flair_unet_want_preds): the same
+// convert('argmax') from per-window (class, probability) maps that the head convolution left (flair_unet_fwd_opts_t::preds_u8): the same
 // ownership windows as detect_convert_kernel, band 0 = class as float32, band 1 = its softmax probability
 __global__ __launch_bounds__(256) void detect_stitch_preds_kernel(const unsigned char* __restrict__ preds, const float* __restrict__ maxprob,
                                                                   int B, int S, int margin, const int* __restrict__ tiles,

@@ -73,6 +73,36 @@ struct Unit {  // conv -> BN -> (+ residual) -> ReLU
   bool bnr_masked = false;
 };
 
+// What one forward() does besides the plain pass (flair_unet_fwd_opts_t, include/flair_hip.h): arguments of that call, read while
+// it runs and never kept, so no forward can meet what an earlier call left behind
+struct FwdOpts {
+  // The caller vouches that parameters and buffers are unchanged since the previous eval-mode forward on this handle: an eval-mode
+  // forward with the same arena, shape, params and buffers addresses then skips the weight pack and the 46 BatchNorm-coefficient
+  // launches (both still sit in the arena at the same offsets)
+  bool reuse_constants = false;
+  // an eval-mode forward without fp32 logits writes argmax predictions [B][H][W] uint8 (and the winner's probability) here
+  unsigned char* preds = nullptr;
+  float* maxprob = nullptr;
+  // labels != null: an eval-mode forward without fp32 logits evaluates the per-pixel head of step() on its logits: weighted CE
+  // mean -> loss, argmax -> preds (optional), confmat += bincount (optional); ws: ce_workspace_floats(B, H, W) floats
+  struct Ce {
+    const void* labels = nullptr; int kind = 0; const float* weight = nullptr;
+    float* loss = nullptr; unsigned char* preds = nullptr; long long* confmat = nullptr; float* ws = nullptr;
+  } ce;
+  // rows (fp32 [B][H/32], device) join the bottleneck feature f_[5] between the encoder and the decoder, element [b][h][w][c] +
+  // rows[b][h], the metadata fusion of model.py:59-60.  Eval mode: every unit materialises its output and f_[5] is read by decoder
+  // block 0 alone, so the add happens in place; the arena layout does not change.  Training: the decoder gets a SECOND tensor,
+  // f5m = T(float(f_[5]) + rows), and f_[5] stays — it is the ReLU mask source of layer4's last block in the backward (bn_backward,
+  // the bnr_out of a residual producer), and out + rows reads as "ReLU on" wherever out == 0 < rows.  The backward of that forward
+  // writes drows[b][h] = sum over w, c of the gradient that reaches f5m (complete and unmasked after the decoder's backward: nothing
+  // produces f5m, so no data-gradient epilogue masks it) and hands that buffer to the encoder as the gradient of f_[5] (d f5m /
+  // d f_[5] is the identity)
+  const float* rows = nullptr;
+  float* drows = nullptr;
+  // 0, or the code forward() returns before it touches the handle or the device: a function of these arguments alone
+  int refusal(int training, bool fp32_logits, int H, int W) const;
+};
+
 class UNet {
  public:
   UNet(int in_channels, int classes, int dtype);
@@ -87,7 +117,7 @@ class UNet {
 
   // stage entry points; features cross the boundary as NCHW fp32 only in the split path
   int forward(const float* params, float* buffers, const float* x_nchw, float* logits_nchw, int B, int H, int W,
-              int training, void* ws, size_t ws_bytes, hipStream_t s);
+              int training, void* ws, size_t ws_bytes, hipStream_t s, const FwdOpts& o);
   // stage_events: optional 7 hipEvent_t recorded on `s` as soon as the gradients of stage k
   // (6 head, 5 decoder, 4..1 encoder layers, 0 stem) are complete — lets the host overlap the
   // bucketed RCCL all-reduce with the rest of the backward pass.
@@ -107,36 +137,9 @@ class UNet {
   int encoder_backward(const float* params, const float* const dfeats_nchw[5], float* grads, void* ws,
                        size_t ws_bytes, hipStream_t s);
 
-  // Inference with constant weights: when the caller vouches that parameters and buffers are unchanged since the previous
-  // eval-mode forward on this handle, the next eval-mode forward with the same arena, shape, params and buffers addresses skips the weight pack and
-  // the 46 BatchNorm-coefficient launches (both still sit in the arena at the same offsets).  One-shot: cleared by forward.
-  void reuse_constants(bool on) { reuse_req_ = on; }
   // every entry point other than forward() lays the arena out differently (the split path re-imports five feature tensors
-  // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone, and so are pending
-  // one-shot requests
-  void invalidate_reuse() {
-    last_valid_ = false; last_params_ = nullptr; last_buffers_ = nullptr; reuse_req_ = false; preds_req_ = nullptr; maxprob_req_ = nullptr; ce_req_ = CeReq(); rowvec_req_ = nullptr;
-    rowvec_train_req_ = nullptr; drows_req_ = nullptr;
-  }
-  // the next forward without fp32 logits writes argmax predictions [B][H][W] uint8 here (one-shot, like reuse_constants)
-  void want_preds(unsigned char* p, float* maxprob) { preds_req_ = p; maxprob_req_ = maxprob; }
-  // the next eval-mode forward without fp32 logits evaluates the per-pixel head of step() on its logits (one-shot): weighted CE
-  // mean -> loss, argmax -> preds (optional), confmat += bincount (optional); ws: ce_workspace_floats(B, H, W) floats
-  struct CeReq {
-    const void* labels = nullptr; int kind = 0; const float* weight = nullptr;
-    float* loss = nullptr; unsigned char* preds = nullptr; long long* confmat = nullptr; float* ws = nullptr;
-  };
-  void want_ce(const CeReq& r) { ce_req_ = r; }
-  // the next eval-mode forward adds v (fp32 [B][H/32], device) to the bottleneck feature f_[5] between the encoder and the decoder
-  // (one-shot): element [b][h][w][c] += v[b][h], the metadata fusion of model.py:59-60.  In eval mode every unit materialises its
-  // output and f_[5] is read by decoder block 0 alone, so the add happens in place; the arena layout does not change
-  void want_rowvec(const float* v) { rowvec_req_ = v; }
-  // the training form (one-shot): the next training forward hands the decoder a SECOND tensor, f5m = T(float(f_[5]) + v), and leaves
-  // f_[5] alone — it is the ReLU mask source of layer4's last block in the backward (bn_backward, the bnr_out of a residual producer),
-  // and out + v reads as "ReLU on" wherever out == 0 < v.  The backward of that forward writes dv[b][h] = sum over w, c of the gradient
-  // that reaches f5m (complete and unmasked after the decoder's backward: nothing produces f5m, so no data-gradient epilogue masks
-  // it) and hands that buffer to the encoder as the gradient of f_[5] (d f5m / d f_[5] is the identity)
-  void want_rowvec_train(const float* v, float* dv) { rowvec_train_req_ = v; drows_req_ = dv; }
+  // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone
+  void invalidate_reuse() { last_valid_ = false; last_params_ = nullptr; last_buffers_ = nullptr; }
   void* last_dlogits_nhwc() const { return dl_nhwc_; }
   const void* logits_nhwc() const { return logits_nhwc_; }
   int head_ld() const { return convs.back().Cout_p; }
@@ -163,7 +166,7 @@ class UNet {
   int enc_units_end_ = 0, dec_units_begin_ = 0;
   size_t fwd_top_ = 0;      // arena top after forward (backward scratch starts here)
   bool packed_d_ = false;
-  bool reuse_req_ = false, reuse_ = false, last_valid_ = false;
+  bool reuse_ = false, last_valid_ = false;
   const void* last_ws_ = nullptr;
   const void* last_params_ = nullptr;   // the flat buffers the packed weights / BatchNorm coefficients in the arena came from
   const void* last_buffers_ = nullptr;
@@ -178,14 +181,8 @@ class UNet {
   hipEvent_t join_ev_ = nullptr;
   size_t fork_next_ = 0;
   bool side_pending_ = false;
-  unsigned char* preds_req_ = nullptr;
-  float* maxprob_req_ = nullptr;
-  CeReq ce_req_;
-  const float* rowvec_req_ = nullptr;
-  const float* rowvec_train_req_ = nullptr;
-  float* drows_req_ = nullptr;
   Act f5m_;                         // the decoder's bottleneck input of the last training forward with rows, for its backward
-  float* drows_pending_ = nullptr;  // where that backward writes the row sums; cleared once written and by every later forward
+  float* drows_pending_ = nullptr;  // where that backward writes the row sums; cleared once written and by every later forward that runs
   bool side_init();
   hipStream_t wgrad_stream();     // forks the side stream behind everything queued on s_ so far
   int side_cus() const;           // WgradArgs::cus of a launch on the side stream
@@ -225,7 +222,7 @@ class UNet {
   bool lazy_into_hg(const Act& y, int cons, bool up0, const Act& skip) const;
   void encoder_fwd_impl(const float* x_nchw);
   void decoder_fwd_impl();
-  void head_fwd_impl(float* logits_nchw);
+  void head_fwd_impl(float* logits_nchw, const FwdOpts& o);
   void unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bool need_dgrad, void* dx_override,
                      bool upcat = false);
   void head_bwd_impl(const void* dl);

@@ -402,7 +402,7 @@ void UNet::decoder_fwd_impl() {
   dec_out_ = x;
 }
 
-void UNet::head_fwd_impl(float* logits_nchw) {
+void UNet::head_fwd_impl(float* logits_nchw, const FwdOpts& o) {
   const ConvDesc& c = convs.back();
   Act none;
   ConvArgs a;
@@ -419,11 +419,9 @@ void UNet::head_fwd_impl(float* logits_nchw) {
     if (!dry_) { a.out = logits_nhwc_; a.out_ld = c.Cout_p; a.out_nchw = nullptr; }
   }
   a.bias = params_ + c.b_off;
-  unsigned char* preds = (!logits_nchw && !training_) ? preds_req_ : nullptr;
-  float* maxprob = preds ? maxprob_req_ : nullptr;
-  preds_req_ = nullptr; maxprob_req_ = nullptr;
-  const CeReq ce = ce_req_;   // (forward() lets it through for eval-mode calls without fp32 logits only)
-  ce_req_ = CeReq();
+  unsigned char* preds = (!logits_nchw && !training_) ? o.preds : nullptr;
+  float* maxprob = preds ? o.maxprob : nullptr;
+  const FwdOpts::Ce& ce = o.ce;   // (FwdOpts::refusal lets it through for eval-mode calls without fp32 logits only)
   if (ce.labels && !dry_) {
     // validation: loss term, argmax and confusion-matrix increment in the head convolution's register epilogue, between the label
     // pass and the fp64 sum of ce_head (the logits never reach HBM); otherwise the head convolution to NHWC logits and ce_head on
@@ -466,31 +464,26 @@ void UNet::head_fwd_impl(float* logits_nchw) {
     RUN(softmax_argmax_nhwc(logits_nhwc_, dtype, c.Cout_p, dec_out_.rows(), c.Cout, preds, nullptr, maxprob, s_));
 }
 
-int UNet::forward(const float* params, float* buffers, const float* x_nchw, float* logits_nchw, int B, int H, int W,
-                  int training, void* ws, size_t ws_bytes, hipStream_t s) {
-  // one-shot requests are consumed on EVERY path out of this call (a refused shape must not leave pointers to the caller's
-  // already freed tensors behind for the next forward without logits)
-  unsigned char* const preds_now = preds_req_;
-  float* const maxprob_now = maxprob_req_;
-  const bool reuse_now = reuse_req_;
-  const CeReq ce_now = ce_req_;
-  const float* const rowvec_now = rowvec_req_;
-  const float* const rows_train_now = rowvec_train_req_;
-  float* const drows_now = drows_req_;
-  preds_req_ = nullptr; maxprob_req_ = nullptr; reuse_req_ = false; ce_req_ = CeReq(); rowvec_req_ = nullptr;
-  rowvec_train_req_ = nullptr; drows_req_ = nullptr;
-  f5m_ = Act(); drows_pending_ = nullptr;   // (a backward belongs to the forward just before it)
+int FwdOpts::refusal(int training, bool fp32_logits, int H, int W) const {
+  if ((maxprob && !preds) || (drows && !rows)) return -1;
+  if (ce.labels && (!ce.loss || !ce.ws || ce.kind < 0 || ce.kind > 3)) return -1;
   // two heads asked of one forward, or the CE head of a forward that is not an eval-mode one without fp32 logits
-  if (ce_now.labels && (preds_now || training || logits_nchw)) return -15;
-  // the in-place add is for eval-mode forwards: in a training forward f_[5] is still needed as it is (the ReLU mask source of the
-  // unit that produced it), which is what the training request below is for
-  if (rowvec_now && training) return -16;
-  if (rows_train_now && !training) return -17;
+  if (ce.labels && (preds || training || fp32_logits)) return -15;
+  // in a training forward f_[5] is still needed as it is (the ReLU mask source of the unit that produced it): the rows go into a
+  // second tensor, whose gradient somebody has to take
+  if (rows && training && !drows) return -16;
+  if (drows && !training) return -17;
   if ((H % 32) || (W % 32)) return -10;
+  return 0;
+}
+
+int UNet::forward(const float* params, float* buffers, const float* x_nchw, float* logits_nchw, int B, int H, int W,
+                  int training, void* ws, size_t ws_bytes, hipStream_t s, const FwdOpts& o) {
+  if (const int rc = o.refusal(training, logits_nchw != nullptr, H, W)) return rc;
+  f5m_ = Act(); drows_pending_ = nullptr;   // (a backward belongs to the forward just before it)
   // (the caller vouches for the CONTENTS of params / buffers; other addresses are other tensors, whatever it believes)
-  reuse_ = reuse_now && !training && last_valid_ && ws == last_ws_ && params == last_params_ && buffers == last_buffers_ &&
+  reuse_ = o.reuse_constants && !training && last_valid_ && ws == last_ws_ && params == last_params_ && buffers == last_buffers_ &&
            B == last_B_ && H == last_H_ && W == last_W_;
-  preds_req_ = preds_now; maxprob_req_ = maxprob_now; ce_req_ = ce_now;   // consumed by head_fwd_impl below
   begin(ws, ws_bytes, s, false);
   fwd_common_begin(params, buffers, B, H, W, training);
   const int lazy_env = tune("FLAIR_LAZY_BN", 1);
@@ -499,18 +492,18 @@ int UNet::forward(const float* params, float* buffers, const float* x_nchw, floa
   if (!reuse_) pack_forward_weights();
   encoder_fwd_impl(x_nchw);
   // metadata fusion (model.py:59-60): f_[5] is the materialised output of layer4's last block, read by decoder block 0 only
-  if (rowvec_now) RUN(add_rowvec_nhwc(dtype, f_[5].p, rowvec_now, f_[5].N, f_[5].H, f_[5].W, f_[5].C, s_));
+  if (o.rows && !training) RUN(add_rowvec_nhwc(dtype, f_[5].p, o.rows, f_[5].N, f_[5].H, f_[5].W, f_[5].C, s_));
   const Act f5 = f_[5];
-  if (rows_train_now) {
+  if (o.rows && training) {
     // training: the decoder reads a second tensor (the swap decoder_forward does with dec_in_), f_[5] stays for the backward
     f5m_ = alloc_act(f5.N, f5.H, f5.W, f5.C);
-    RUN(add_rowvec_nhwc_to(dtype, f5.p, rows_train_now, f5m_.p, f5.N, f5.H, f5.W, f5.C, s_));
+    RUN(add_rowvec_nhwc_to(dtype, f5.p, o.rows, f5m_.p, f5.N, f5.H, f5.W, f5.C, s_));
     f_[5] = f5m_;
-    drows_pending_ = drows_now;
+    drows_pending_ = o.drows;
   }
   decoder_fwd_impl();
   f_[5] = f5;
-  head_fwd_impl(logits_nchw);
+  head_fwd_impl(logits_nchw, o);
   fwd_top_ = top_;
   reuse_ = false;
   last_valid_ = !training && !err_;   // (a training forward lays the arena out differently)
@@ -563,7 +556,7 @@ int UNet::head_forward(const float* params, const float* x_nchw, float* logits_n
   Act x = alloc_act(B, H, W, 16);
   RUN(nchw_f32_to_nhwc(dtype, x_nchw, x.p, B, 16, H, W, 16, s_));
   dec_out_ = x;
-  head_fwd_impl(logits_nchw);
+  head_fwd_impl(logits_nchw, FwdOpts());
   fwd_top_ = top_;
   return err_;
 }
@@ -997,7 +990,7 @@ size_t UNet::plan_bytes(int B, int H, int W, int training) {
   decoder_fwd_impl();
   for (int i = 1; i <= 5; ++i) f_[i] = saved[i];
   dec_out_ = alloc_act(B, H, W, 16);
-  head_fwd_impl(nullptr);
+  head_fwd_impl(nullptr, FwdOpts());
   if (training) {
     alloc((size_t)dec_out_.rows() * convs.back().Cout_p * dtype_size(dtype));
     grads_ = nullptr;

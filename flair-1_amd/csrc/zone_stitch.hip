@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void blend_flush_kernel(float* __restrict__ ri
   }
 }
 
-// preds != null: the (class, probability) maps of flair_unet_want_preds; otherwise softmax + first argmax of the logits
+// preds != null: the (class, probability) maps of flair_unet_fwd_opts_t::preds_u8; otherwise softmax + first argmax of the logits
 template <class SRC>
 __global__ __launch_bounds__(256) void stitch_max_kernel(const float* __restrict__ logits, const unsigned char* __restrict__ preds,
                                                          const float* __restrict__ maxprob, int B, int C, int S, int margin,

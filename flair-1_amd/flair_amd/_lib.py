@@ -30,7 +30,7 @@ PROTOTYPES = {
                                      C.POINTER(i32), C.POINTER(i32)]),
     "flair_unet_stage_range": (i32, [vp, i32, C.POINTER(i64), C.POINTER(i64)]),
     "flair_unet_workspace_bytes": (i64, [vp, i32, i32, i32, i32]),
-    "flair_unet_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]),
+    "flair_unet_forward": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp, vp]),
     "flair_unet_backward": (i32, [vp, vp, vp, vp, vp, vp, sz, vp, C.POINTER(vp)]),
     "flair_unet_head_ld": (i32, [vp]),
     "flair_unet_encoder_forward": (i32, [vp, vp, vp, vp, C.POINTER(vp), i32, i32, i32, i32, vp, sz, vp]),
@@ -109,11 +109,6 @@ PROTOTYPES = {
                                    C.POINTER(C.c_double)]),
     "flair_metadata_mlp_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "flair_metadata_mlp_backward": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]),
-    "flair_unet_reuse_constants": (i32, [vp, i32]),
-    "flair_unet_want_preds": (i32, [vp, vp, vp]),
-    "flair_unet_want_ce": (i32, [vp, vp, i32, vp, vp, vp, vp, vp]),
-    "flair_unet_want_rowvec": (i32, [vp, vp]),
-    "flair_unet_want_rowvec_train": (i32, [vp, vp, vp]),
     "flair_detect_stitch_preds": (i32, [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp]),
     "flair_detect_blend_accum": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_detect_blend_flush": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, vp]),
@@ -149,6 +144,14 @@ PROTOTYPES = {
     "flair_tune_set": (i32, [C.c_char_p, i32]),
     "flair_debug_buffer": (i32, [vp]),
 }
+
+
+class UnetFwdOpts(C.Structure):
+    """flair_unet_fwd_opts_t: the last argument of flair_unet_forward (by reference; None = a plain forward)"""
+    _fields_ = [("reuse_constants", i32), ("preds_u8", vp), ("maxprob_f32", vp),
+                ("ce_labels", vp), ("ce_label_kind", i32), ("ce_class_weight", vp), ("ce_loss", vp),
+                ("ce_preds_u8", vp), ("ce_confmat", vp), ("ce_workspace", vp),
+                ("rows_f32", vp), ("drows_f32", vp)]
 
 
 class ConvEx(C.Structure):

@@ -7,7 +7,7 @@ Same constructor argument (the YAML config dict), same attributes (``seg_model``
   * the metadata broadcast ``x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16)`` + ``torch.add``
     (model.py:59-60; element [b,c,h,w] += x_enc[b,h]) runs as one in-place HIP kernel on a copy of feats[-1]
     instead of materialising the (B,512,16,16) repeat; with an eval-mode ``seg_model`` the add happens inside ONE native forward
-    (``Unet.eval_logits(x, bottleneck_rows=x_enc)``, flair_unet_want_rowvec) on the executor's own NHWC bottleneck — no fp32 NCHW
+    (``Unet.eval_logits(x, bottleneck_rows=x_enc)``, rows_f32 of flair_unet_fwd_opts_t) on the executor's own NHWC bottleneck — no fp32 NCHW
     round trip of the features, constants reused, HIP-graph replay at small batches; FLAIR_META_FUSE=0 (read per call) keeps the
     three-call split path, which a training-mode ``seg_model`` always takes;
   * the HuggingFace provider branch (model.py:43-50,66-68) builds SegFormer-MiT and 3-channel UperNet-Swin natively

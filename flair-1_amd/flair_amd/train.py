@@ -150,7 +150,7 @@ class SegTrainer:
 
         ``mtd``: (B,45) metadata vectors (BASELINE config 4, model.py:57-62).  ``metadata_encoder`` encodes them in whatever mode it
         is in — the trainer never switches it — and the encoding is added to the bottleneck inside the one native training forward
-        (flair_unet_want_rowvec_train); the native backward returns its gradient, which goes through the MetadataMLP's own backward
+        (rows_f32 + drows_f32 of flair_unet_fwd_opts_t); the native backward returns its gradient, which goes through the MetadataMLP's own backward
         kernel, and the MLP's six tensors take the same SGD step as the U-Net's (tasks_utils.py:95 hands the optimizer
         ``model.parameters()``, the MLP included); their ``.grad`` is None afterwards.  ``mtd_masks``: the three dropout masks of
         MetadataMLP.forward — "auto" draws them from torch's generator when the encoder is in training mode (none in eval mode),
@@ -273,11 +273,11 @@ class SegTrainer:
     def validate_step(self, img, labels, mtd=None):
         """validation_step of the reference (task_module.py:104-109) on the eval handle and the eval workspace, with the
         running statistics whatever ``model.training`` says: one native call, the loss term, the argmax and the confusion
-        matrix increment come out of the head convolution's epilogue (flair_unet_want_ce).  img / labels as for train_step.
+        matrix increment come out of the head convolution's epilogue (the ce_ fields of flair_unet_fwd_opts_t).  img / labels as for train_step.
         Returns this batch's device scalar loss (no host sync), adds it to the running mean and the batch's confusion matrix to
         ``val_confmat``; the predictions stay in ``_val_preds``.  No parameter, buffer or training activation is touched.
         ``mtd``: (B,45) metadata vectors, encoded by ``metadata_encoder`` without dropout and added to the bottleneck inside the
-        same native call (flair_unet_want_rowvec)."""
+        same native call (rows_f32)."""
         with torch.cuda.device(self.grads.device):
             return self._validate_step(img, labels, self._meta_rows(img, mtd))
 

@@ -480,13 +480,9 @@ class Unet(nn.Module):
                 # thread_local: another thread of the process (a DataLoader's pin-memory thread allocating page-locked memory)
                 # may call the runtime while this one captures; under the default mode that call fails and the capture with it
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    L.check(l.flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
-                    if preds is not None:
-                        L.check(l.flair_unet_want_preds(h, L.ptr(ent["preds"]), L.ptr(ent["prob"])), "flair_unet_want_preds")
-                    if rows is not None:
-                        L.check(l.flair_unet_want_rowvec(h, L.ptr(ent["rows"])), "flair_unet_want_rowvec")
+                    opts = self._fwd_opts(True, ent["preds"], ent["prob"], None, ent["rows"], None)
                     L.check(l.flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(ent["x"]), L.ptr(ent["logits"]), B, H, W, 0,
-                                                 L.ptr(ws), ws.numel(), L.stream()), "flair_unet_forward")
+                                                 L.ptr(ws), ws.numel(), L.stream(), C.byref(opts)), "flair_unet_forward")
             except Exception as e:
                 # nothing ran (capture records); the caller runs this same call eagerly, and this kind of call stays eager until
                 # the key changes
@@ -505,17 +501,30 @@ class Unet(nn.Module):
                 prob.copy_(ent["prob"])
         return None if ent["logits"] is None else ent["logits"].clone()
 
+    @staticmethod
+    def _fwd_opts(reuse, preds, prob, ce, rows, train_rows):
+        """The flair_unet_fwd_opts_t of one native forward.  It holds raw device pointers: the caller keeps the tensors alive."""
+        o = L.UnetFwdOpts(reuse_constants=int(reuse))
+        if preds is not None:
+            o.preds_u8, o.maxprob_f32 = L.ptr(preds), L.ptr(prob)
+        if ce is not None:
+            o.ce_labels, o.ce_label_kind, o.ce_class_weight, o.ce_loss, o.ce_preds_u8, o.ce_confmat, o.ce_workspace = ce
+        if train_rows is not None:
+            rows, o.drows_f32 = train_rows[0], L.ptr(train_rows[1])
+        o.rows_f32 = L.ptr(rows)
+        return o
+
     @_on_model_device
     def _c_forward(self, x, training, want_logits=True, preds=None, prob=None, ce=None, rows=None, train_rows=None):
         """want_logits=False (fused trainer): the head's output stays in the workspace as NHWC rows of the compute dtype
         (flair_unet_logits_nhwc) and no fp32 NCHW tensor is produced; returns None.  preds / prob (eval mode, no logits): uint8
-        argmax and its fp32 probability from the head convolution's epilogue (flair_unet_want_preds).  ce (eval mode, no
-        logits): the arguments of flair_unet_want_ce behind the handle — the validation head in the same call; such a forward
+        argmax and its fp32 probability from the head convolution's epilogue (flair_unet_fwd_opts_t::preds_u8).  ce (eval mode, no
+        logits): the seven ce_ fields of flair_unet_fwd_opts_t in their order — the validation head in the same call; such a forward
         always runs eagerly (never captured, not counted towards the captures of the plain paths).  rows (eval mode only): fp32
         (B, H/32) added to the bottleneck feature between encoder and decoder, element [b,c,h,w] += rows[b,h]
-        (flair_unet_want_rowvec) — the metadata fusion of model.py:57-62 inside the one native call; combines with all of the above.
+        (rows_f32 of the options) — the metadata fusion of model.py:57-62 inside the one native call; combines with all of the above.
         train_rows (training mode only, excludes rows): a pair (rows, drows) of fp32 (B, H/32) tensors — the same add in a training
-        forward, out of place (flair_unet_want_rowvec_train); the _c_backward of this forward writes d loss / d rows into drows."""
+        forward, out of place (rows_f32 + drows_f32); the _c_backward of this forward writes d loss / d rows into drows."""
         x = self._prep(x)
         B, _, H, W = x.shape
         if train_rows is not None:
@@ -559,29 +568,20 @@ class Unet(nn.Module):
                     if out is not self._NOT_CAPTURED:
                         return out
                     # a capture that broke inside the native call has advanced the executor's host state without running a kernel:
-                    # withdraw the reuse request and pack again (the output requests below replace the capture's own)
-                    L.check(L.lib().flair_unet_reuse_constants(h, 0), "flair_unet_reuse_constants")
+                    # pack again
                     repack = True
         logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
-        if preds is not None:
-            L.check(L.lib().flair_unet_want_preds(h, L.ptr(preds), L.ptr(prob)), "flair_unet_want_preds")
-        if ce is not None:
-            L.check(L.lib().flair_unet_want_ce(h, *ce), "flair_unet_want_ce")
-        if rows is not None:
-            L.check(L.lib().flair_unet_want_rowvec(h, L.ptr(rows)), "flair_unet_want_rowvec")
-        if train_rows is not None:
-            L.check(L.lib().flair_unet_want_rowvec_train(h, L.ptr(train_rows[0]), L.ptr(train_rows[1])), "flair_unet_want_rowvec_train")
+        # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
+        # BatchNorm-coefficient launches while the key (_eval_cache_key) stands.  Writes through .data are invisible to it,
+        # as they are to autograd: weights_changed() is the call for those.
+        reuse = not training and self.__dict__.get("_eval_key") == key and not repack
+        opts = self._fwd_opts(reuse, preds, prob, ce, rows, train_rows)
         if not training:
-            # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
-            # BatchNorm-coefficient launches while the key (_eval_cache_key) stands.  Writes through .data are invisible to it,
-            # as they are to autograd: weights_changed() is the call for those.
-            if self.__dict__.get("_eval_key") == key and not repack:
-                L.check(L.lib().flair_unet_reuse_constants(h, 1), "flair_unet_reuse_constants")
             self._eval_key = key
         else:
             self._native_writes = self.__dict__.get("_native_writes", 0) + 1
         L.check(L.lib().flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(x), L.ptr(logits), B, H, W,
-                                           int(training), L.ptr(ws), ws.numel(), L.stream()), "flair_unet_forward")
+                                           int(training), L.ptr(ws), ws.numel(), L.stream(), C.byref(opts)), "flair_unet_forward")
         if training:
             self._fwd_id += 1
             self._live_id = self._fwd_id

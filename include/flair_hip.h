@@ -43,10 +43,55 @@ int flair_unet_tensor_info(const flair_unet_t* h, int i, char* name, int name_ca
 int flair_unet_stage_range(const flair_unet_t* h, int stage, int64_t* begin, int64_t* end);
 int64_t flair_unet_workspace_bytes(flair_unet_t* h, int B, int H, int W, int training);
 
+/* Options of ONE flair_unet_forward.  The struct is read during the call and nothing of it is kept: what a forward does depends on
+ * its own arguments only, never on an earlier call.  Every pointer is a device pointer; the outputs (preds_u8, maxprob_f32, ce_loss,
+ * ce_preds_u8, ce_confmat, ce_workspace) must stay valid until the enqueued work has run, drows_f32 until the flair_unet_backward of
+ * this forward has run.  A zeroed struct, like opts == NULL, asks for nothing.  Malformed options (below) return -1, combinations a
+ * forward cannot serve -15 / -16 / -17, all of them before anything is enqueued or the handle is touched. */
+typedef struct flair_unet_fwd_opts {
+  /* Inference with constant weights (zone_detect's window loop, predict): a promise that `params` and `buffers` are bit-identical
+   * to those of the previous eval-mode flair_unet_forward on this handle.  Honoured only if this is an eval-mode forward with the
+   * same workspace, shape and `params` / `buffers` pointers and no other call on the handle came between: it then skips re-packing
+   * the weights and re-deriving the 46 BatchNorm affine pairs (both are still in the workspace); with other pointers the promise
+   * cannot be about what was packed and the forward packs again.  The reference has no counterpart: PyTorch modules keep their
+   * weights in the layout they compute in. */
+  int reuse_constants;
+  /* uint8 argmax predictions [B][H][W] — predict_step's argmax(softmax(logits)), task_module.py:206-213 — from the head
+   * convolution's epilogue; the logits are then not kept (flair_unet_logits_nhwc returns NULL until the next forward).  Used only
+   * by a forward with training = 0 and logits_nchw = NULL; any other forward ignores both fields.  maxprob_f32 (optional, needs
+   * preds_u8): the winner's softmax probability, fp32 [B][H][W]. */
+  uint8_t* preds_u8; float* maxprob_f32;
+  /* ce_labels != NULL: the head of step() on this forward's logits — task_module.py:71-79, tasks_utils.py:88-93, what
+   * validation_step needs: the weighted cross-entropy mean -> ce_loss, argmax(softmax) -> ce_preds_u8 (optional),
+   * ce_confmat[target][pred] += 1 (int64 [C][C], optional).  Labels and ce_label_kind (0..3) as for flair_ce_head; ce_workspace:
+   * flair_ce_workspace_bytes(B, H, W).  Where the head convolution's persistent kernel takes the shape — preds_u8's condition, and
+   * the head's 16 input channels materialised (not handed over as a lazy BatchNorm input, FLAIR_LAZY_BN >= 2) — and the tune key
+   * FLAIR_HEAD_CE is on (default off) all of it happens in that kernel's epilogue and the logits are not kept
+   * (flair_unet_logits_nhwc returns NULL); otherwise the same call runs the head convolution and flair_ce_head_nhwc's kernels on
+   * its NHWC logits.  Needs training = 0, logits_nchw = NULL and preds_u8 = NULL (-15 otherwise).  ce_labels == NULL: no CE
+   * head, the other ce_ fields are not read. */
+  const void* ce_labels; int ce_label_kind; const float* ce_class_weight; float* ce_loss;
+  uint8_t* ce_preds_u8; int64_t* ce_confmat; void* ce_workspace;
+  /* Bottleneck rows, fp32 (B, H/32): the metadata fusion of model.py:57-62 (x_enc of MetadataMLP; at 512 x 512 tiles H/32 = 16 =
+   * its width) without leaving the fused forward, element [b][c][h][w] of the encoder's last feature + rows[b][h].  Combines with
+   * everything above.  training = 0: added in place between the encoder and the decoder (flair_add_rowvec_nhwc).  training = 1:
+   * the decoder reads a second tensor, dtype(float(f5) + rows[b][h]) (flair_add_rowvec_nhwc_to; f5 itself stays, it is the ReLU
+   * mask source of layer4's last block), and drows_f32 is required (-16 without it); the workspace size and layout bound of
+   * flair_unet_workspace_bytes hold. */
+  const float* rows_f32;
+  /* Training forwards only (-17 otherwise), needs rows_f32: the flair_unet_backward of this forward writes
+   * drows_f32[b][h] = sum over c, w of the gradient reaching the second tensor (flair_rowvec_grad_nhwc) before it walks the
+   * encoder.  The handle keeps this one pointer from the forward to its backward; any later forward that is
+   * not refused drops it. */
+  float* drows_f32;
+} flair_unet_fwd_opts_t;
+
 /* seg_model(x)  — model.py:64 (and zone_detect/compare.py:31).  training != 0: BatchNorm batch
- * statistics + running-stat update in `buffers`, activations kept in `workspace` for backward. */
+ * statistics + running-stat update in `buffers`, activations kept in `workspace` for backward.
+ * opts: what else this forward does (above); NULL = a plain forward. */
 int flair_unet_forward(flair_unet_t* h, const float* params, float* buffers, const float* x_nchw, float* logits_nchw,
-                       int B, int H, int W, int training, void* workspace, size_t workspace_bytes, void* stream);
+                       int B, int H, int W, int training, void* workspace, size_t workspace_bytes, void* stream,
+                       const flair_unet_fwd_opts_t* opts);
 /* autograd backward of the call above (Lightning's loss.backward(), task_module.py:82-86).
  * Exactly one of dlogits_nchw (fp32 (B,C,H,W)) / dlogits_nhwc (as written by flair_ce_head with
  * flair_unet_head_ld) is non-null.  Writes every parameter gradient into `grads` (flat, OIHW).
@@ -57,41 +102,6 @@ int flair_unet_backward(flair_unet_t* h, const float* params, const float* dlogi
                         float* grads, void* workspace, size_t workspace_bytes, void* stream,
                         void* const* stage_events);
 int flair_unet_head_ld(const flair_unet_t* h);
-/* Inference with constant weights (zone_detect's window loop, predict): a one-shot promise that `params` and `buffers` are
- * bit-identical to those of the previous eval-mode flair_unet_forward on this handle.  If the next eval-mode forward also
- * uses the same workspace, shape and `params` / `buffers` pointers, it skips re-packing the weights and re-deriving the 46
- * BatchNorm affine pairs (both are still in the workspace); with other pointers the promise cannot be about what was packed
- * and the forward packs again; any other call clears the promise.  The reference has no counterpart: PyTorch modules keep
- * their weights in the layout they compute in. */
-int flair_unet_reuse_constants(flair_unet_t* h, int on);
-/* One-shot: the next flair_unet_forward with training = 0 and logits = NULL writes uint8 argmax predictions [B][H][W] to preds_u8
- * (device pointer) — predict_step's argmax(softmax(logits)), task_module.py:206-213 — from the head convolution's epilogue; the
- * logits are then not kept (flair_unet_logits_nhwc returns NULL until the next forward). */
-int flair_unet_want_preds(flair_unet_t* h, uint8_t* preds_u8, float* maxprob_f32 /* optional: the winner's softmax probability */);
-/* One-shot: the next flair_unet_forward with training = 0 and logits = NULL evaluates the head of step() on its logits —
- * task_module.py:71-79, tasks_utils.py:88-93, what validation_step needs: the weighted cross-entropy mean -> loss, argmax(softmax) ->
- * preds_u8, confmat[target][pred] += 1 (int64 [C][C]).  Labels as for flair_ce_head.  Where the head convolution's persistent kernel takes
- * the shape — flair_unet_want_preds's condition, and the head's 16 input channels materialised (not handed over as a lazy
- * BatchNorm input, FLAIR_LAZY_BN >= 2) — and the tune key FLAIR_HEAD_CE is on (default off) all of it happens in that kernel's epilogue and the logits are not kept
- * (flair_unet_logits_nhwc returns NULL); otherwise the same call runs the head convolution and flair_ce_head_nhwc's kernels on its
- * NHWC logits.  All pointers are device pointers that must stay valid until that forward has run.  A forward that also holds a
- * flair_unet_want_preds request, trains or returns fp32 logits is refused (-15); the request is dropped by any forward. */
-int flair_unet_want_ce(flair_unet_t* h, const void* labels, int label_kind, const float* class_weight, float* loss,
-                       uint8_t* preds_u8 /* optional */, int64_t* confmat /* optional */,
-                       void* ce_workspace /* flair_ce_workspace_bytes(B, H, W) */);
-/* One-shot: the next flair_unet_forward with training = 0 adds rows_f32 (device, fp32 (B, H/32)) to the bottleneck feature between the
- * encoder and the decoder, element [b][c][h][w] += rows[b][h] — the metadata fusion of model.py:57-62 (x_enc of MetadataMLP; at 512 x 512
- * tiles H/32 = 16 = its width) without leaving the fused forward.  Combines with flair_unet_reuse_constants, fp32 logits,
- * flair_unet_want_preds and flair_unet_want_ce.  A training forward that meets the request is refused (-16); the request is dropped by
- * any forward. */
-int flair_unet_want_rowvec(flair_unet_t* h, const float* rows_f32);
-/* The training form, one-shot like the others: the next flair_unet_forward with training = 1 feeds the decoder a second bottleneck
- * tensor, dtype(float(f5) + rows[b][h]) (flair_add_rowvec_nhwc_to; f5 itself stays, it is the ReLU mask source of layer4's last block),
- * and the flair_unet_backward of that forward writes drows_f32[b][h] = sum over c, w of the gradient reaching that tensor
- * (flair_rowvec_grad_nhwc) before it walks the encoder.  Both are device fp32 (B, H/32) and must stay valid until that backward has
- * run.  The workspace size and layout bound of flair_unet_workspace_bytes hold.  An eval-mode forward that meets the request is
- * refused (-17) and runs nothing; the request is dropped by any forward, a pending drows by any later forward. */
-int flair_unet_want_rowvec_train(flair_unet_t* h, const float* rows_f32, float* drows_f32);
 
 /* seg_model.encoder(x) / .decoder(*feats) / .segmentation_head(t) — the metadata path model.py:57-62.
  * feats[i] = feature i+1 of the encoder, NCHW fp32: (B,64,H/2,W/2) ... (B,512,H/32,W/32). */
@@ -189,7 +199,7 @@ int flair_gather_tiles(const uint8_t* raster_u8, int bands, int raster_h, int ra
                        const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
                        float* img_out, void* stream);
 /* flair_detect_stitch_preds: convert('argmax') + stitch (dataset.py:23-30, main.py:404-421) from the per-window class / probability maps
- * flair_unet_want_preds leaves, instead of from logits: raster_out (2, raster_h, raster_w) fp32 = [class, its softmax probability]. */
+ * flair_unet_fwd_opts_t::preds_u8 / maxprob_f32 leave, instead of from logits: raster_out (2, raster_h, raster_w) fp32 = [class, its softmax probability]. */
 int flair_detect_stitch_preds(const uint8_t* preds_u8, const float* maxprob_f32, int B, int S, int margin, const int32_t* tiles,
                               float* raster_out, int raster_h, int raster_w, void* stream);
 int flair_detect_stitch(const float* logits_nchw, int B, int C, int S, int margin, int output_type, const int32_t* tiles,
@@ -205,7 +215,7 @@ int flair_detect_stitch(const float* logits_nchw, int B, int C, int S, int margi
  * flair_detect_blend_flush: ring columns of raster columns [x_lo, x_hi) (x_hi - x_lo <= ring_cols), every row: where plane C
  *   is > 0, raster_out (2, raster_h, raster_w) fp32 = [first argmax, max] of sum(w p) / sum(w); those ring entries are zeroed.
  * flair_detect_stitch_max(_preds): raster_out (2, raster_h, raster_w) fp32 holds a running [class, probability]; a window's
- *   (first argmax, its probability) — of softmax(logits), or the maps flair_unet_want_preds leaves — replaces it unless the
+ *   (first argmax, its probability) — of softmax(logits), or the maps a forward with preds_u8 / maxprob_f32 leaves — replaces it unless the
  *   held probability is strictly greater. */
 int flair_detect_blend_accum(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, const float* cheb_weights,
                              int x_lo, int x_hi, int y_lo, int y_hi, float* ring, int raster_h, int raster_w, void* stream);

@@ -1,7 +1,7 @@
 """Every writer of U-Net weights against every cache of the eval forward (case table: eval_cache_cases.py).
 
 ``flair_amd.Unet`` keeps two things between eval forwards: the packed weights and BatchNorm coefficients in the eval workspace, reused
-while one key stands (flair_unet_reuse_constants), and from the third identical call on a captured HIP graph, which has the addresses
+while one key stands (reuse_constants of flair_unet_fwd_opts_t), and from the third identical call on a captured HIP graph, which has the addresses
 of the flat parameter / buffer tensors baked in.  Each case arms one consumer of those caches, applies one writer, and compares the
 next three calls — a full pack, the reuse path, the re-captured graph — bit for bit (the bar the two older cache tests hold) with a
 COLD model: a fresh instance loaded from the written model's state_dict that runs once, without graphs.  That every writer changes
@@ -194,7 +194,7 @@ def test_writer_is_seen_by_consumer(dev, shared, writer, consumer, dtype, classe
 
 # ------------------------------------------------------------------------------------------------ the C ABI, no Python cache
 def test_native_reuse_request_is_refused_for_other_parameter_or_buffer_addresses(dev, shared):
-    """flair_unet_reuse_constants is a vouch for the CONTENTS behind the same pointers.  A caller that repeats it with another
+    """reuse_constants is a vouch for the CONTENTS behind the same pointers.  A caller that repeats it with another
     parameter or buffer tensor must get a full pack, not the previous tensor's packed weights / BatchNorm coefficients."""
     from flair_amd import _lib as L
     s = shared(13)
@@ -227,10 +227,9 @@ def test_native_reuse_request_is_refused_for_other_parameter_or_buffer_addresses
 
     def forward(h, P, F, arena, reuse):
         out = torch.empty(B, 13, H, W, dtype=torch.float32, device=dev)
-        if reuse:
-            L.check(l.flair_unet_reuse_constants(h, 1), "reuse_constants")
-        L.check(l.flair_unet_forward(h, L.ptr(P), L.ptr(F), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(arena), arena.numel(), L.stream()),
-                "flair_unet_forward")
+        opts = L.UnetFwdOpts(reuse_constants=int(reuse))
+        L.check(l.flair_unet_forward(h, L.ptr(P), L.ptr(F), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(arena), arena.numel(), L.stream(),
+                                     C.byref(opts)), "flair_unet_forward")
         return out
 
     try:
@@ -262,7 +261,7 @@ def _eager(m, x, calls=1):
 
 
 def test_failed_capture_falls_back_to_the_eager_call(dev, shared, monkeypatch):
-    """The first native call inside the capture raises: that call returns the eager bits, the graph key is marked and later
+    """The native call inside the capture raises: that call returns the eager bits, the graph key is marked and later
     calls run eagerly without another attempt."""
     from flair_amd import _lib as L
     s = shared(13)
@@ -270,16 +269,16 @@ def test_failed_capture_falls_back_to_the_eager_call(dev, shared, monkeypatch):
     x = s["inp"]["x"]
     want = _eager(m, x)
     m.weights_changed()
-    real = L.lib().flair_unet_reuse_constants
+    real = L.lib().flair_unet_forward
     attempts = []
 
-    def reuse_constants(h, on):
+    def forward(*args):
         if torch.cuda.is_current_stream_capturing() and not attempts:
-            attempts.append(on)
-            raise RuntimeError("planted: the first native call of the capture")
-        return real(h, on)
+            attempts.append(args[-1]._obj.reuse_constants)     # (opts arrives as ctypes.byref(struct))
+            raise RuntimeError("planted: the native call of the capture")
+        return real(*args)
 
-    monkeypatch.setattr(L.lib(), "flair_unet_reuse_constants", reuse_constants)
+    monkeypatch.setattr(L.lib(), "flair_unet_forward", forward)
     gkey = (True, False, False, False)
     with torch.no_grad():
         assert torch.equal(m(x), want) and torch.equal(m(x), want)

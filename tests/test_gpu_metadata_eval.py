@@ -1,4 +1,4 @@
-"""Metadata fusion in the native eval forward (flair_unet_want_rowvec): the row-vector add of model.py:59-60 on the executor's own NHWC
+"""Metadata fusion in the native eval forward (rows_f32 of flair_unet_fwd_opts_t): the row-vector add of model.py:59-60 on the executor's own NHWC
 bottleneck, between the encoder and the decoder of ONE flair_unet_forward, reachable from Unet (eval_logits / predict_classes),
 FLAIR_ModelFactory, segmentation_task_predict.predict_step and SegTrainer (validate_step / predict).
 
@@ -154,8 +154,10 @@ def test_fused_rows_equal_the_split_path(dev, small, dtype):
     assert torch.equal(m._c_forward(x, training=False), c["plain"])
 
 
-# ------------------------------------------------------------------------------------------------ 3. one-shot hygiene
+# ------------------------------------------------------------------------------------------------ 3. per-call hygiene
 def test_rowvec_request_is_one_shot_on_every_path(dev, small):
+    """The rows are an option of ONE call: a forward that was refused with them, or ran with them, leaves nothing for the next."""
+    import ctypes as C
     from flair_amd import _lib as L
     c = small("f32")
     m, x, v, plain = c["m"], c["x"], c["v"], c["plain"]
@@ -168,33 +170,79 @@ def test_rowvec_request_is_one_shot_on_every_path(dev, small):
         with_rows = m._c_forward(x, training=False, rows=v)
         key = m._eval_key
         again = m._c_forward(x, training=False)
-        assert m._eval_key == key                          # (same key: this forward ran with flair_unet_reuse_constants)
+        assert m._eval_key == key                          # (same key: this forward ran with reuse_constants = 1)
     assert torch.equal(again, plain) and not torch.equal(with_rows, plain)
-    # a request, a refused shape, a plain forward
+    # rows on a refused shape, then a plain forward
     ws = m._workspace(B, H, W, False)
     out = torch.empty_like(plain)
+    rows = L.UnetFwdOpts(rows_f32=L.ptr(v))
     with torch.cuda.device(dev):
-        L.check(l.flair_unet_want_rowvec(h, L.ptr(v)), "want_rowvec")
-        rc = l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, 48, W, 0, L.ptr(ws), ws.numel(), L.stream())
+        rc = l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, 48, W, 0, L.ptr(ws), ws.numel(), L.stream(),
+                                  C.byref(rows))
         assert rc == -10
         L.check(l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(ws), ws.numel(),
-                                     L.stream()), "forward")
+                                     L.stream(), None), "forward")
     assert torch.equal(out, plain)
-    # a request that meets a training forward: refused with the new code, dropped
+    # rows alone on a training forward: refused with its code, nothing runs and nothing is kept
     m._eval_key = None
     wst = m._workspace(B, H, W, True)
     buffers = m._flat_b.clone()
     with torch.cuda.device(dev):
-        L.check(l.flair_unet_want_rowvec(m._h, L.ptr(v)), "want_rowvec")
         rc = l.flair_unet_forward(m._h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 1, L.ptr(wst), wst.numel(),
-                                  L.stream())
-        assert rc == -16 and b"flair_unet_want_rowvec" in l.flair_strerror(rc)
+                                  L.stream(), C.byref(rows))
+        assert rc == -16 and b"rows_f32" in l.flair_strerror(rc)
         assert torch.equal(m._flat_b, buffers)             # nothing ran
         L.check(l.flair_unet_forward(m._h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(wst), wst.numel(),
-                                     L.stream()), "forward")
+                                     L.stream(), None), "forward")
     assert torch.equal(out, plain)
-    assert l.flair_unet_want_rowvec(h, None) == -1 and l.flair_unet_want_rowvec(None, L.ptr(v)) == -1
+    # a malformed struct (a gradient pointer without rows) and a null handle: -1, nothing runs
+    out.fill_(3.0)
+    bad = L.UnetFwdOpts(drows_f32=L.ptr(v))
+    with torch.cuda.device(dev):
+        assert l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(ws), ws.numel(),
+                                    L.stream(), C.byref(bad)) == -1
+        assert l.flair_unet_forward(None, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(ws), ws.numel(),
+                                    L.stream(), C.byref(rows)) == -1
+    assert torch.equal(out, torch.full_like(out, 3.0)) and torch.equal(m._flat_b, buffers)
     assert torch.equal(m._c_forward(x, training=False), plain)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_forward_options_are_read_not_consumed(dev, dtype):
+    """One struct (preds + maxprob + rows) serves two consecutive forwards alike, and a forward with opts = NULL on the same handle
+    does none of it: the struct is an argument, the handle keeps nothing of it."""
+    import ctypes as C
+    from flair_amd import _lib as L
+    _, m = _pair(5, 13, 23, dev, dtype)
+    _, untouched = _pair(5, 13, 23, dev, dtype)
+    m, untouched = m.eval(), untouched.eval()
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(1, 5, 64, 64, generator=g).to(dev)
+    v = torch.randn(1, 2, generator=g).to(dev)
+    m._c_forward(x, training=False)   # flat parameters, eval handle and workspace exist
+    l, h, ws = L.lib(), m._hh(False), m._workspace(1, 64, 64, False)
+    preds = torch.empty(1, 64, 64, dtype=torch.uint8, device=dev)
+    prob = torch.empty(1, 64, 64, dtype=torch.float32, device=dev)
+    opts = L.UnetFwdOpts(preds_u8=L.ptr(preds), maxprob_f32=L.ptr(prob), rows_f32=L.ptr(v))
+
+    def fwd(logits, opts):
+        preds.fill_(99)
+        prob.fill_(-1.0)
+        with torch.cuda.device(dev):
+            L.check(l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(logits), 1, 64, 64, 0, L.ptr(ws), ws.numel(),
+                                         L.stream(), None if opts is None else C.byref(opts)), "forward")
+        return preds.clone(), prob.clone()
+
+    first, second = fwd(None, opts), fwd(None, opts)
+    assert torch.equal(first[0], second[0]) and torch.equal(first[1], second[1])
+    assert int((first[0] >= 13).sum()) == 0 and bool(((first[1] > 0) & (first[1] <= 1)).all())      # written, every pixel
+    want = untouched.predict_classes(x, want_prob=True, bottleneck_rows=v)
+    assert torch.equal(first[0], want[0]) and torch.equal(first[1], want[1])                        # ... with the rows
+    logits = torch.empty(1, 13, 64, 64, dtype=torch.float32, device=dev)
+    for out in (None, logits):     # (without fp32 logits a forward that still held the pointers would use them)
+        after = fwd(out, None)
+        assert int((after[0] != 99).sum()) == 0 and bool((after[1] == -1.0).all())
+    assert torch.equal(logits, untouched._c_forward(x, training=False))                             # ... and no rows
 
 
 # ------------------------------------------------------------------------------------------------ 4. graph replay

@@ -1,13 +1,14 @@
 """Metadata in the native training step (BASELINE config 4): the bottleneck row add of model.py:59-60 inside ONE training forward
-(flair_unet_want_rowvec_train: a second tensor for the decoder, the encoder's output stays as the ReLU mask source of its unit), the
+(rows_f32 + drows_f32 of flair_unet_fwd_opts_t: a second tensor for the decoder, the encoder's output stays as the ReLU mask source of its unit), the
 gradient of the rows out of the native backward (flair_rowvec_grad_nhwc), and SegTrainer.train_step(img, labels, mtd), which also
 trains the MetadataMLP.
 
 Sections: 1 the two operators (exact integer sums, the any-order rounding bound, refusals), 2 the executor on the 2x5x160x128 batch
 of test_train_step_matches_oracle_elementwise_fp32 (zero rows are invisible bit for bit; large positive rows, which an in-place add
-would turn into wrong ReLU masks, against the CPU fp32 and fp64 oracles; one-shot hygiene; workspace), 3 SegTrainer at 512 x 512,
+would turn into wrong ReLU masks, against the CPU fp32 and fp64 oracles; per-call hygiene; workspace), 3 SegTrainer at 512 x 512,
 4 two ranks on one GPU."""
 import copy
+import ctypes as C
 import os
 import socket
 
@@ -260,10 +261,6 @@ def test_train_request_hygiene(dev, small):
     v = torch.full((2, 5), 2.0, device=dev)
     drows = torch.full((2, 5), 7.0, device=dev)
     sentinel = drows.clone()
-    # null arguments
-    assert l.flair_unet_want_rowvec_train(m._h, None, L.ptr(drows)) == -1
-    assert l.flair_unet_want_rowvec_train(m._h, L.ptr(v), None) == -1
-    assert l.flair_unet_want_rowvec_train(None, L.ptr(v), L.ptr(drows)) == -1
     # the Python argument
     with pytest.raises(RuntimeError, match="training-mode"):
         m._c_forward(x, training=False, train_rows=(v, drows))
@@ -281,26 +278,33 @@ def test_train_request_hygiene(dev, small):
     ws = m._workspace(B, H, W, False)
     out = torch.full_like(eval_plain, 3.0)
     buffers = m._flat_b.clone()
+    both = L.UnetFwdOpts(rows_f32=L.ptr(v), drows_f32=L.ptr(drows))
+
+    def fwd(handle, H_, training, arena, opts):
+        return l.flair_unet_forward(handle, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H_, W, training, L.ptr(arena),
+                                    arena.numel(), L.stream(), None if opts is None else C.byref(opts))
+
     with torch.cuda.device(dev):
-        L.check(l.flair_unet_want_rowvec_train(h, L.ptr(v), L.ptr(drows)), "want_rowvec_train")
-        rc = l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(ws), ws.numel(), L.stream())
-        assert rc == -17 and b"flair_unet_want_rowvec_train" in l.flair_strerror(rc)
+        rc = fwd(h, H, 0, ws, both)
+        assert rc == -17 and b"drows_f32" in l.flair_strerror(rc)
         torch.cuda.synchronize()
         assert torch.equal(out, torch.full_like(out, 3.0)) and torch.equal(m._flat_b, buffers) and torch.equal(drows, sentinel)
-        L.check(l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 0, L.ptr(ws), ws.numel(),
-                                     L.stream()), "forward")
+        # malformed structs: a gradient pointer without rows, in either mode, and a null handle
+        wst = m._workspace(B, H, W, True)
+        assert fwd(h, H, 0, ws, L.UnetFwdOpts(drows_f32=L.ptr(drows))) == -1
+        assert fwd(m._h, H, 1, wst, L.UnetFwdOpts(drows_f32=L.ptr(drows))) == -1
+        assert fwd(None, H, 1, wst, both) == -1
+        torch.cuda.synchronize()
+        assert torch.equal(out, torch.full_like(out, 3.0)) and torch.equal(m._flat_b, buffers) and torch.equal(drows, sentinel)
+        L.check(fwd(h, H, 0, ws, None), "forward")
     assert torch.equal(out, eval_plain)
     m._eval_key = None
-    # the old request still refuses a training forward with its own code
-    wst = m._workspace(B, H, W, True)
     with torch.cuda.device(dev):
-        L.check(l.flair_unet_want_rowvec(m._h, L.ptr(v)), "want_rowvec")
-        rc = l.flair_unet_forward(m._h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, H, W, 1, L.ptr(wst), wst.numel(), L.stream())
+        # rows without a gradient pointer still refuse a training forward with their own code
+        rc = fwd(m._h, H, 1, wst, L.UnetFwdOpts(rows_f32=L.ptr(v)))
         assert rc == -16
-        # the request, a refused shape, then a plain training forward + backward: the plain step, d rows not written
-        L.check(l.flair_unet_want_rowvec_train(m._h, L.ptr(v), L.ptr(drows)), "want_rowvec_train")
-        rc = l.flair_unet_forward(m._h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), L.ptr(out), B, 48, W, 1, L.ptr(wst), wst.numel(), L.stream())
-        assert rc == -10
+        # both on a refused shape, then a plain training forward + backward: the plain step, d rows not written
+        assert fwd(m._h, 48, 1, wst, both) == -10
     assert torch.equal(m._flat_b, buffers)
     assert _same_step(_hip_step(c), plain) == ALL_SAME
     assert torch.equal(drows, sentinel)

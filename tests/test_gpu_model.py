@@ -726,7 +726,7 @@ def test_metadata_mlp_kernel_matches_reference_module(dev):
 
 def test_constant_weight_reuse_in_eval_loops_is_invalidated_by_every_writer(dev):
     """Eval forwards with unchanged weights skip the weight pack and the BatchNorm-coefficient launches
-    (flair_unet_reuse_constants).  Same outputs as a cold forward, and every way the weights can change between two
+    (reuse_constants of flair_unet_fwd_opts_t).  Same outputs as a cold forward, and every way the weights can change between two
     eval forwards — torch in-place writes, load_state_dict, a training forward (running statistics), the fused
     trainer's native SGD — is noticed."""
     import flair_amd
@@ -907,7 +907,7 @@ def test_small_eval_forwards_replay_a_hip_graph_with_identical_results(dev):
 
 @pytest.mark.parametrize("dtype,classes", [("f32", 13), ("bf16", 13), ("bf16", 19), ("f32", 19)])
 def test_predict_argmax_from_the_head_epilogue_equals_argmax_of_the_logits(dev, dtype, classes):
-    """SegTrainer.predict takes the argmax out of the head convolution's epilogue (flair_unet_want_preds).  It must equal the
+    """SegTrainer.predict takes the argmax out of the head convolution's epilogue (preds_u8 of flair_unet_fwd_opts_t).  It must equal the
     first-maximum argmax of the logits the same forward would have returned (fp32 NCHW copy of the same rounded values), for
     the one-block (13 classes) and the two-block (19 classes) column layouts."""
     import flair_amd

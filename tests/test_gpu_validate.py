@@ -1,6 +1,6 @@
 """SegTrainer.validate_step / validation_epoch_end on the GPU: the per-pixel head of the reference's step() (label argmax, weighted
 cross-entropy mean, argmax(softmax), confusion-matrix bincount; task_module.py:71-79, 104-154) taken out of the head convolution's
-register epilogue (flair_unet_want_ce), and the fallback that runs the head convolution and flair_ce_head_nhwc's kernels instead.
+register epilogue (the ce_ fields of flair_unet_fwd_opts_t), and the fallback that runs the head convolution and flair_ce_head_nhwc's kernels instead.
 
 Loss tolerance, used by every loss assertion against the HIP logits: "truth" is the fp64 host recomputation of the weighted CE mean
 (oracle.seg_step.cross_entropy_np) from the fp32 NCHW logits the same eval forward returns — the rounded values the epilogue sees —
@@ -9,6 +9,8 @@ covers what differs between the two kernels at these shapes: at most 12 sequenti
 blocks, one pixel per lane and block), 8 reduction levels over 256 threads, and a three-term reordering of the exp-sum; both share
 __expf / logf.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -336,18 +338,26 @@ def test_conflicting_requests_are_refused_and_dropped(dev):
     loss = torch.full((), 7.0, dtype=torch.float32, device=dev)
     preds = torch.full((1, 64, 64), 99, dtype=torch.uint8, device=dev)
     cews = torch.empty(l.flair_ce_workspace_bytes(1, 64, 64) + 256, dtype=torch.uint8, device=dev)
-    L.check(l.flair_unet_want_preds(h, L.ptr(preds), None), "want_preds")
-    L.check(l.flair_unet_want_ce(h, L.ptr(lab), 0, None, L.ptr(loss), None, None, L.ptr(cews)), "want_ce")
-    with torch.cuda.device(dev):
-        rc = l.flair_unet_forward(h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), None, 1, 64, 64, 0, L.ptr(ws), ws.numel(), L.stream())
-    assert rc == -15 and b"want_ce" in l.flair_strerror(rc)
+    ce = dict(ce_labels=L.ptr(lab), ce_label_kind=0, ce_loss=L.ptr(loss), ce_workspace=L.ptr(cews))
+
+    def fwd(handle, training, arena, **fields):
+        opts = L.UnetFwdOpts(**fields)
+        with torch.cuda.device(dev):
+            return l.flair_unet_forward(handle, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), None, 1, 64, 64, training, L.ptr(arena),
+                                        arena.numel(), L.stream(), ctypes.byref(opts))
+
+    rc = fwd(h, 0, ws, preds_u8=L.ptr(preds), **ce)
+    assert rc == -15 and b"ce_labels" in l.flair_strerror(rc)
     assert loss.item() == 7.0 and int((preds != 99).sum()) == 0   # nothing ran
-    # nothing is left armed: a plain eval forward behaves like an untouched model's
+    # malformed structs are refused before that: no loss, no workspace, a label kind out of range, a probability map without preds
+    for bad in (dict(ce, ce_loss=None), dict(ce, ce_workspace=None), dict(ce, ce_label_kind=4), dict(ce, ce_label_kind=-1),
+                dict(maxprob_f32=L.ptr(loss))):
+        assert fwd(h, 0, ws, **bad) == -1
+    assert loss.item() == 7.0 and int((preds != 99).sum()) == 0
+    # nothing is kept: a plain eval forward behaves like an untouched model's
     assert torch.equal(m._c_forward(x, training=False), untouched._c_forward(x, training=False))
     assert loss.item() == 7.0 and int((preds != 99).sum()) == 0
-    # a request that meets a training forward is refused and dropped as well
-    L.check(l.flair_unet_want_ce(m._h, L.ptr(lab), 0, None, L.ptr(loss), None, None, L.ptr(cews)), "want_ce")
+    # the CE head on a training forward is refused as well
     wst = m._workspace(1, 64, 64, True)
-    with torch.cuda.device(dev):
-        rc = l.flair_unet_forward(m._h, L.ptr(m._flat_p), L.ptr(m._flat_b), L.ptr(x), None, 1, 64, 64, 1, L.ptr(wst), wst.numel(), L.stream())
+    rc = fwd(m._h, 1, wst, **ce)
     assert rc == -15 and loss.item() == 7.0

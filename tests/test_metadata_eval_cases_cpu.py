@@ -1,5 +1,5 @@
 """The case table of flair_add_rowvec_nhwc (tests/metadata_eval_cases.py) checked on the CPU: the planted bf16 ties, the expectations
-against a naive NCHW loop with a rounding of its own, and the declaration of the two new entry points."""
+against a naive NCHW loop with a rounding of its own, and the declaration of the operator's entry point."""
 import os
 import re
 
@@ -57,10 +57,11 @@ def test_expectations_equal_a_naive_nchw_loop():
 
 
 def test_new_entry_points_are_declared_in_the_header_and_the_ctypes_table():
+    """(the forward's rows_f32 option: the struct-mirror test of test_unet_fwd_opts_cpu.py)"""
     from flair_amd import _lib as L
     hdr = open(os.path.join(ROOT, "include", "flair_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, n_want in (("flair_add_rowvec_nhwc", 8), ("flair_unet_want_rowvec", 2)):
+    for name, n_want in (("flair_add_rowvec_nhwc", 8),):
         m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
         assert m, f"{name} is not declared in include/flair_hip.h"
         n_args = len([a for a in m.group(1).split(",") if a.strip()])

@@ -1,4 +1,4 @@
-"""tests/metadata_train_cases.py checked on the CPU, and the declaration of the three new entry points."""
+"""tests/metadata_train_cases.py checked on the CPU, and the declaration of the two operator entry points."""
 import ctypes as C
 import os
 import re
@@ -46,7 +46,7 @@ def test_new_entry_points_are_declared_in_the_header_and_the_ctypes_table():
     from flair_amd import _lib as L
     hdr = open(os.path.join(ROOT, "include", "flair_hip.h")).read()
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name, n_want in (("flair_add_rowvec_nhwc_to", 9), ("flair_rowvec_grad_nhwc", 8), ("flair_unet_want_rowvec_train", 3)):
+    for name, n_want in (("flair_add_rowvec_nhwc_to", 9), ("flair_rowvec_grad_nhwc", 8)):
         m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
         assert m, f"{name} is not declared in include/flair_hip.h"
         n_args = len([a for a in m.group(1).split(",") if a.strip()])
@@ -59,14 +59,17 @@ def test_error_texts_and_the_workspace_bound_without_a_device():
     request existed (the request's extra bottleneck tensor must fit inside it — checked on the GPU)."""
     from flair_amd import _lib as L
     l = L.lib()
-    assert b"flair_unet_want_rowvec_train" in l.flair_strerror(-17)
-    assert b"flair_unet_want_rowvec:" in l.flair_strerror(-16)
+    assert b"drows_f32" in l.flair_strerror(-17)
+    assert b"rows_f32" in l.flair_strerror(-16) and l.flair_strerror(-16) != l.flair_strerror(-17)
     for dt, name in ((0, "f32"), (1, "bf16")):
         h = C.c_void_p()
         assert l.flair_unet_create(C.byref(h), 5, 13, dt) == 0
         try:
             got = (l.flair_unet_workspace_bytes(h, 2, 160, 128, 1), l.flair_unet_workspace_bytes(h, 2, 160, 128, 0))
             assert got == tc.WORKSPACE_2x160x128[name], (name, got)
-            assert l.flair_unet_want_rowvec_train(h, None, None) == -1
+            drows = torch.full((2, 5), 7.0)     # a gradient pointer without rows: refused before anything looks behind it
+            opts = L.UnetFwdOpts(drows_f32=drows.data_ptr())
+            assert l.flair_unet_forward(h, None, None, None, None, 2, 160, 128, 1, None, 0, None, C.byref(opts)) == -1
+            assert bool((drows == 7.0).all())
         finally:
             l.flair_unet_destroy(h)

@@ -1,14 +1,10 @@
-"""Host-side pieces of the fused trainer's validation: the cross-rank reduction of its accumulators (gloo, host tensors) and the
-declaration of the native request in the public header and the ctypes table."""
+"""Host-side pieces of the fused trainer's validation: the cross-rank reduction of its accumulators (gloo, host tensors)."""
 import os
-import re
 import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _free_port():
@@ -57,15 +53,3 @@ def test_reduce_validation_state_world2_gloo():
         assert abs(loss_sum - all_losses.sum().item()) <= 1e-12
         # MeanMetric over the concatenated batches of one process
         assert abs(loss_sum / count - all_losses.mean().item()) <= 1e-12
-
-
-def test_want_ce_is_declared_in_the_header_and_the_ctypes_table():
-    from flair_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "flair_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    m = re.search(r"\bint\s+flair_unet_want_ce\s*\(([^;]*)\)\s*;", hdr)
-    assert m, "flair_unet_want_ce is not declared in include/flair_hip.h"
-    n_args = len([a for a in m.group(1).split(",") if a.strip()])
-    assert "flair_unet_want_ce" in L.PROTOTYPES
-    res, args = L.PROTOTYPES["flair_unet_want_ce"]
-    assert res is L.i32 and len(args) == n_args == 8
