@@ -822,6 +822,12 @@ int flair_swin_bilinear_add(int dtype, const void* x, void* y, int B, int h, int
 }
 #undef FLAIR_DT_OK
 
+long flair_tiff_lzw_slot_bytes(int rows_per_strip, int W) { return tiff_lzw_slot_bytes(rows_per_strip, W); }
+int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_strip, uint8_t* out, long slot_bytes, int32_t* counts,
+                          void* stream) {
+  return tiff_lzw_encode(img, B, H, W, rows_per_strip, out, slot_bytes, counts, (hipStream_t)stream);
+}
+
 // ------------------------------------------------------------------------------------------ SegFormer (zone_detect, HuggingFace provider)
 int flair_segformer_create(flair_segformer_t** out, int in_channels, int num_labels, const int depths[4], const int hidden_sizes[4],
                            const int num_heads[4], const int sr_ratios[4], int decoder_hidden_size, int dtype) {

@@ -145,5 +145,8 @@ int zone_window_confmat(int source, const void* pred, int B, int C, int S, int m
 int zone_raster_confmat(const float* band, const unsigned char* truth, int Hr, int Wr, int C, long long* confmat, hipStream_t s);
 int zone_error_map(const float* band, const unsigned char* truth, int Hr, int Wr, int K, const int* ys, int ny, const int* xs, int nx,
                    double sigma, int radius, unsigned char* mask, int* colsum, int* counts, double* tmp, double* out, hipStream_t s);
+// TIFF 6.0 LZW streams, one per strip of R rows of a (B, H, W) u8 tensor (csrc/tiff_lzw.hip)
+long tiff_lzw_slot_bytes(int R, int W);
+int tiff_lzw_encode(const unsigned char* img, int B, int H, int W, int R, unsigned char* out, long slot_bytes, int* counts, hipStream_t s);
 
 }  // namespace flair

@@ -357,6 +357,28 @@ def jaccard(confmat):
     return per, w, m
 
 
+def tiff_lzw_slot_bytes(rows_per_strip, W):
+    return int(L.lib().flair_tiff_lzw_slot_bytes(int(rows_per_strip), int(W)))
+
+
+def tiff_lzw_encode(u8, rows_per_strip=None):
+    """TIFF 6.0 LZW streams of a (B, H, W) uint8 tensor, one per strip of ``rows_per_strip`` rows (default: libtiff's 8 KB strips).
+    Returns (out, counts, slot_bytes, rows_per_strip): strip s of tile b is ``out[b, s, :counts[b, s]]``."""
+    if u8.dtype != torch.uint8 or u8.dim() != 3:
+        raise L.FlairHipError("tiff_lzw_encode needs a (B, H, W) uint8 tensor")
+    B, H, W = u8.shape
+    R = max(1, 8192 // W) if rows_per_strip is None else int(rows_per_strip)
+    if R < 1:
+        raise ValueError(f"rows_per_strip must be at least 1, got {rows_per_strip!r}")
+    nstrips = -(-H // R)
+    slot = tiff_lzw_slot_bytes(R, W)
+    src = L.ptr(u8)   # refuses host and non-contiguous tensors before anything is allocated
+    out = torch.empty(B, nstrips, slot, dtype=torch.uint8, device=u8.device)
+    counts = torch.empty(B, nstrips, dtype=torch.int32, device=u8.device)
+    L.check(L.lib().flair_tiff_lzw_encode(src, B, H, W, R, L.ptr(out), slot, L.ptr(counts), L.stream()), "tiff_lzw_encode")
+    return out, counts, slot, R
+
+
 def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
 

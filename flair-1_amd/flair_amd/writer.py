@@ -6,11 +6,16 @@ the training thread.  Here the uint8 cast happens on the device, the copy lands 
 side stream (1 byte/pixel), and encoding runs on a worker thread while the next batch is on the GPU.
 ``georeferencing_output`` needs rasterio (absent in this image): that branch raises; the plain branch writes the
 same ``PRED_<name>`` LZW TIFFs through PIL as the reference does (writer.py:45-50).
+
+``encode="device"`` moves the LZW encode to the GPU as well (csrc/tiff_lzw.hip): the worker then only frames the finished
+strips (``tiff_lzw_file``) and writes them.  ``encode="host"``, the default, is the PIL path above.
 """
 from __future__ import annotations
 
 import atexit
+import os
 import queue
+import struct
 import threading
 import weakref
 from pathlib import Path
@@ -29,9 +34,45 @@ def pred_filename(output_dir: str, filename: str) -> str:
     return str(output_dir + "/" + "PRED_" + filename.split("/")[-1])
 
 
+ENCODE_MODES = ("host", "device")
+ENCODE_DEFAULT = "host"   # predictionwriter(encode=None) without FLAIR_WRITER_ENCODE in the environment
+
+
+def tiff_lzw_file(H: int, W: int, rows_per_strip: int, strips) -> bytes:
+    """A classic little-endian TIFF of one (H, W) 8-bit grey image from its LZW-compressed strips (bytes-like, in order):
+    header, one IFD, the StripOffsets and StripByteCounts arrays, the strips back to back.  A single strip keeps its offset
+    and count inside the IFD entries."""
+    n = len(strips)
+    if n != -(-H // rows_per_strip):
+        raise ValueError(f"{n} strips for {H} rows at {rows_per_strip} rows per strip")
+    SHORT, LONG = 3, 4
+    ifd_end = 8 + 2 + 10 * 12 + 4
+    data0 = ifd_end + (8 * n if n > 1 else 0)
+    counts = [len(st) for st in strips]
+    offsets = [data0]
+    for c in counts[:-1]:
+        offsets.append(offsets[-1] + c)
+    entries = [(256, LONG, 1, W), (257, LONG, 1, H), (258, SHORT, 1, 8), (259, SHORT, 1, 5), (262, SHORT, 1, 1),
+               (273, LONG, n, offsets[0] if n == 1 else ifd_end), (277, SHORT, 1, 1), (278, LONG, 1, rows_per_strip),
+               (279, LONG, n, counts[0] if n == 1 else ifd_end + 4 * n), (284, SHORT, 1, 1)]
+    parts = [b"II*\0", struct.pack("<I", 8), struct.pack("<H", len(entries))]
+    parts += [struct.pack("<HHIHH" if typ == SHORT else "<HHII", tag, typ, cnt, *((val, 0) if typ == SHORT else (val,)))
+              for tag, typ, cnt, val in entries]
+    parts.append(struct.pack("<I", 0))
+    if n > 1:
+        parts += [struct.pack(f"<{n}I", *offsets), struct.pack(f"<{n}I", *counts)]
+    parts += strips
+    return b"".join(parts)
+
+
 class predictionwriter(_Base):
-    def __init__(self, config, output_dir, write_interval, max_pending: int = 4):
+    def __init__(self, config, output_dir, write_interval, max_pending: int = 4, encode=None):
         super().__init__(write_interval)
+        if encode is None:
+            encode = os.environ.get("FLAIR_WRITER_ENCODE") or ENCODE_DEFAULT
+        if encode not in ENCODE_MODES:
+            raise ValueError(f"predictionwriter encode must be one of {ENCODE_MODES}, got {encode!r}")
+        self.encode = encode
         self.config = config
         self.output_dir = output_dir
         Path(self.output_dir).mkdir(exist_ok=True, parents=True)
@@ -50,6 +91,10 @@ class predictionwriter(_Base):
             host, done, filenames = item
             try:
                 done.synchronize()
+                if isinstance(host, tuple):   # encode="device": the strips are compressed already
+                    slots, counts, (H, W, rows) = host
+                    self._write_strips(slots.numpy(), counts.numpy(), H, W, rows, filenames)
+                    continue
                 arr = host.numpy()
                 for prediction, filename in zip(arr, filenames):
                     Image.fromarray(prediction).save(pred_filename(self.output_dir, filename), compression="tiff_lzw")
@@ -57,6 +102,13 @@ class predictionwriter(_Base):
                 self._error = e
             finally:
                 self._q.task_done()
+
+    def _write_strips(self, slots, counts, H, W, rows, filenames):
+        """one file per tile from the device's (B, nstrips, slot_bytes) slots and (B, nstrips) stream lengths"""
+        for tile, tile_counts, filename in zip(slots, counts, filenames):
+            strips = [strip[:c] for strip, c in zip(tile, tile_counts)]
+            with open(pred_filename(self.output_dir, filename), "wb") as f:
+                f.write(tiff_lzw_file(H, W, rows, strips))
 
     def write_on_batch_end(self, trainer, pl_module, prediction, batch_indices, batch, batch_idx, dataloader_idx):
         if self.config["georeferencing_output"]:
@@ -77,11 +129,23 @@ class predictionwriter(_Base):
             ref = weakref.ref(self)
             atexit.register(lambda: (ref() is not None) and ref()._close_quietly())
         u8 = preds if preds.dtype == torch.uint8 else preds.to(torch.uint8)  # astype('uint8'), on the device
-        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+        if self.encode == "device":
+            from . import ops
+            # whole slots travel (1.5 x the mask at worst, the streams fill a fraction of them): no compaction pass on the device
+            slots, counts, _, rows = ops.tiff_lzw_encode(u8.contiguous())
+            src = (slots, counts)
+            dst = (torch.empty(slots.shape, dtype=torch.uint8, pin_memory=True),
+                   torch.empty(counts.shape, dtype=torch.int32, pin_memory=True))
+            host = (*dst, (u8.shape[1], u8.shape[2], rows))
+        else:
+            src = (u8,)
+            host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+            dst = (host,)
         self._copy_stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._copy_stream):
-            host.copy_(u8, non_blocking=True)
-            u8.record_stream(self._copy_stream)
+            for d, t in zip(dst, src):
+                d.copy_(t, non_blocking=True)
+                t.record_stream(self._copy_stream)
             done = torch.cuda.Event()
             done.record()
         self._q.put((host, done, list(filenames)))

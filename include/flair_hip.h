@@ -269,6 +269,19 @@ int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raste
                          int n_rows, const int32_t* col_origins, int n_cols, double sigma, int radius, uint8_t* mask_ws,
                          int32_t* colsum_ws, int32_t* counts_ws, double* tmp_ws, double* error_map, void* stream);
 
+/* TIFF 6.0 LZW (Compression = 5, no predictor) of uint8 tiles on the device (csrc/tiff_lzw.hip): the streams of the PRED_*.tif files.
+ * img (B, H, W) uint8.  Strip s of tile b covers rows [s*R, min(H, (s+1)*R)), R = rows_per_strip, as one byte stream; its LZW stream
+ * (ClearCode first, EOI last, codes MSB first, the widths and the table reset of libtiff's encoder) is written to
+ * out + (b*nstrips + s) * slot_bytes and its length in bytes to counts[b*nstrips + s], nstrips = ceil(H / R).  Bytes of a slot past
+ * its count are unspecified; nothing is written outside a slot.
+ * flair_tiff_lzw_slot_bytes: the smallest slot_bytes the encoder accepts, a multiple of 16 that holds the longest possible stream of
+ *   a full strip; -1 for rows_per_strip < 1 or W < 1.
+ * flair_tiff_lzw_encode: -1 for a null pointer or an extent / rows_per_strip < 1, -100 for slot_bytes below
+ *   flair_tiff_lzw_slot_bytes, -2 unless out is 16-byte aligned, slot_bytes a multiple of 16 and counts 4-byte aligned. */
+long flair_tiff_lzw_slot_bytes(int rows_per_strip, int W);
+int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_strip, uint8_t* out, long slot_bytes, int32_t* counts,
+                          void* stream);
+
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream);
