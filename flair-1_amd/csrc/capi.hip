@@ -827,6 +827,13 @@ int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_
                           void* stream) {
   return tiff_lzw_encode(img, B, H, W, rows_per_strip, out, slot_bytes, counts, (hipStream_t)stream);
 }
+int flair_tiff_lzw_decode_max_strip(void) { return tiff_lzw_decode_max_strip(); }
+int flair_tiff_lzw_decode(const uint8_t* src, long src_bytes, const int64_t* strip_src_off, const int32_t* strip_src_len,
+                          const int64_t* strip_dst_off, const int32_t* strip_dst_len, const int32_t* strip_mode, long nstrips, uint8_t* dst,
+                          long dst_bytes, int32_t* status, void* stream) {
+  return tiff_lzw_decode(src, src_bytes, (const long long*)strip_src_off, strip_src_len, (const long long*)strip_dst_off, strip_dst_len,
+                         strip_mode, nstrips, dst, dst_bytes, status, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------ SegFormer (zone_detect, HuggingFace provider)
 int flair_segformer_create(flair_segformer_t** out, int in_channels, int num_labels, const int depths[4], const int hidden_sizes[4],

@@ -148,5 +148,10 @@ int zone_error_map(const float* band, const unsigned char* truth, int Hr, int Wr
 // TIFF 6.0 LZW streams, one per strip of R rows of a (B, H, W) u8 tensor (csrc/tiff_lzw.hip)
 long tiff_lzw_slot_bytes(int R, int W);
 int tiff_lzw_encode(const unsigned char* img, int B, int H, int W, int R, unsigned char* out, long slot_bytes, int* counts, hipStream_t s);
+// the inverse, strip by strip from device tables: per-strip status (include/flair_hip.h), two launches (strips up to 16 KB, up to the cap)
+int tiff_lzw_decode_max_strip();
+int tiff_lzw_decode(const unsigned char* src, long src_bytes, const long long* strip_src_off, const int* strip_src_len,
+                    const long long* strip_dst_off, const int* strip_dst_len, const int* strip_mode, long nstrips, unsigned char* dst,
+                    long dst_bytes, int* status, hipStream_t s);
 
 }  // namespace flair

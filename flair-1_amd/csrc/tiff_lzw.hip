@@ -10,6 +10,7 @@
 // at load <= 3836 / 8192 = 0.47; five strips fit a CU.  All 64 lanes clear the table (at the start and at a reset) and fetch the
 // input 256 bytes at a time, 4 bytes per lane, one chunk ahead of the walk; the walk itself is executed by every lane on the same
 // values (a wave-uniform program: the current byte comes out of the chunk registers with v_readlane), lane 0 alone writes.
+// The decoder of the same streams (and of PIL's and libtiff's), the read path of metrics(), follows the encoder below.
 #include "ops.h"
 #include "prof.h"
 
@@ -130,7 +131,166 @@ __global__ __launch_bounds__(64) void tiff_lzw_encode_kernel(const unsigned char
   if (lane == 0) counts[strip] = count;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- the decoder
+// The read path of metrics(): one wave per strip again.  Every string a code can name already lies contiguously in the decoded
+// output: entry k, added after the code that follows `old`, is string(old) plus the first byte of what came next, i.e. the bytes at
+// [old_pos, old_pos + old_len + 1) of the strip.  So the table holds (position, length) packed in one u32 (16 + 16 bits: positions
+// stay below the 65 536-byte cap, lengths below 3840), 3838 entries (literals need none), and a code is emitted as a copy from
+// earlier output, 64 bytes per step across the lanes.  The serial chain is per code, not per byte.  The strip is decoded into
+// LDS and flushed to `dst` once, so the kernel never reads its own global stores back; the stage starts at the 16-byte phase of
+// the strip's global address, which makes the flush aligned 16-byte words on both sides.
+// Bit parsing is wave-uniform: the input is held 256 bytes per register of the wave (4 bytes per lane, big-endian words), one
+// chunk ahead, and a code is cut out of two words read with v_readlane.  Lane 0 alone writes the table.
+constexpr int LZW_DEC_SMALL = 16384, LZW_DEC_CAP = 65536;   // decoded bytes of an LZW strip per size class
+constexpr int LZW_DEC_ENTRIES = 4096 - LZW_FIRST;
+constexpr int lzw_dec_lds(int cap) { return cap + 16 + LZW_DEC_ENTRIES * 4; }   // stage (+ 16: the alignment phase), table
+
+// 4 bytes of the strip at `off` (any alignment, 64-bit offsets) as one big-endian word; offsets past the strip's end are clamped to
+// its last byte (n >= 1)
+__device__ __forceinline__ unsigned lzw_fetch_be(const unsigned char* __restrict__ src, long off, long n) {
+  unsigned w = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) w = (w << 8) | src[min(off + e, n - 1)];
+  return w;
+}
+
+// LDS stores of some lanes are read by other lanes afterwards: complete them, and keep the compiler from moving accesses across
+__device__ __forceinline__ void lzw_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Strips of one size class: LZW strips with lo < dst_len <= hi.  The launch with `first` set also serves the stored strips and
+// gives the out-of-range ones their status, so that every strip is served by exactly one launch.
+__global__ __launch_bounds__(64) void tiff_lzw_decode_kernel(const unsigned char* __restrict__ src, long src_bytes,
+                                                             const long long* __restrict__ strip_src_off, const int* __restrict__ strip_src_len,
+                                                             const long long* __restrict__ strip_dst_off, const int* __restrict__ strip_dst_len,
+                                                             const int* __restrict__ strip_mode, unsigned char* __restrict__ dst, long dst_bytes,
+                                                             int* __restrict__ status, int lo, int hi, int first) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lzw_dec_smem[];
+  const int lane = threadIdx.x;
+  const long strip = blockIdx.x;
+  const long so = strip_src_off[strip], dO = strip_dst_off[strip];
+  const int sn = strip_src_len[strip], dn = strip_dst_len[strip], md = strip_mode[strip];
+  const bool ok = so >= 0 && sn >= 0 && dO >= 0 && dn >= 1 && so <= src_bytes - sn && dO <= dst_bytes - dn &&
+                  (md == 0 || (md == 1 && dn <= LZW_DEC_CAP));
+  const unsigned char* __restrict__ s = src + so;
+  unsigned char* __restrict__ g = dst + dO;
+  if (!ok || md == 0) {
+    if (!first) return;
+    if (!ok) { if (lane == 0) status[strip] = 5; return; }
+    const int n = min(sn, dn);
+    for (int i = lane; i < n; i += 64) g[i] = s[i];
+    if (lane == 0) status[strip] = sn >= dn ? 0 : 1;
+    return;
+  }
+  if (dn <= lo || dn > hi) return;
+  if (sn == 0) { if (lane == 0) status[strip] = 1; return; }
+
+  const int phase = (int)((uintptr_t)g & 15);
+  unsigned char* stage = lzw_dec_smem + phase;                                  // stage[i] is g[i]
+  unsigned* tab = reinterpret_cast<unsigned*>(lzw_dec_smem + hi + 16);          // entry of code k at tab[k - LZW_FIRST]
+
+  const long nbits = (long)sn * 8;
+  unsigned cur = lzw_fetch_be(s, 4 * lane, sn), ahead = lzw_fetch_be(s, LZW_CHUNK + 4 * lane, sn);
+  long base = 0;                       // the strip offset of `cur`, bytes
+  int b = 0;                           // the next code's bit offset inside `cur`, < 2048
+  int nxt = LZW_FIRST, width = 9, op = 0, st;
+  int old_pos = 0, old_len = 0;        // where the previous code's string was emitted; length 0: no previous code
+  // every round consumes `width` >= 9 bits of the strip or ends: at most src_len * 8 / 9 rounds whatever the bytes are
+  for (;;) {
+    if (op >= dn) { st = 0; break; }
+    if (base * 8 + b + width > nbits) { st = 1; break; }
+    const int wi = b >> 5;
+    const unsigned w0 = __builtin_amdgcn_readlane(cur, wi);
+    const unsigned w1 = wi < 63 ? __builtin_amdgcn_readlane(cur, (wi + 1) & 63) : __builtin_amdgcn_readlane(ahead, 0);
+    const int code = (int)(((((unsigned long long)w0 << 32) | w1) >> (64 - (b & 31) - width)) & ((1u << width) - 1));
+    b += width;
+    if (b >= 8 * LZW_CHUNK) {
+      b -= 8 * LZW_CHUNK;
+      base += LZW_CHUNK;
+      cur = ahead;
+      ahead = lzw_fetch_be(s, base + LZW_CHUNK + 4 * lane, sn);
+    }
+    if (code == LZW_CLEAR) { nxt = LZW_FIRST; width = 9; old_len = 0; continue; }
+    if (code == LZW_EOI) { st = 2; break; }
+    if (old_len == 0) {
+      if (code >= 256) { st = 3; break; }
+      if (lane == 0) stage[op] = (unsigned char)code;
+      lzw_lds_order();
+      old_pos = op; old_len = 1; ++op;
+      continue;
+    }
+    // the string of `code`: [from, from + len) of the stage, except that at index `wrap` it starts over (code == nxt: string(old)
+    // and its own first byte again, which is where this copy's first byte lands; the source stays below `op` all the same)
+    int from = 0, len = 1, wrap = 0x7fffffff;
+    if (code >= 256) {
+      if (code < nxt) {
+        const unsigned e = __builtin_amdgcn_readfirstlane(tab[code - LZW_FIRST]);
+        from = (int)(e >> 16); len = (int)(e & 0xffff);
+      } else if (code == nxt && nxt < 4096) {
+        from = old_pos; len = old_len + 1; wrap = old_len;
+      } else { st = 4; break; }
+    }
+    const int n = min(len, dn - op);
+    if (code < 256) {
+      if (lane == 0) stage[op] = (unsigned char)code;
+    } else {
+      for (int j = lane; j < n; j += 64) stage[op + j] = stage[from + (j < wrap ? j : 0)];
+    }
+    if (nxt < 4096) {
+      if (lane == 0) tab[nxt - LZW_FIRST] = ((unsigned)old_pos << 16) | (unsigned)(old_len + 1);
+      ++nxt;
+      if (nxt == 511 || nxt == 1023 || nxt == 2047) ++width;
+    }
+    lzw_lds_order();
+    old_pos = op; old_len = n; op += n;
+  }
+
+  // the flush: what was produced (all of the strip at status 0), bytes up to the first 16-byte boundary of g, words, bytes
+  const int head = min(op, (16 - phase) & 15);
+  if (lane < head) g[lane] = stage[lane];
+  const int nvec = (op - head) >> 4;
+  for (int i = lane; i < nvec; i += 64)
+    *reinterpret_cast<uint4*>(g + head + 16 * i) = *reinterpret_cast<const uint4*>(stage + head + 16 * i);
+  const int t = head + 16 * nvec + lane;
+  if (t < op) g[t] = stage[t];
+  if (lane == 0) status[strip] = st;
+}
+
 }  // namespace
+
+int tiff_lzw_decode_max_strip() { return LZW_DEC_CAP; }
+
+// Both size classes are launched over all strips (the tables are on the device: the host cannot sort them without a sync); a
+// workgroup whose strip belongs to the other launch leaves at once.
+int tiff_lzw_decode(const unsigned char* src, long src_bytes, const long long* strip_src_off, const int* strip_src_len,
+                    const long long* strip_dst_off, const int* strip_dst_len, const int* strip_mode, long nstrips, unsigned char* dst,
+                    long dst_bytes, int* status, hipStream_t s) {
+  if (!src || !strip_src_off || !strip_src_len || !strip_dst_off || !strip_dst_len || !strip_mode || !dst || !status) return -1;
+  if (nstrips < 1 || nstrips > 0x7fffffffL || src_bytes < 0 || dst_bytes < 0) return -1;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(tiff_lzw_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       lzw_dec_lds(LZW_DEC_CAP));
+    if (e != hipSuccess) return (int)e;
+    attr_set = true;
+  }
+  {
+    ProfScope ps("tiff_lzw_decode_small", 0.0, 0.0, s);
+    hipLaunchKernelGGL(tiff_lzw_decode_kernel, dim3((unsigned)nstrips), dim3(64), lzw_dec_lds(LZW_DEC_SMALL), s, src, src_bytes, strip_src_off,
+                       strip_src_len, strip_dst_off, strip_dst_len, strip_mode, dst, dst_bytes, status, 0, LZW_DEC_SMALL, 1);
+    FLAIR_CHECK_LAUNCH();
+  }
+  {
+    ProfScope ps("tiff_lzw_decode_large", 0.0, 0.0, s);
+    hipLaunchKernelGGL(tiff_lzw_decode_kernel, dim3((unsigned)nstrips), dim3(64), lzw_dec_lds(LZW_DEC_CAP), s, src, src_bytes, strip_src_off,
+                       strip_src_len, strip_dst_off, strip_dst_len, strip_mode, dst, dst_bytes, status, LZW_DEC_SMALL, LZW_DEC_CAP, 0);
+    FLAIR_CHECK_LAUNCH();
+  }
+  return 0;
+}
 
 // at most n + n / 3836 + 3 codes of at most 12 bits (ClearCode, one per byte, one per reset, EOI)
 long tiff_lzw_slot_bytes(int R, int W) {

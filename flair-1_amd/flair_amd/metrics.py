@@ -6,10 +6,12 @@ process (metrics.py:60-75).  Here decoded uint8 rasters are shipped in chunks an
 ``- 1`` label shift, the ``labels=range(C)`` filter and the sum over tiles into one int64 C x C matrix on the device;
 what follows (weight-0 class removal, the IoU / OA / precision / recall / F-score family, ``metrics.json`` and
 ``confmat.npy``) is float64 arithmetic on that C x C matrix and stays on the host, in the reference's operation order.
+``metrics(decode="device")`` also moves the TIFF decode of the masks to the GPU (flair_amd/tiff.py, csrc/tiff_lzw.hip).
 """
 from __future__ import annotations
 
 import json
+import os
 from pathlib import Path
 
 import numpy as np
@@ -115,15 +117,23 @@ def _raster_pairs(test_csv, path_preds: Path):
         yield u, msk, (path_preds / ("PRED_" + str(img).split("/")[-1])).as_posix()
 
 
-def metrics(config: dict, path_preds, remove_preds: bool = False, device="cuda", chunk_tiles: int = 64):
-    """Same inputs and outputs as the reference's ``metrics`` (metrics.py:44-125): test CSV -> truth rasters,
-    ``PRED_<name>`` rasters under ``path_preds`` -> ``<out>/metrics/{confmat.npy, metrics.json}``; returns the dict.
-    A pair that cannot be read or whose sizes differ is reported and skipped, like the reference's try/except."""
+DECODE_MODES = ("host", "device")
+DECODE_DEFAULT = "host"   # metrics(decode=None) without FLAIR_METRICS_DECODE in the environment
+
+
+def resolve_decode(decode):
+    """the ``decode`` argument of ``metrics``: None reads FLAIR_METRICS_DECODE, then DECODE_DEFAULT"""
+    if decode is None:
+        decode = os.environ.get("FLAIR_METRICS_DECODE") or DECODE_DEFAULT
+    if decode not in DECODE_MODES:
+        raise ValueError(f"metrics decode must be one of {DECODE_MODES}, got {decode!r}")
+    return decode
+
+
+def _accumulate_host(acc, pairs, device, chunk_tiles):
+    """every file through PIL on this thread, decoded rasters uploaded chunk by chunk"""
     from PIL import Image
 
-    path_preds = Path(path_preds)
-    print("-- Calculating metrics --")
-    acc = MaskConfusion(len(config["classes"]), device=device)
     pending = ([], [])
 
     def flush():
@@ -132,7 +142,7 @@ def metrics(config: dict, path_preds, remove_preds: bool = False, device="cuda",
             pending[0].clear()
             pending[1].clear()
 
-    for u, truth_path, pred_path in _raster_pairs(config["paths"]["test_csv"], path_preds):
+    for u, truth_path, pred_path in pairs:
         try:
             target = _as_u8(np.asarray(Image.open(truth_path)), truth=True)
             preds = _as_u8(np.asarray(Image.open(pred_path)), truth=False)
@@ -146,6 +156,85 @@ def metrics(config: dict, path_preds, remove_preds: bool = False, device="cuda",
         if len(pending[0]) >= chunk_tiles:
             flush()
     flush()
+
+
+def _accumulate_device(acc, pairs, device, chunk_tiles, stats):
+    """compressed strips up, decoded on the device (tiff.begin_read_masks), the confusion-matrix kernel reads the pixels where they
+    landed: one update per run of good pairs whose pixels are adjacent in the chunk's buffer (a skipped pair ends a run, and so
+    does a pair whose size is no multiple of 16, the alignment flair_confmat_masks asks of its pointers)"""
+    from .tiff import begin_read_masks, finish_read_masks
+
+    def begin(chunk):
+        k = len(chunk)
+        return chunk, begin_read_masks([c[1] for c in chunk] + [c[2] for c in chunk], device, "device", truth=[True] * k + [False] * k)
+
+    def finish(chunk, job):
+        k = len(chunk)
+        reads = finish_read_masks(job)
+        for r in reads:
+            stats[r.where] += 1
+        buf = next((r.buffer for r in reads if r.buffer is not None), None)
+        run = None   # (truth start, prediction start, bytes) in the buffer the chunk's pixels share
+
+        def update_run():
+            if run:
+                acc.update(buf[run[0]:run[0] + run[2]], buf[run[1]:run[1] + run[2]])
+
+        for (u, _, _), t, p in zip(chunk, reads[:k], reads[k:]):
+            try:
+                for r in (t, p):
+                    if r.error is not None:
+                        raise r.error
+                if t.pixels.numel() != p.pixels.numel():
+                    raise ValueError("Found input variables with inconsistent numbers of samples")
+            except Exception as e:  # noqa: BLE001
+                print(f"Error at index {u}: {e}")
+                continue
+            n = t.pixels.numel()
+            if t.buffer is None or p.buffer is None:   # a file PIL read at another size than its IFD says: a tensor of its own
+                acc.update(t.pixels.reshape(-1), p.pixels.reshape(-1))
+            elif run and run[0] + run[2] == t.offset and run[1] + run[2] == p.offset:
+                run = (run[0], run[1], run[2] + n)
+            else:
+                update_run()
+                run = (t.offset, p.offset, n)
+        update_run()
+
+    # one chunk ahead: while the device decodes a chunk, the host reads the files of the next
+    chunk, queued = [], None
+    for pair in pairs:
+        chunk.append(pair)
+        if len(chunk) >= chunk_tiles:
+            queued, done = begin(chunk), queued
+            if done:
+                finish(*done)
+            chunk = []
+    if chunk:
+        queued, done = begin(chunk), queued
+        if done:
+            finish(*done)
+    if queued:
+        finish(*queued)
+
+
+def metrics(config: dict, path_preds, remove_preds: bool = False, device="cuda", chunk_tiles: int = 64, decode=None):
+    """Same inputs and outputs as the reference's ``metrics`` (metrics.py:44-125): test CSV -> truth rasters,
+    ``PRED_<name>`` rasters under ``path_preds`` -> ``<out>/metrics/{confmat.npy, metrics.json}``; returns the dict.
+    A pair that cannot be read or whose sizes differ is reported and skipped, like the reference's try/except.
+    ``decode="host"`` opens every file with PIL; ``decode="device"`` decodes stored and LZW masks on the GPU (flair_amd/tiff.py) and
+    leaves every other file, and every file the kernel reports an error for, to PIL: same pairs, same matrix.  ``None`` reads
+    FLAIR_METRICS_DECODE, then DECODE_DEFAULT.  ``metrics.last_read_stats`` counts where the files of the last call were decoded."""
+    decode = resolve_decode(decode)
+    path_preds = Path(path_preds)
+    print("-- Calculating metrics --")
+    acc = MaskConfusion(len(config["classes"]), device=device)
+    pairs = _raster_pairs(config["paths"]["test_csv"], path_preds)
+    stats = {"device": 0, "host": 0, "host_after_device_error": 0, "error": 0}
+    if decode == "device":
+        _accumulate_device(acc, pairs, device, chunk_tiles, stats)
+    else:
+        _accumulate_host(acc, pairs, device, chunk_tiles)
+    metrics.last_read_stats = {"decode": decode, **stats}
     sum_confmat = acc.compute()
     out = metrics_from_confmat(sum_confmat, config["classes"])
 
@@ -163,3 +252,6 @@ def metrics(config: dict, path_preds, remove_preds: bool = False, device="cuda",
         import shutil
         shutil.rmtree(path_preds)
     return out
+
+
+metrics.last_read_stats = None

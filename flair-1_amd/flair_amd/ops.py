@@ -379,6 +379,40 @@ def tiff_lzw_encode(u8, rows_per_strip=None):
     return out, counts, slot, R
 
 
+def tiff_lzw_decode_max_strip():
+    return int(L.lib().flair_tiff_lzw_decode_max_strip())
+
+
+_STRIP_TABLE_DTYPES = (("src_off", torch.int64), ("src_len", torch.int32), ("dst_off", torch.int64), ("dst_len", torch.int32),
+                       ("mode", torch.int32))
+
+
+def tiff_lzw_decode(src, src_off, src_len, dst_off, dst_len, mode, dst_bytes, out=None):
+    """Decodes TIFF strips on the device: strip i, ``src[src_off[i] : src_off[i] + src_len[i]]``, goes to
+    ``dst[dst_off[i] : dst_off[i] + dst_len[i]]``; ``mode[i]`` 0 = stored, 1 = LZW.  ``src`` is a flat uint8 device tensor, the five
+    tables are device tensors of one length (offsets int64, the others int32).  Returns (dst uint8 of ``dst_bytes``, status int32 per
+    strip; include/flair_hip.h lists the codes).  ``out``, a flat uint8 device tensor of ``dst_bytes``, is decoded into when given."""
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise L.FlairHipError("tiff_lzw_decode needs a flat uint8 tensor of compressed bytes")
+    tables = (src_off, src_len, dst_off, dst_len, mode)
+    n = int(src_off.numel())
+    for t, (name, dt) in zip(tables, _STRIP_TABLE_DTYPES):
+        if t.dtype != dt or t.dim() != 1 or t.numel() != n:
+            raise L.FlairHipError(f"tiff_lzw_decode: {name} must be a flat {dt} tensor of {n} entries")
+    dst_bytes = int(dst_bytes)
+    if n < 1 or dst_bytes < 1:
+        raise ValueError("tiff_lzw_decode needs at least one strip and dst_bytes >= 1")
+    ptrs = [L.ptr(src)] + [L.ptr(t) for t in tables]   # refuses host and non-contiguous tensors before anything is allocated
+    if out is None:
+        out = torch.empty(dst_bytes, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != dst_bytes:
+        raise L.FlairHipError(f"tiff_lzw_decode: out must be a flat uint8 tensor of {dst_bytes} bytes")
+    status = torch.empty(n, dtype=torch.int32, device=src.device)
+    L.check(L.lib().flair_tiff_lzw_decode(ptrs[0], src.numel(), *ptrs[1:], n, L.ptr(out), dst_bytes, L.ptr(status), L.stream()),
+            "tiff_lzw_decode")
+    return out, status
+
+
 def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
 

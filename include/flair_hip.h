@@ -281,6 +281,28 @@ int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raste
 long flair_tiff_lzw_slot_bytes(int rows_per_strip, int W);
 int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_strip, uint8_t* out, long slot_bytes, int32_t* counts,
                           void* stream);
+/* The inverse on the device (the read path of metrics()): strip i, the bytes [strip_src_off[i], + strip_src_len[i]) of src, is
+ * decoded into [strip_dst_off[i], + strip_dst_len[i]) of dst; strip_mode[i] 0 = stored (Compression 1: a copy), 1 = LZW (Compression
+ * 5).  All pointers are device pointers, the five tables have nstrips entries, status receives one code per strip.  One wave per
+ * strip, two launches (decoded LZW strips up to 16 KB, and up to flair_tiff_lzw_decode_max_strip() = 65 536 bytes, PIL's strip);
+ * stored strips have no cap.  Returns -1 for a null pointer, nstrips < 1 or a negative size; no device sync.
+ * Stream rules (TIFF 6.0 LZW as libtiff reads it, MSB-first codes, no predictor): a fresh table, next free code nxt = 258, width 9;
+ * 256 clears (nxt = 258, width 9, no previous code); 257 ends the stream; the first code after a clear or the start must be a
+ * literal; otherwise code < nxt emits its string, code == nxt emits string(old) + first(string(old)), anything larger is an error;
+ * after each non-first code string(old) + first(string(code)) becomes entry nxt++ unless nxt is 4096 already; the width grows when
+ * the decoder's nxt reaches 511, 1023 and 2047 and stops at 12.  Decoding stops once strip_dst_len bytes are produced: the last
+ * string is clipped, the bytes after it are ignored, no EOI is needed.
+ * status: 0 exactly strip_dst_len bytes produced; 1 the input ran out first; 2 EOI came first; 3 a non-literal code first after a
+ * clear or the start; 4 code > nxt, or code == nxt with a full table; 5 a range or cap error (an offset or length below 0,
+ * src_off + src_len > src_bytes, dst_off + dst_len > dst_bytes, dst_len < 1, a mode other than 0 / 1, an LZW dst_len above the
+ * cap): nothing of that strip is written.  At status 1 - 4 the bytes decoded before the error are written, the rest of the strip's
+ * region is left as it was.
+ * Whatever the input bytes are the kernel terminates (every round consumes at least 9 bits of the strip), reads src only inside
+ * the strip's own [src_off, src_off + src_len) and writes dst only inside its own [dst_off, dst_off + dst_len). */
+int flair_tiff_lzw_decode_max_strip(void);
+int flair_tiff_lzw_decode(const uint8_t* src, long src_bytes, const int64_t* strip_src_off, const int32_t* strip_src_len,
+                          const int64_t* strip_dst_off, const int32_t* strip_dst_len, const int32_t* strip_mode, long nstrips, uint8_t* dst,
+                          long dst_bytes, int32_t* status, void* stream);
 
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
