@@ -16,6 +16,28 @@ import torch.nn as nn
 from . import _lib as L
 
 
+def tensor_of(root, name):
+    """(module, leaf) of the dotted parameter / buffer name under ``root`` (digits index Sequential / ModuleList children)."""
+    mod = root
+    *path, leaf = name.split(".")
+    for p in path:
+        mod = mod._modules[p]
+    return mod, leaf
+
+
+def query_layout(num_tensors, tensor_info, h, stage=False):
+    """The native tensor table of handle ``h``: name -> (shape, float offset, kind) and, with ``stage``, the gradient stage."""
+    out = {}
+    name = C.create_string_buffer(160)
+    shape = (C.c_int64 * 4)()
+    nd, kind, st, off = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+    extra = (C.byref(st),) if stage else ()
+    for i in range(num_tensors(h)):
+        L.check(tensor_info(h, i, name, 160, shape, C.byref(nd), C.byref(off), C.byref(kind), *extra))
+        out[name.value.decode()] = (tuple(shape[d] for d in range(nd.value)), off.value, kind.value) + ((st.value,) if stage else ())
+    return out
+
+
 class _Box(nn.Module):
     """A node of the parameter tree (children are added by dotted name)."""
 
@@ -34,7 +56,7 @@ class NativeModel(nn.Module):
     def _init_tensors(self, h, initializer_range):
         """Takes the native handle: builds the parameter tree from its tensor table, initialised like the library."""
         object.__setattr__(self, "_h", h)
-        self._layout = self._query_layout()
+        self._layout = query_layout(self._fn("num_tensors"), self._fn("tensor_info"), h)
         self._n = self._fn("param_count")(h)
         g = torch.Generator().manual_seed(torch.initial_seed() & 0x7FFFFFFF)
         for name, (shape, off, kind) in self._layout.items():
@@ -51,7 +73,7 @@ class NativeModel(nn.Module):
             if leaf == "running_var":        # BatchNorm2d's counter follows its running statistics in the library's order
                 self._attach(name[:-len("running_var")] + "num_batches_tracked", torch.zeros((), dtype=torch.int64), 1)
         self._flat = None
-        self._version = -1
+        self._seen_version = -1
         self._ws = None
 
     # ---- parameter tree
@@ -67,23 +89,6 @@ class NativeModel(nn.Module):
         else:
             mod.register_buffer(leaf, tensor)
 
-    def _tensor(self, name):
-        mod = self
-        *path, leaf = name.split(".")
-        for p in path:
-            mod = mod._modules[p]
-        return mod, leaf
-
-    def _query_layout(self):
-        out = {}
-        name = C.create_string_buffer(160)
-        shape = (C.c_int64 * 4)()
-        nd, kind, off = C.c_int(), C.c_int(), C.c_int64()
-        for i in range(self._fn("num_tensors")(self._h)):
-            L.check(self._fn("tensor_info")(self._h, i, name, 160, shape, C.byref(nd), C.byref(off), C.byref(kind)))
-            out[name.value.decode()] = (tuple(shape[d] for d in range(nd.value)), off.value, kind.value)
-        return out
-
     def train(self, mode=True):
         if mode:
             raise RuntimeError(f"flair_amd.{type(self).__name__} is inference-only (zone_detect never trains)")
@@ -98,27 +103,25 @@ class NativeModel(nn.Module):
             base = self._flat.data_ptr()
             version = 0
             for name, (shape, off, _) in self._layout.items():
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
+                t = getattr(*tensor_of(self, name))
                 if t.data_ptr() != base + 4 * off or t.dtype != torch.float32:
                     ok = False
                     break
                 version += t._version
         if ok:
-            if version != self._version:      # an in-place update (load_state_dict, copy_, ...) since the last forward:
-                self.weights_changed()        # the library re-packs its cached weight layouts
-                self._version = version
+            if version != self._seen_version:   # an in-place update (load_state_dict, copy_, ...) since the last forward:
+                self.weights_changed()          # the library re-packs its cached weight layouts
+                self._seen_version = version
             return self._flat
         flat = torch.zeros(self._n, dtype=torch.float32, device=dev)
         with torch.no_grad():
             for name, (shape, off, _) in self._layout.items():
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
+                t = getattr(*tensor_of(self, name))
                 view = flat[off:off + math.prod(shape)].view(shape)
                 view.copy_(t.detach().to(device=dev, dtype=torch.float32))
                 t.data = view
         self._flat = flat
-        self._version = sum(getattr(*self._tensor(name))._version for name in self._layout)
+        self._seen_version = sum(getattr(*tensor_of(self, name))._version for name in self._layout)
         self.weights_changed()
         return flat
 

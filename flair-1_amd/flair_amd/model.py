@@ -25,6 +25,12 @@ from . import ops
 from .unet import create_model
 
 
+def check_metadata_tile(x):
+    """The reference hard-codes repeat(1,512,1,16) (model.py:59, quirk Q4): the metadata branch takes 512 x 512 tiles only."""
+    if tuple(x.shape[-2:]) != (512, 512):
+        raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+
+
 class _AddRowVec(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, x_enc):
@@ -149,8 +155,6 @@ class FLAIR_ModelFactory(nn.Module):
                 self.seg_model = SegformerForSemanticSegmentation(num_channels=n_channels, num_labels=n_classes,
                                                                   compute_dtype=compute_dtype, **kw)
 
-    _Q4 = "metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)"
-
     def _meta_fused(self):
         """Metadata branch of an eval-mode U-Net: the add rides inside the single native forward (FLAIR_META_FUSE=0: split path)."""
         return not self.seg_model.training and os.environ.get("FLAIR_META_FUSE", "1") != "0"
@@ -159,14 +163,11 @@ class FLAIR_ModelFactory(nn.Module):
         if self.use_metadata == True and self.model_provider == "SegmentationModelsPytorch":  # noqa: E712
             if self._meta_fused():
                 x_enc = self.enc(met)
-                if tuple(x.shape[-2:]) != (512, 512):   # (quirk Q4, as below)
-                    raise RuntimeError(self._Q4)
+                check_metadata_tile(x)
                 return self.seg_model.eval_logits(x, bottleneck_rows=x_enc)
             feats = self.seg_model.encoder(x)
             x_enc = self.enc(met)
-            if feats[-1].shape[1:] != (512, 16, 16):
-                # the reference hard-codes repeat(1,512,1,16): only 512x512 tiles are valid (quirk Q4)
-                raise RuntimeError(self._Q4)
+            check_metadata_tile(x)   # (behind the encoder: a tile it refuses raises its own error first)
             feats[-1] = _AddRowVec.apply(feats[-1], x_enc)
             output = self.seg_model.decoder(*feats)
             output = self.seg_model.segmentation_head(output)
@@ -190,8 +191,7 @@ class FLAIR_ModelFactory(nn.Module):
                 raise ValueError("this model was built with use_metadata: predict_classes needs the (B,45) metadata vectors")
             if os.environ.get("FLAIR_META_FUSE", "1") != "0":
                 x_enc = self.enc(met, masks=None)
-                if tuple(x.shape[-2:]) != (512, 512):
-                    raise RuntimeError(self._Q4)
+                check_metadata_tile(x)
                 return self.seg_model.predict_classes(x, want_prob=want_prob, bottleneck_rows=x_enc)
         logits = self.forward(x, met)
         return ops.softmax_argmax(logits.detach().float().contiguous(), want="u8", want_maxprob=want_prob)

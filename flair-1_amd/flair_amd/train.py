@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import ops
+from .model import check_metadata_tile
 
 
 def bucket_ranges(stage_ranges, min_elems=0):
@@ -165,8 +166,7 @@ class SegTrainer:
         enc = self.metadata_encoder
         if enc is None:
             raise ValueError("SegTrainer was built without a metadata_encoder: pass the MetadataMLP to take metadata")
-        if tuple(img.shape[-2:]) != (512, 512):   # the reference hard-codes repeat(1,512,1,16) (quirk Q4)
-            raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+        check_metadata_tile(img)
         dev = self.grads.device
         if self.exchange and not self._mlp_synced:
             # DDP's initial broadcast covers the whole module: rank 0's MLP, once
@@ -239,7 +239,7 @@ class SegTrainer:
             self._mlp_step(rows)
         # DDP averages: fold 1/world into the step size
         ops.sgd_step_(m._flat_p, self.grads, self.lr / self.world)
-        m._native_writes = m.__dict__.get("_native_writes", 0) + 1   # parameters changed behind torch's version counter
+        m._eval.note_native_write()   # parameters changed behind torch's version counter
         return self.loss
 
     def _meta_rows(self, img, mtd):
@@ -249,8 +249,7 @@ class SegTrainer:
             return None
         if self.metadata_encoder is None:
             raise ValueError("SegTrainer was built without a metadata_encoder: pass the MetadataMLP to take metadata")
-        if tuple(img.shape[-2:]) != (512, 512):   # the reference hard-codes repeat(1,512,1,16) (quirk Q4)
-            raise RuntimeError("metadata fusion expects a (B,512,16,16) bottleneck (512x512 input tiles)")
+        check_metadata_tile(img)
         return self.metadata_encoder(mtd.to(self.grads.device), masks=None).detach()
 
     @torch.no_grad()

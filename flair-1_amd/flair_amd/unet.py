@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import copy
 import ctypes as C
+import functools
 import math
 import os
 import warnings
@@ -28,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._native_model import query_layout, tensor_of
 
 
 def _on_model_device(fn):
@@ -35,11 +37,9 @@ def _on_model_device(fn):
     current device: run them with the model's device current (a model on cuda:1 while cuda:0 is current — two replicas in
     one process, a forgotten set_device — would otherwise launch on the wrong device's stream), and refuse inputs that
     live elsewhere."""
-    import functools
-
     @functools.wraps(fn)
     def wrapper(self, *args, **kwargs):
-        dev = self._flat_p.device if getattr(self, "_flat_p", None) is not None else None
+        dev = self._flat_p.device if self._flat_p is not None else None
         if dev is None or dev.type != "cuda":
             return fn(self, *args, **kwargs)
         for a in args:
@@ -53,6 +53,10 @@ def _on_model_device(fn):
 
 
 # ------------------------------------------------------------------------------------------------ containers
+def _container_forward(self, *a, **k):
+    raise RuntimeError("flair_amd: sub-modules are parameter containers; call the Unet / encoder / decoder / head")
+
+
 class _BasicBlock(nn.Module):
     def __init__(self, inplanes, planes, stride, downsample):
         super().__init__()
@@ -66,12 +70,7 @@ class _BasicBlock(nn.Module):
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride, bias=False), nn.BatchNorm2d(planes))
         self.stride = stride
 
-    def forward(self, x):
-        raise RuntimeError("flair_amd: sub-modules are parameter containers; call the Unet / encoder / decoder / head")
-
-
-def _container_forward(self, *a, **k):
-    raise RuntimeError("flair_amd: sub-modules are parameter containers; call the Unet / encoder / decoder / head")
+    forward = _container_forward
 
 
 class _Encoder(nn.Module):
@@ -142,7 +141,7 @@ class _WholeFn(torch.autograd.Function):
     def forward(ctx, owner, x, *params):
         logits = owner._c_forward(x, training=True)
         ctx.owner = owner
-        ctx.fwd_id = owner._fwd_id
+        ctx.fwd_id = owner._live.id
         return logits
 
     @staticmethod
@@ -158,7 +157,7 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, owner, x, *params):
         feats = owner._c_encoder_forward(x, training=True)
         ctx.owner = owner
-        ctx.fwd_id = owner._fwd_id
+        ctx.fwd_id = owner._live.id
         return tuple(feats)
 
     @staticmethod
@@ -166,7 +165,7 @@ class _EncoderFn(torch.autograd.Function):
         owner = ctx.owner
         owner._check_live(ctx.fwd_id)
         owner._c_encoder_backward([d.contiguous() for d in dfeats])
-        return (None, None) + tuple(owner._stage_grad_views("encoder"))
+        return (None, None) + tuple(owner._grad_views(owner._live.grads, "encoder"))
 
 
 class _DecoderFn(torch.autograd.Function):
@@ -174,7 +173,7 @@ class _DecoderFn(torch.autograd.Function):
     def forward(ctx, owner, f1, f2, f3, f4, f5, *params):
         out = owner._c_decoder_forward([f1, f2, f3, f4, f5], training=True)
         ctx.owner = owner
-        ctx.fwd_id = owner._fwd_id
+        ctx.fwd_id = owner._live.id
         return out
 
     @staticmethod
@@ -182,7 +181,7 @@ class _DecoderFn(torch.autograd.Function):
         owner = ctx.owner
         owner._check_live(ctx.fwd_id)
         dfeats = owner._c_decoder_backward(dout.contiguous())
-        return (None,) + tuple(dfeats) + tuple(owner._stage_grad_views("decoder"))
+        return (None,) + tuple(dfeats) + tuple(owner._grad_views(owner._live.grads, "decoder"))
 
 
 class _HeadFn(torch.autograd.Function):
@@ -190,7 +189,7 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, owner, x, *params):
         logits = owner._c_head_forward(x, training=True)
         ctx.owner = owner
-        ctx.fwd_id = owner._fwd_id
+        ctx.fwd_id = owner._live.id
         return logits
 
     @staticmethod
@@ -198,7 +197,61 @@ class _HeadFn(torch.autograd.Function):
         owner = ctx.owner
         owner._check_live(ctx.fwd_id)
         dx = owner._c_head_backward(dlogits.contiguous())
-        return (None, dx) + tuple(owner._stage_grad_views("segmentation_head"))
+        return (None, dx) + tuple(owner._grad_views(owner._live.grads, "segmentation_head"))
+
+
+# ------------------------------------------------------------------------------------------------ host state
+class _LiveForward:
+    """The training forward that awaits its backward: its number (``_check_live``), the workspace its activations are in, (B, H, W),
+    the (rows, drows) pair the native side holds raw pointers to until that backward, and the split path's gradient buffer."""
+    __slots__ = ("id", "ws", "shape", "rows", "grads")
+
+    def __init__(self, id=0, ws=None, shape=None, rows=None):   # (no forward has number 0)
+        self.id, self.ws, self.shape, self.rows, self.grads = id, ws, shape, rows, None
+
+
+class EvalCache:
+    """What eval forwards keep between calls, and the decision what the next one does (plain Python, no device call).  ``key`` vouches
+    for the packed weights and BatchNorm coefficients in the eval workspace; ``graphs`` holds one captured HIP graph per kind of call
+    (graph key: (want_logits, preds, prob, rows)), ``hits`` the repeats of each kind under the key, ``nocapture`` the kinds whose capture
+    failed: all four go when the key changes.  The caller's key is extended by the count of native writes (``note_native_write``):
+    changes no torch version counter sees — training forwards (running statistics) and the fused trainer's SGD (parameters)."""
+    FULL, REUSE, GRAPH = "full", "reuse", "graph"
+    # eval forwards of small batches are launch-bound (~150 kernels of a few microseconds: predict_step at the reference's
+    # batch size 1, data_module.py:100, ran at 870 tiles/s against 10 000 at batch 32): the third identical call — same weights,
+    # shape, workspace and requested outputs — is captured into a HIP graph and replayed from then on (FLAIR_EVAL_GRAPH=0: never)
+    MAX_GRAPH_PIXELS = 4 * 512 * 512
+
+    def __init__(self):
+        self._native_writes = 0
+        self.drop()
+
+    def drop(self):
+        """No key (the next eval forward packs again) and no graph captured under it."""
+        self.key, self.graphs, self.hits, self.nocapture = None, {}, {}, set()
+
+    def note_native_write(self):
+        self._native_writes += 1
+
+    def decide(self, key, gkey, has_ce, pixels, graphs_allowed, capturing):
+        """FULL: pack the constants and run eagerly.  REUSE: run eagerly over the constants in the workspace.  GRAPH: replay the
+        graph of ``gkey``, capturing it first if there is none — the third identical call, the first repeat having run eagerly with
+        reuse so that every kernel's one-time set-up is done.  A call with the CE head neither counts nor is captured."""
+        if self.key != (key, self._native_writes):
+            self.drop()
+            return self.FULL
+        if has_ce or not graphs_allowed or pixels > self.MAX_GRAPH_PIXELS or capturing:
+            return self.REUSE
+        self.hits[gkey] = self.hits.get(gkey, 0) + 1
+        return self.GRAPH if gkey not in self.nocapture and (gkey in self.graphs or self.hits[gkey] >= 2) else self.REUSE
+
+    def capture_failed(self, gkey):
+        """This kind of call stays eager until the key changes (and runs now as FULL: the broken capture advanced the executor's state)."""
+        self.nocapture.add(gkey)
+
+    def packed(self, key):
+        """An eager eval forward under ``key`` is being issued: from here on the constants in the workspace are that key's."""
+        self.key = (key, self._native_writes)
 
 
 # ------------------------------------------------------------------------------------------------ the model
@@ -228,26 +281,41 @@ class Unet(nn.Module):
         self.name = "u-resnet34"
         self._init_weights(encoder_weights)
         # native handle + layout
-        h = C.c_void_p()
-        L.check(L.lib().flair_unet_create(C.byref(h), self.in_channels, self.classes, self._dt), "flair_unet_create")
-        object.__setattr__(self, "_h", h)
-        self._layout = self._query_layout()
-        sd_tensors = dict(self.named_parameters())
-        sd_tensors.update(dict(self.named_buffers()))
+        self._reset_native_state()
+        self._layout = query_layout(L.lib().flair_unet_num_tensors, L.lib().flair_unet_tensor_info, self._h, stage=True)
+        sd_tensors = {**dict(self.named_parameters()), **dict(self.named_buffers())}
         for name, (shape, off, kind, stage) in self._layout.items():
             t = sd_tensors.get(name)
             if t is None or tuple(t.shape) != shape:
                 raise RuntimeError(f"layout mismatch for {name}: native {shape} vs module {None if t is None else tuple(t.shape)}")
         self._param_names = [n for n, (_, _, k, _) in self._layout.items() if k == 0]
         self._buffer_names = [n for n, (_, _, k, _) in self._layout.items() if k == 1]
-        self._n_params = L.lib().flair_unet_param_count(h)
-        self._n_buffers = L.lib().flair_unet_buffer_count(h)
-        self._flat_p = None
-        self._flat_b = None
-        self._ws = {}
-        self._fwd_id = 0
-        self._live_id = -1
-        self._grads = None
+        self._n_params = L.lib().flair_unet_param_count(self._h)
+        self._n_buffers = L.lib().flair_unet_buffer_count(self._h)
+        # BatchNorm layers in modules() order, the order of _flat_n: the encoder's, then the decoder's
+        self._n_bn_encoder = sum(n.startswith("encoder.") and n.endswith(".running_mean") for n in self._buffer_names)
+
+    def _new_handle(self):
+        h = C.c_void_p()
+        L.check(L.lib().flair_unet_create(C.byref(h), self.in_channels, self.classes, self._dt), "flair_unet_create")
+        return h
+
+    # the names these had before EvalCache / _LiveForward, for code that still reads them
+    _eval_graphs = property(lambda self: self._eval.graphs)
+    _eval_nocapture = property(lambda self: self._eval.nocapture)
+    _eval_key = property(lambda self: self._eval.key, lambda self, key: setattr(self._eval, "key", key))
+    _live_ws = property(lambda self: self._live.ws)
+
+    def _reset_native_state(self):
+        """Every attribute that holds native or device state, as a model has it before its first forward.  __init__ and
+        __setstate__ call this and nothing else creates such an attribute; __getstate__ drops exactly these."""
+        state = dict(_h=self._new_handle(), _h_eval=None,         # native executors: training, and eval (made at its first use: _hh)
+                     _flat_p=None, _flat_b=None, _flat_n=None,    # flat device buffers: parameters, running statistics, num_batches_tracked
+                     _ws={}, _ws_need={},                         # workspaces by mode, and their planned sizes by (B, H, W, training)
+                     _eval=EvalCache(), _live=_LiveForward(),
+                     _eval_split=None)   # ((B, H, W), workspace) of the eval-mode split forward: it must not disturb _live
+        self.__dict__.update(state)
+        self._native_state = tuple(state)
 
     # -------------------------------------------------------------------------------------------- init
     def _init_weights(self, encoder_weights):
@@ -293,17 +361,6 @@ class Unet(nn.Module):
         self.encoder.load_state_dict(sd, strict=True)
 
     # -------------------------------------------------------------------------------------------- layout
-    def _query_layout(self):
-        l = L.lib()
-        out = {}
-        name = C.create_string_buffer(128)
-        shape = (C.c_int64 * 4)()
-        nd, kind, stage, off = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
-        for i in range(l.flair_unet_num_tensors(self._h)):
-            L.check(l.flair_unet_tensor_info(self._h, i, name, 128, shape, C.byref(nd), C.byref(off), C.byref(kind), C.byref(stage)))
-            out[name.value.decode()] = (tuple(shape[d] for d in range(nd.value)), off.value, kind.value, stage.value)
-        return out
-
     def stage_ranges(self):
         """[(begin, end)] float offsets of the 7 gradient buckets (stem, layer1-4, decoder, head)."""
         b, e = C.c_int64(), C.c_int64()
@@ -312,13 +369,6 @@ class Unet(nn.Module):
             L.check(L.lib().flair_unet_stage_range(self._h, s, C.byref(b), C.byref(e)))
             res.append((b.value, e.value))
         return res
-
-    def _tensor(self, name):
-        mod = self
-        *path, leaf = name.split(".")
-        for p in path:
-            mod = getattr(mod, p) if not p.isdigit() else mod[int(p)]
-        return mod, leaf
 
     def flatten_(self):
         """(Re)bind every parameter / running statistic as a view of the two flat device buffers."""
@@ -329,8 +379,7 @@ class Unet(nn.Module):
         if ok:
             base_p, base_b = self._flat_p.data_ptr(), self._flat_b.data_ptr()
             for name in self._param_names + self._buffer_names:
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
+                t = getattr(*tensor_of(self, name))
                 _, off, kind, _ = self._layout[name]
                 if t.data_ptr() != (base_p if kind == 0 else base_b) + 4 * off or t.dtype != torch.float32:
                     ok = False
@@ -341,8 +390,7 @@ class Unet(nn.Module):
         flat_b = torch.zeros(max(self._n_buffers, 1), dtype=torch.float32, device=dev)
         with torch.no_grad():
             for name in self._param_names + self._buffer_names:
-                mod, leaf = self._tensor(name)
-                t = getattr(mod, leaf)
+                t = getattr(*tensor_of(self, name))
                 shape, off, kind, _ = self._layout[name]
                 n = math.prod(shape)
                 view = (flat_p if kind == 0 else flat_b)[off:off + n].view(shape)
@@ -356,32 +404,22 @@ class Unet(nn.Module):
         self._flat_p, self._flat_b, self._flat_n = flat_p, flat_b, flat_n
         # new buffers repeat the version counters of the ones they replace (one copy_ per tensor) and `.data =` moves none:
         # what was packed from, or captured with, the old addresses goes here, not by a key that may compare equal
-        self._drop_eval_cache()
-
-    def _drop_eval_cache(self):
-        """Forget what eval forwards keep between calls: the key that vouches for the packed weights and BatchNorm coefficients
-        in the eval workspace (no key: the next eval forward packs again) and every HIP graph captured under it."""
-        self._eval_key = None
-        self._eval_graphs = {}
-        self._eval_hits = {}
-        self._eval_nocapture = set()
+        self._eval.drop()
 
     def weights_changed(self):
         """Announce a change of parameters or running statistics that torch's version counters cannot see — an in-place write
         through ``.data`` (``p.data.mul_(...)``) or through a raw pointer: the next eval forward packs the weights again and
         captures no graph before its third identical call.  Every other writer (in-place torch ops, ``load_state_dict``,
         ``.data =`` / ``.to()`` / ``.cpu()`` rebinds, training forwards, the fused trainer) is noticed without it."""
-        self._drop_eval_cache()
+        self._eval.drop()
 
     def _eval_cache_key(self, B, H, W, ws):
         """What must be unchanged for the constants in the eval workspace, and a graph captured over them, to be still valid.
         Versions: torch bumps a tensor's _version on every in-place write (optimizers, load_state_dict); the parameters and
-        buffers are .data views of the flat buffers and each carries its own counter.  _native_writes: native writers (training
-        forwards: running statistics; the fused trainer's SGD).  Addresses of the flat buffers: a rebuilt buffer repeats its
-        predecessor's versions, and a captured graph has the addresses baked in."""
+        buffers are .data views of the flat buffers and each carries its own counter.  Addresses of the flat buffers: a rebuilt
+        buffer repeats its predecessor's versions, and a captured graph has the addresses baked in.  (Native writers: EvalCache.)"""
         ver = sum(p._version for p in self.parameters()) + sum(b._version for b in self.buffers())
-        return (ver, self._flat_p._version, self._flat_b._version, self._flat_p.data_ptr(), self._flat_b.data_ptr(),
-                self.__dict__.get("_native_writes", 0), B, H, W, ws.data_ptr())
+        return (ver, self._flat_p._version, self._flat_b._version, self._flat_p.data_ptr(), self._flat_b.data_ptr(), B, H, W, ws.data_ptr())
 
     def flat_parameters(self):
         self.flatten_()
@@ -393,11 +431,7 @@ class Unet(nn.Module):
 
     def _params_list(self, prefix=None):
         names = [n for n in self._param_names if prefix is None or n.startswith(prefix + ".")]
-        out = []
-        for n in names:
-            mod, leaf = self._tensor(n)
-            out.append(getattr(mod, leaf))
-        return names, out
+        return names, [getattr(*tensor_of(self, n)) for n in names]
 
     def _grad_views(self, grads, prefix=None):
         views = []
@@ -408,9 +442,6 @@ class Unet(nn.Module):
             views.append(grads[off:off + math.prod(shape)].view(shape))
         return views
 
-    def _stage_grad_views(self, prefix):
-        return self._grad_views(self._grads, prefix)
-
     # -------------------------------------------------------------------------------------------- native calls
     def _hh(self, training):
         """The native executor for this call: eval-mode forwards (predict, validation, ZoneDetector) run on a second
@@ -418,16 +449,13 @@ class Unet(nn.Module):
         training graph alone."""
         if training:
             return self._h
-        h = self.__dict__.get("_h_eval")
-        if h is None:
-            h = C.c_void_p()
-            L.check(L.lib().flair_unet_create(C.byref(h), self.in_channels, self.classes, self._dt), "flair_unet_create")
-            object.__setattr__(self, "_h_eval", h)
-        return h
+        if self._h_eval is None:
+            self._h_eval = self._new_handle()
+        return self._h_eval
 
     def _workspace(self, B, H, W, training):
         key = "train" if training else "eval"
-        plan = self.__dict__.setdefault("_ws_need", {})
+        plan = self._ws_need
         need = plan.get((B, H, W, bool(training)))
         if need is None:   # the dry run walks the whole 47-conv graph on the host: once per shape, not once per step
             need = L.lib().flair_unet_workspace_bytes(self._h, B, H, W, int(training))
@@ -461,14 +489,10 @@ class Unet(nn.Module):
         """num_batches_tracked += 1 for BatchNorm layers [lo, hi) (one op on the flat int64 buffer)."""
         self._flat_n[lo:hi] += 1
 
-    # eval forwards of small batches are launch-bound (~150 kernels of a few microseconds: predict_step at the reference's
-    # batch size 1, data_module.py:100, ran at 870 tiles/s against 10 000 at batch 32): the third identical call — same weights,
-    # shape, workspace and requested outputs — is captured into a HIP graph and replayed from then on (FLAIR_EVAL_GRAPH=0: never)
-    _GRAPH_MAX_PIXELS = 4 * 512 * 512
     _NOT_CAPTURED = object()
 
     def _eval_graph(self, gkey, x, want_logits, preds, prob, ws, h, rows=None):
-        ent = self._eval_graphs.get(gkey)
+        ent = self._eval.graphs.get(gkey)
         if ent is None:
             B, _, H, W = x.shape
             ent = {"x": x.clone(), "logits": torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None,
@@ -487,10 +511,10 @@ class Unet(nn.Module):
                 # nothing ran (capture records); the caller runs this same call eagerly, and this kind of call stays eager until
                 # the key changes
                 warnings.warn(f"flair_amd.Unet: HIP graph capture of the eval forward failed ({type(e).__name__}: {e}); running eagerly")
-                self._eval_nocapture.add(gkey)
+                self._eval.capture_failed(gkey)
                 return self._NOT_CAPTURED
             ent["graph"] = g
-            self._eval_graphs[gkey] = ent
+            self._eval.graphs[gkey] = ent
         ent["x"].copy_(x)       # (capture records, it does not run: the first use replays too)
         if rows is not None:
             ent["rows"].copy_(rows)
@@ -533,11 +557,8 @@ class Unet(nn.Module):
             if not training:
                 raise RuntimeError("flair_amd.Unet: train_rows= is for training-mode forwards; an eval-mode forward takes rows=")
             t_rows, t_drows = train_rows
-            for t in (t_rows, t_drows):
-                if not t.is_cuda or t.device != x.device:
-                    raise L.FlairHipError("flair_amd.Unet: bottleneck rows must live on the input's HIP device")
-                if tuple(t.shape) != (B, H // 32):
-                    raise RuntimeError(f"bottleneck rows must be (B, H/32) = ({B}, {H // 32}), got {tuple(t.shape)}")
+            self._check_rows(t_rows, x)
+            self._check_rows(t_drows, x)
             if t_drows.dtype != torch.float32 or not t_drows.is_contiguous():
                 raise RuntimeError("flair_amd.Unet: the gradient tensor of train_rows must be contiguous fp32 (the backward writes it)")
             train_rows = (t_rows.detach().to(torch.float32).contiguous(), t_drows.detach())
@@ -545,70 +566,66 @@ class Unet(nn.Module):
             if training:
                 raise RuntimeError("flair_amd.Unet: bottleneck rows are added in eval-mode forwards only; a training-mode model "
                                    "takes the split path (encoder, add, decoder, segmentation_head)")
-            if not rows.is_cuda or rows.device != x.device:
-                raise L.FlairHipError("flair_amd.Unet: bottleneck rows must live on the input's HIP device")
-            if tuple(rows.shape) != (B, H // 32):
-                raise RuntimeError(f"bottleneck rows must be (B, H/32) = ({B}, {H // 32}), got {tuple(rows.shape)}")
+            self._check_rows(rows, x)
             rows = rows.detach().to(torch.float32).contiguous()
         ws = self._workspace(B, H, W, training)
         h = self._hh(training)
-        key, repack = None, False
-        if not training:
-            key = self._eval_cache_key(B, H, W, ws)
-            if self.__dict__.get("_eval_key") != key:
-                self._drop_eval_cache()
-            elif (ce is None and os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0" and B * H * W <= self._GRAPH_MAX_PIXELS
-                  and not torch.cuda.is_current_stream_capturing()):
-                gkey = (want_logits, preds is not None, prob is not None, rows is not None)
-                hits = self._eval_hits
-                hits[gkey] = hits.get(gkey, 0) + 1
-                # (the first repeat ran eagerly with reuse: every kernel's one-time set-up is done)
-                if gkey not in self._eval_nocapture and (gkey in self._eval_graphs or hits[gkey] >= 2):
-                    out = self._eval_graph(gkey, x, want_logits, preds, prob, ws, h, rows)
-                    if out is not self._NOT_CAPTURED:
-                        return out
-                    # a capture that broke inside the native call has advanced the executor's host state without running a kernel:
-                    # pack again
-                    repack = True
-        logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
         # constant weights between two eval forwards (predict / zone_detect loops): skip the weight pack and the
         # BatchNorm-coefficient launches while the key (_eval_cache_key) stands.  Writes through .data are invisible to it,
         # as they are to autograd: weights_changed() is the call for those.
-        reuse = not training and self.__dict__.get("_eval_key") == key and not repack
+        reuse = False
+        if not training:
+            key = self._eval_cache_key(B, H, W, ws)
+            gkey = (want_logits, preds is not None, prob is not None, rows is not None)
+            todo = self._eval.decide(key, gkey, ce is not None, B * H * W, os.environ.get("FLAIR_EVAL_GRAPH", "1") != "0",
+                                torch.cuda.is_current_stream_capturing())
+            if todo == self._eval.GRAPH:
+                out = self._eval_graph(gkey, x, want_logits, preds, prob, ws, h, rows)
+                if out is not self._NOT_CAPTURED:
+                    return out
+                todo = self._eval.FULL   # (EvalCache.capture_failed: this call packs again)
+            reuse = todo == self._eval.REUSE
+        logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device) if want_logits else None
         opts = self._fwd_opts(reuse, preds, prob, ce, rows, train_rows)
         if not training:
-            self._eval_key = key
+            self._eval.packed(key)
         else:
-            self._native_writes = self.__dict__.get("_native_writes", 0) + 1
+            self._eval.note_native_write()   # running statistics are about to change
         L.check(L.lib().flair_unet_forward(h, L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(x), L.ptr(logits), B, H, W,
                                            int(training), L.ptr(ws), ws.numel(), L.stream(), C.byref(opts)), "flair_unet_forward")
         if training:
-            self._fwd_id += 1
-            self._live_id = self._fwd_id
-            self._live_ws = ws
-            self._live_rows = train_rows   # (the native side holds raw pointers until the backward of this forward)
+            # (rows: the native side holds raw pointers until the backward of this forward)
+            self._live = _LiveForward(self._live.id + 1, ws, (B, H, W), train_rows)
             self._bump_bn()
         return logits
 
+    @staticmethod
+    def _check_rows(t, x):
+        B, H = x.shape[0], x.shape[2]
+        if not t.is_cuda or t.device != x.device:
+            raise L.FlairHipError("flair_amd.Unet: bottleneck rows must live on the input's HIP device")
+        if tuple(t.shape) != (B, H // 32):
+            raise RuntimeError(f"bottleneck rows must be (B, H/32) = ({B}, {H // 32}), got {tuple(t.shape)}")
+
     def _check_live(self, fwd_id):
-        if fwd_id != self._live_id:
+        if fwd_id != self._live.id:
             raise RuntimeError("flair_amd.Unet: the activations of this forward were overwritten by a later training "
                                "forward; call backward before the next training-mode forward")
 
     def _new_grads(self):
-        self._grads = torch.zeros(self._n_params, dtype=torch.float32, device=self._flat_p.device)
-        return self._grads
+        self._live.grads = torch.zeros(self._n_params, dtype=torch.float32, device=self._flat_p.device)
+        return self._live.grads
 
     @_on_model_device
     def _c_backward(self, dlogits=None, dlogits_nhwc=None, grads=None, stage_events=None):
-        ws = self._live_ws
+        ws = self._live.ws
         grads = grads if grads is not None else self._new_grads()
         ev = None
         if stage_events is not None:
             ev = (C.c_void_p * 7)(*[e.cuda_event for e in stage_events])
         L.check(L.lib().flair_unet_backward(self._h, L.ptr(self._flat_p), L.ptr(dlogits), L.ptr(dlogits_nhwc), L.ptr(grads),
                                             L.ptr(ws), ws.numel(), L.stream(), ev), "flair_unet_backward")
-        self._live_rows = None
+        self._live.rows = None
         return grads
 
     # ---- split path (model.py:57-62)
@@ -621,58 +638,49 @@ class Unet(nn.Module):
         feats = [torch.empty(B, c, H >> (i + 1), W >> (i + 1), dtype=torch.float32, device=x.device) for i, c in enumerate(chans)]
         arr = (C.c_void_p * 5)(*[f.data_ptr() for f in feats])
         if not training:
-            self._eval_key = None   # the split path re-lays the eval arena: the fused forward's constants are gone
+            self._eval.key = None   # the split path re-lays the eval arena: the fused forward's constants are gone
         L.check(L.lib().flair_unet_encoder_forward(self._hh(training), L.ptr(self._flat_p), L.ptr(self._flat_b), L.ptr(x), arr, B, H, W,
                                                    int(training), L.ptr(ws), ws.numel(), L.stream()), "encoder_forward")
         if training:
-            self._native_writes = self.__dict__.get("_native_writes", 0) + 1   # running statistics are about to change
-        # per mode: an eval-mode split forward must not disturb a training one that still awaits its backward
-        self.__dict__.setdefault("_split", {})[bool(training)] = ((B, H, W), ws)
-        if training:
-            self._split_shape = (B, H, W)
-            self._split_ws = ws
-            self._fwd_id += 1
-            self._live_id = self._fwd_id
-            self._live_ws = ws
-            self._grads = None
-            self._bump_bn(0, 36)
+            self._eval.note_native_write()   # running statistics are about to change
+            self._live = _LiveForward(self._live.id + 1, ws, (B, H, W))
+            self._bump_bn(0, self._n_bn_encoder)
+        else:
+            self._eval_split = ((B, H, W), ws)
         return feats
 
     @_on_model_device
     def _c_decoder_forward(self, feats, training):
-        (B, H, W), ws = self._split[bool(training)]
+        (B, H, W), ws = (self._live.shape, self._live.ws) if training else self._eval_split
         feats = [f.detach().to(torch.float32).contiguous() for f in feats]
         out = torch.empty(B, 16, H, W, dtype=torch.float32, device=feats[0].device)
         arr = (C.c_void_p * 5)(*[f.data_ptr() for f in feats])
         if not training:
-            self._eval_key = None
+            self._eval.key = None
         L.check(L.lib().flair_unet_decoder_forward(self._hh(training), L.ptr(self._flat_p), L.ptr(self._flat_b), arr, L.ptr(out), B, H, W,
                                                    int(training), L.ptr(ws), ws.numel(), L.stream()), "decoder_forward")
         if training:
-            self._native_writes = self.__dict__.get("_native_writes", 0) + 1   # decoder running statistics changed
-            self._bump_bn(36, 46)
+            self._eval.note_native_write()   # decoder running statistics changed
+            self._bump_bn(self._n_bn_encoder)
         return out
 
     @_on_model_device
     def _c_head_forward(self, x, training):
-        (B, H, W), ws = self._split[bool(training)]
+        (B, H, W), ws = (self._live.shape, self._live.ws) if training else self._eval_split
         x = x.detach().to(torch.float32).contiguous()
         logits = torch.empty(B, self.classes, H, W, dtype=torch.float32, device=x.device)
         if not training:
-            self._eval_key = None
+            self._eval.key = None
         L.check(L.lib().flair_unet_head_forward(self._hh(training), L.ptr(self._flat_p), L.ptr(x), L.ptr(logits), B, H, W, int(training),
                                                 L.ptr(ws), ws.numel(), L.stream()), "head_forward")
         return logits
 
     def _split_grads(self):
-        if self._grads is None:
-            self._new_grads()
-        return self._grads
+        return self._live.grads if self._live.grads is not None else self._new_grads()
 
     @_on_model_device
     def _c_head_backward(self, dlogits):
-        B, H, W = self._split_shape
-        ws = self._split_ws
+        (B, H, W), ws = self._live.shape, self._live.ws
         g = self._split_grads()
         dx = torch.empty(B, 16, H, W, dtype=torch.float32, device=dlogits.device)
         L.check(L.lib().flair_unet_head_backward(self._h, L.ptr(self._flat_p), L.ptr(dlogits), L.ptr(dx), L.ptr(g), L.ptr(ws),
@@ -681,8 +689,7 @@ class Unet(nn.Module):
 
     @_on_model_device
     def _c_decoder_backward(self, dout):
-        B, H, W = self._split_shape
-        ws = self._split_ws
+        (B, H, W), ws = self._live.shape, self._live.ws
         g = self._split_grads()
         chans = (64, 64, 128, 256, 512)
         dfe = [torch.empty(B, c, H >> (i + 1), W >> (i + 1), dtype=torch.float32, device=dout.device) for i, c in enumerate(chans)]
@@ -693,7 +700,7 @@ class Unet(nn.Module):
 
     @_on_model_device
     def _c_encoder_backward(self, dfeats):
-        ws = self._split_ws
+        ws = self._live.ws
         g = self._split_grads()
         arr = (C.c_void_p * 5)(*[f.data_ptr() for f in dfeats])
         L.check(L.lib().flair_unet_encoder_backward(self._h, L.ptr(self._flat_p), arr, L.ptr(g), L.ptr(ws), ws.numel(),
@@ -773,13 +780,9 @@ class Unet(nn.Module):
         except Exception:
             pass
 
-    _NATIVE_STATE = ("_h", "_h_eval", "_eval_key", "_eval_graphs", "_eval_hits", "_eval_nocapture", "_ws_need", "_split", "_ws", "_flat_p", "_flat_b", "_flat_n", "_grads", "_live_ws", "_split_ws", "_live_rows")
-
     def __getstate__(self):
-        d = dict(self.__dict__)
-        for k in self._NATIVE_STATE:
-            d.pop(k, None)
-        if self.__dict__.get("_flat_p") is not None:
+        d = {k: v for k, v in self.__dict__.items() if k not in self._native_state}   # (the names _reset_native_state assigned)
+        if self._flat_p is not None:
             # every parameter is a view of the flat buffer and pickle writes a view's WHOLE storage, once per tensor (some hundred
             # times 85 MB): hand out compact clones instead.  (The sub-modules' _owner, this object, is not copied along:
             # __setstate__ sets it.)
@@ -788,12 +791,7 @@ class Unet(nn.Module):
 
     def __setstate__(self, d):
         self.__dict__.update(d)
-        h = C.c_void_p()
-        L.check(L.lib().flair_unet_create(C.byref(h), self.in_channels, self.classes, self._dt), "flair_unet_create")
-        object.__setattr__(self, "_h", h)
-        self._flat_p = self._flat_b = self._flat_n = self._grads = None
-        self._ws = {}
-        self._live_id = -1
+        self._reset_native_state()
         for m in (self.encoder, self.decoder, self.segmentation_head):
             object.__setattr__(m, "_owner", self)
 

@@ -32,7 +32,7 @@ NARROW_WRITERS = ("rebind_all", "cpu_cuda_roundtrip", "trainer_sgd")
 NARROW_CONSUMERS = ("logits_graph", "preds_prob_graph")
 
 CONSUMERS = ("logits_reuse", "logits_graph", "preds_prob_graph", "rows_graph", "validate_ce", "factory_metadata")
-# consumer -> (identical calls that arm it, the _eval_graphs entry those calls must have left: (logits, preds, prob, rows) or None)
+# consumer -> (identical calls that arm it, the _eval.graphs entry those calls must have left: (logits, preds, prob, rows) or None)
 ARMING = {
     "logits_reuse": (2, None),
     "logits_graph": (4, (True, False, False, False)),

@@ -21,7 +21,7 @@ import eval_cache_cases as ec
 
 pytestmark = pytest.mark.gpu
 
-CACHE_STATE = ("_eval_key", "_eval_graphs", "_eval_hits", "_eval_nocapture")
+CACHE_STATE = ("key", "graphs", "hits", "nocapture")   # of Unet._eval (an EvalCache)
 
 
 class _env:
@@ -125,7 +125,7 @@ def _cold(m, consumer, s, dtype, dev):
     fresh = _model(m.state_dict(), dtype, s["classes"], dev)
     with _env("FLAIR_EVAL_GRAPH", "0"):
         out = _consumer(consumer, fresh, s)()
-    assert len(fresh._eval_graphs) == 0
+    assert len(fresh._eval.graphs) == 0
     return out
 
 
@@ -133,11 +133,11 @@ def _arm(m, run, consumer):
     calls, gkey = ec.ARMING[consumer]
     armed = [run() for _ in range(calls)]
     assert all(_same(a, armed[0]) for a in armed[1:])
-    assert m._eval_key is not None                       # the reuse path is armed ...
+    assert m._eval.key is not None                       # the reuse path is armed ...
     if gkey is None:
-        assert len(m._eval_graphs) == 0
+        assert len(m._eval.graphs) == 0
     else:
-        assert list(m._eval_graphs) == [gkey]            # ... and so is the graph: nothing passes because nothing was cached
+        assert list(m._eval.graphs) == [gkey]            # ... and so is the graph: nothing passes because nothing was cached
     return armed[0]
 
 
@@ -169,7 +169,8 @@ def test_writer_is_seen_by_consumer(dev, shared, writer, consumer, dtype, classe
     made = fn(hip, s["donor"], s["inp"]) if writer in ec.NEEDS_INPUTS else fn(hip, s["donor"])
 
     if writer in ec.COPY_WRITERS:
-        assert made is not hip and not any(k in made.__dict__ for k in CACHE_STATE), sorted(made.__dict__)
+        assert made is not hip and made._eval is not hip._eval
+        assert [getattr(made._eval, k) for k in CACHE_STATE] == [None, {}, {}, set()]
         made = made.eval()
         subjects = [(made, _consumer(consumer, made, s), True), (hip, run, False)]
     else:
@@ -181,7 +182,7 @@ def test_writer_is_seen_by_consumer(dev, shared, writer, consumer, dtype, classe
         first = call()
         if written:
             # (before the result is read) a written model starts over: no graph of the old state is left, let alone replayed
-            assert len(m._eval_graphs) == 0
+            assert len(m._eval.graphs) == 0
             if writer in ec.REBUILDING or m is not hip:
                 assert m._flat_p.data_ptr() != armed_ptr[0] and m._flat_b.data_ptr() != armed_ptr[1]
         assert _same(first, want), f"{writer} -> {consumer}: first call after the writer"
@@ -189,7 +190,7 @@ def test_writer_is_seen_by_consumer(dev, shared, writer, consumer, dtype, classe
         assert _same(call(), want), f"{writer} -> {consumer}: second call (reuse path)"
         assert _same(call(), want), f"{writer} -> {consumer}: third call (graph, where one is captured)"
         if gkey is not None:
-            assert list(m._eval_graphs) == [gkey]
+            assert list(m._eval.graphs) == [gkey]
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI, no Python cache
@@ -256,7 +257,7 @@ def test_native_reuse_request_is_refused_for_other_parameter_or_buffer_addresses
 def _eager(m, x, calls=1):
     with _env("FLAIR_EVAL_GRAPH", "0"), torch.no_grad():
         outs = [m(x).clone() for _ in range(calls)]
-    assert len(m._eval_graphs) == 0
+    assert len(m._eval.graphs) == 0
     return outs[-1]
 
 
@@ -286,18 +287,18 @@ def test_failed_capture_falls_back_to_the_eager_call(dev, shared, monkeypatch):
             third = m(x)
         assert attempts == [1] and torch.equal(third, want)
         assert not torch.cuda.is_current_stream_capturing()
-        assert gkey in m._eval_nocapture and len(m._eval_graphs) == 0
+        assert gkey in m._eval.nocapture and len(m._eval.graphs) == 0
         for _ in range(3):
             assert torch.equal(m(x), want)
-        assert attempts == [1] and len(m._eval_graphs) == 0
+        assert attempts == [1] and len(m._eval.graphs) == 0
         # another kind of call under the same key is captured as usual
         p = [m.predict_classes(x).clone() for _ in range(3)]
-        assert list(m._eval_graphs) == [(False, True, False, False)] and torch.equal(p[0], p[2])
+        assert list(m._eval.graphs) == [(False, True, False, False)] and torch.equal(p[0], p[2])
     monkeypatch.undo()
     with torch.no_grad():
         m.weights_changed()                                # a new key: the mark is gone with the old one
         outs = [m(x) for _ in range(3)]
-    assert gkey in m._eval_graphs and all(torch.equal(o, want) for o in outs)
+    assert gkey in m._eval.graphs and all(torch.equal(o, want) for o in outs)
 
 
 def test_capture_survives_another_thread_that_pins_host_memory(dev, shared, monkeypatch):
@@ -327,4 +328,4 @@ def test_capture_survives_another_thread_that_pins_host_memory(dev, shared, monk
         outs = [m(x).clone() for _ in range(4)]
     assert len(pinned) == 1 and pinned[0].is_pinned()
     assert all(torch.equal(o, want) for o in outs)
-    assert list(m._eval_graphs) == [(True, False, False, False)]   # thread-local capture mode: the capture itself went through
+    assert list(m._eval.graphs) == [(True, False, False, False)]   # thread-local capture mode: the capture itself went through

@@ -166,11 +166,11 @@ def test_rowvec_request_is_one_shot_on_every_path(dev, small):
     B, _, H, W = x.shape
     # rows, then a plain forward that reuses the constants of the one before it
     with _env("FLAIR_EVAL_GRAPH", "0"):
-        m._eval_key = None
+        m._eval.key = None
         with_rows = m._c_forward(x, training=False, rows=v)
-        key = m._eval_key
+        key = m._eval.key
         again = m._c_forward(x, training=False)
-        assert m._eval_key == key                          # (same key: this forward ran with reuse_constants = 1)
+        assert m._eval.key == key                          # (same key: this forward ran with reuse_constants = 1)
     assert torch.equal(again, plain) and not torch.equal(with_rows, plain)
     # rows on a refused shape, then a plain forward
     ws = m._workspace(B, H, W, False)
@@ -184,7 +184,7 @@ def test_rowvec_request_is_one_shot_on_every_path(dev, small):
                                      L.stream(), None), "forward")
     assert torch.equal(out, plain)
     # rows alone on a training forward: refused with its code, nothing runs and nothing is kept
-    m._eval_key = None
+    m._eval.key = None
     wst = m._workspace(B, H, W, True)
     buffers = m._flat_b.clone()
     with torch.cuda.device(dev):
@@ -254,18 +254,18 @@ def test_predict_with_rows_replays_a_graph_that_takes_fresh_rows(dev):
     vs = [torch.randn(1, 16, generator=g).to(dev) for _ in range(5)]
     with _env("FLAIR_EVAL_GRAPH", "0"):
         want = [m.predict_classes(x, bottleneck_rows=v).clone() for v in vs]
-        assert len(m.__dict__.get("_eval_graphs", {})) == 0
+        assert len(m._eval.graphs) == 0
     assert not torch.equal(want[0], want[1])
-    m._eval_key = None
+    m._eval.key = None
     assert os.environ.get("FLAIR_EVAL_GRAPH") is None
     for i, (v, w) in enumerate(zip(vs, want)):
         got = m.predict_classes(x, bottleneck_rows=v)
         assert torch.equal(got, w), (i, int((got != w).sum()))
-        assert (len(m._eval_graphs) > 0) == (i >= 2)       # calls 3 to 5 replay
-    assert list(m._eval_graphs) == [(False, True, False, True)]
+        assert (len(m._eval.graphs) > 0) == (i >= 2)       # calls 3 to 5 replay
+    assert list(m._eval.graphs) == [(False, True, False, True)]
     # the plain key has a graph of its own and never sees the rows
     plain = [m.predict_classes(x).clone() for _ in range(3)]
-    assert torch.equal(plain[0], plain[2]) and not torch.equal(plain[2], want[4]) and len(m._eval_graphs) == 2
+    assert torch.equal(plain[0], plain[2]) and not torch.equal(plain[2], want[4]) and len(m._eval.graphs) == 2
 
 
 # ------------------------------------------------------------------------------------------------ 5. head epilogue

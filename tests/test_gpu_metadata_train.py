@@ -272,7 +272,7 @@ def test_train_request_hygiene(dev, small):
         m._c_forward(x, training=True, train_rows=(v[:, :4].contiguous(), drows))
     # the request meets an eval-mode forward: -17, nothing runs; a plain eval forward afterwards is the plain one
     m._flat_b.copy_(c["b0"]); m._flat_n.copy_(c["n0"])
-    m._eval_key = None
+    m._eval.key = None
     eval_plain = m._c_forward(x, training=False).clone()
     h = m._hh(False)
     ws = m._workspace(B, H, W, False)
@@ -298,7 +298,7 @@ def test_train_request_hygiene(dev, small):
         assert torch.equal(out, torch.full_like(out, 3.0)) and torch.equal(m._flat_b, buffers) and torch.equal(drows, sentinel)
         L.check(fwd(h, H, 0, ws, None), "forward")
     assert torch.equal(out, eval_plain)
-    m._eval_key = None
+    m._eval.key = None
     with torch.cuda.device(dev):
         # rows without a gradient pointer still refuse a training forward with their own code
         rc = fwd(m._h, H, 1, wst, L.UnetFwdOpts(rows_f32=L.ptr(v)))
@@ -344,7 +344,7 @@ def test_rows_step_fits_the_reported_workspace(dev, small, dtype):
     assert m._workspace(B, H, W, True).numel() == need
     drows = torch.full((2, 5), float("nan"), device=dev)
     got = _hip_step(c, torch.ones(2, 5, device=dev), drows)        # (L.check raises on -100, workspace too small)
-    assert m._live_ws.numel() == need and bool(torch.isfinite(drows).all()) and bool(torch.isfinite(got["grads"]).all())
+    assert m._live.ws.numel() == need and bool(torch.isfinite(drows).all()) and bool(torch.isfinite(got["grads"]).all())
 
 
 # ------------------------------------------------------------------------------------------------ 3. SegTrainer, 512 x 512
@@ -385,7 +385,7 @@ def _by_hand(model, enc, tr, img, lab, mtd, masks, lr):
         ops.sgd_step_(p.data, p.grad, lr)
         p.grad = None
     ops.sgd_step_(model._flat_p, tr.grads, lr)
-    model._native_writes = model.__dict__.get("_native_writes", 0) + 1
+    model._eval.note_native_write()
     return tr.loss.clone()
 
 

@@ -889,17 +889,17 @@ def test_small_eval_forwards_replay_a_hip_graph_with_identical_results(dev):
             want = [(hip(x).clone(), *[t.clone() for t in hip.predict_classes(x, want_prob=True)]) for x in xs]
     finally:
         os.environ.pop("FLAIR_EVAL_GRAPH")
-    hip._eval_key = None
+    hip._eval.key = None
     with torch.no_grad():
         for rep in range(2):
             for x, (lg, pr, pb) in zip(xs, want):
                 assert torch.equal(hip(x), lg)
                 p, q = hip.predict_classes(x, want_prob=True)
                 assert torch.equal(p, pr) and torch.equal(q, pb)
-        assert len(hip._eval_graphs) == 2                      # logits, and preds + probability
+        assert len(hip._eval.graphs) == 2                      # logits, and preds + probability
         next(iter(hip.parameters())).mul_(1.25)                # a torch in-place write: version counter moves
         a = hip(xs[0])
-        assert len(hip._eval_graphs) == 0 and not torch.equal(a, want[0][0])
+        assert len(hip._eval.graphs) == 0 and not torch.equal(a, want[0][0])
         m2 = flair_amd.create_model("unet", "resnet34", encoder_weights=None, in_channels=5, classes=13, compute_dtype="f32")
         m2.load_state_dict(hip.state_dict())
         assert torch.equal(a, m2.to(dev).eval()(xs[0]))
