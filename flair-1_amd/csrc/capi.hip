@@ -827,6 +827,16 @@ int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_
                           void* stream) {
   return tiff_lzw_encode(img, B, H, W, rows_per_strip, out, slot_bytes, counts, (hipStream_t)stream);
 }
+long flair_tiff_lzw_tile_slot_bytes(int tile, int samples) { return tiff_lzw_tile_slot_bytes(tile, samples); }
+int flair_tiff_lzw_encode_tiles(const void* raster, int src_f32, const float* scale, int bands, int H, int W, int tile, int interleave,
+                                long first_stream, long n_streams, uint8_t* out, long slot_bytes, int32_t* counts, void* stream) {
+  return tiff_lzw_encode_tiles(raster, src_f32, scale, bands, H, W, tile, interleave, first_stream, n_streams, out, slot_bytes, counts,
+                               (hipStream_t)stream);
+}
+int flair_tiff_pack_streams(const uint8_t* slots, long slot_bytes, const int32_t* counts, const int64_t* dst_off, long n_streams, uint8_t* dst,
+                            long dst_bytes, void* stream) {
+  return tiff_pack_streams(slots, slot_bytes, counts, (const long long*)dst_off, n_streams, dst, dst_bytes, (hipStream_t)stream);
+}
 int flair_tiff_lzw_decode_max_strip(void) { return tiff_lzw_decode_max_strip(); }
 int flair_tiff_lzw_decode(const uint8_t* src, long src_bytes, const int64_t* strip_src_off, const int32_t* strip_src_len,
                           const int64_t* strip_dst_off, const int32_t* strip_dst_len, const int32_t* strip_mode, long nstrips, uint8_t* dst,

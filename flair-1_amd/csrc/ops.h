@@ -149,6 +149,12 @@ int zone_error_map(const float* band, const unsigned char* truth, int Hr, int Wr
 long tiff_lzw_slot_bytes(int R, int W);
 int tiff_lzw_encode(const unsigned char* img, int B, int H, int W, int R, unsigned char* out, long slot_bytes, int* counts, hipStream_t s);
 // the inverse, strip by strip from device tables: per-strip status (include/flair_hip.h), two launches (strips up to 16 KB, up to the cap)
+// one stream per TIFF tile of a (bands, H, W) raster, u8 or fp32 with a per-band scale; packing streams out of their slots
+long tiff_lzw_tile_slot_bytes(int T, int samples);
+int tiff_lzw_encode_tiles(const void* raster, int src_f32, const float* scale, int bands, int H, int W, int T, int interleave,
+                          long first_stream, long n_streams, unsigned char* out, long slot_bytes, int* counts, hipStream_t s);
+int tiff_pack_streams(const unsigned char* slots, long slot_bytes, const int* counts, const long long* dst_off, long n_streams,
+                      unsigned char* dst, long dst_bytes, hipStream_t s);
 int tiff_lzw_decode_max_strip();
 int tiff_lzw_decode(const unsigned char* src, long src_bytes, const long long* strip_src_off, const int* strip_src_len,
                     const long long* strip_dst_off, const int* strip_dst_len, const int* strip_mode, long nstrips, unsigned char* dst,

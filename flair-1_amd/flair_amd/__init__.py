@@ -12,10 +12,11 @@ from .head import FusedCrossEntropyLoss, MulticlassJaccardIndex, MeanMetric
 from .task_module import segmentation_task_training, segmentation_task_predict
 from .train import SegTrainer, bucket_ranges, allreduce_buckets, shard_indices, reduce_validation_state
 from .data_feed import TileFeed, draw_d4
-from . import checkpoint, metrics, tasks_utils, writer, zone_detect, zone_metrics
+from . import checkpoint, metrics, raster_writer, tasks_utils, writer, zone_detect, zone_metrics
+from .raster_writer import read_geo_tags, tiled_tiff_header, tiled_tiff_ifd, write_raster
 
 __all__ = ["Unet", "create_model", "FLAIR_ModelFactory", "MetadataMLP", "FusedCrossEntropyLoss", "SegformerForSemanticSegmentation",
            "UperNetForSemanticSegmentation",
            "MulticlassJaccardIndex", "MeanMetric", "segmentation_task_training", "segmentation_task_predict",
            "SegTrainer", "bucket_ranges", "allreduce_buckets", "shard_indices", "reduce_validation_state", "TileFeed", "draw_d4", "checkpoint", "metrics", "tasks_utils",
-           "writer", "zone_detect", "zone_metrics"]
+           "writer", "zone_detect", "zone_metrics", "raster_writer", "write_raster", "read_geo_tags", "tiled_tiff_ifd", "tiled_tiff_header"]

@@ -126,6 +126,9 @@ PROTOTYPES = {
     "flair_zone_error_map": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, vp, vp, vp]),
     "flair_tiff_lzw_slot_bytes": (C.c_long, [i32, i32]),
     "flair_tiff_lzw_encode": (i32, [vp, i32, i32, i32, i32, vp, C.c_long, vp, vp]),
+    "flair_tiff_lzw_tile_slot_bytes": (C.c_long, [i32, i32]),
+    "flair_tiff_lzw_encode_tiles": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, C.c_long, C.c_long, vp, C.c_long, vp, vp]),
+    "flair_tiff_pack_streams": (i32, [vp, C.c_long, vp, vp, C.c_long, vp, C.c_long, vp]),
     "flair_tiff_lzw_decode_max_strip": (i32, []),
     "flair_tiff_lzw_decode": (i32, [vp, C.c_long, vp, vp, vp, vp, vp, C.c_long, vp, C.c_long, vp, vp]),
     "flair_segformer_create": (i32, [C.POINTER(vp), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32]),

@@ -379,6 +379,80 @@ def tiff_lzw_encode(u8, rows_per_strip=None):
     return out, counts, slot, R
 
 
+TIFF_INTERLEAVE = {"band": 0, "pixel": 1}   # PlanarConfiguration 2 / 1 (GDAL's INTERLEAVE=BAND / PIXEL)
+
+
+def tiff_lzw_tile_slot_bytes(tile, samples):
+    return int(L.lib().flair_tiff_lzw_tile_slot_bytes(int(tile), int(samples)))
+
+
+def tiff_tile_streams(bands, H, W, tile, interleave="band"):
+    """how many streams ``tiff_lzw_encode_tiles`` makes of a (bands, H, W) raster"""
+    if interleave not in TIFF_INTERLEAVE:
+        raise ValueError(f"interleave must be 'band' or 'pixel', got {interleave!r}")
+    return (1 if interleave == "pixel" else int(bands)) * -(-int(H) // int(tile)) * -(-int(W) // int(tile))
+
+
+def tiff_lzw_encode_tiles(raster, tile, interleave="band", scale=None, first_stream=0, n_streams=None):
+    """TIFF 6.0 LZW streams of the ``tile`` x ``tile`` TIFF tiles of a (bands, H, W) device raster, uint8 or float32 (include/flair_hip.h:
+    the stream order of each ``interleave``, zero padding of edge tiles).  A float32 raster needs ``scale``, one factor per band (a
+    sequence or a float32 device tensor): byte = uint8(trunc(min(max(v * scale, 0), 255))), NaN -> 0.  ``first_stream`` / ``n_streams``
+    select a window of the streams.  Returns (slots uint8 (n, slot_bytes), counts int32 (n,)): stream first_stream + i is
+    ``slots[i, :counts[i]]``."""
+    if raster.dim() != 3 or raster.dtype not in (torch.uint8, torch.float32):
+        raise L.FlairHipError("tiff_lzw_encode_tiles needs a (bands, H, W) uint8 or float32 tensor")
+    bands, H, W = raster.shape
+    tile = int(tile)
+    if tile < 16 or tile % 16:
+        raise ValueError(f"tile must be a positive multiple of 16, got {tile}")
+    total = tiff_tile_streams(bands, H, W, tile, interleave)
+    f32 = raster.dtype == torch.float32
+    if f32 != (scale is not None):
+        raise ValueError("a float32 raster needs a scale per band, a uint8 raster takes none")
+    src = L.ptr(raster)   # refuses host and non-contiguous tensors before anything is allocated
+    if f32:
+        if not torch.is_tensor(scale):
+            scale = torch.tensor([float(v) for v in scale], dtype=torch.float32).to(raster.device)
+        if scale.dtype != torch.float32 or scale.dim() != 1 or scale.numel() != bands:
+            raise ValueError(f"scale must hold one float32 factor per band ({bands})")
+    first_stream = int(first_stream)
+    n = total - first_stream if n_streams is None else int(n_streams)
+    if first_stream < 0 or n < 1 or first_stream + n > total:
+        raise ValueError(f"streams [{first_stream}, {first_stream + n}) are not a window of the raster's {total}")
+    slot = tiff_lzw_tile_slot_bytes(tile, bands if interleave == "pixel" else 1)
+    if slot < 0:
+        raise ValueError(f"a tile of {tile} x {tile} x {bands} samples is more than one stream holds")
+    slots = torch.empty(n, slot, dtype=torch.uint8, device=raster.device)
+    counts = torch.empty(n, dtype=torch.int32, device=raster.device)
+    L.check(L.lib().flair_tiff_lzw_encode_tiles(src, int(f32), L.ptr(scale), bands, H, W, tile, TIFF_INTERLEAVE[interleave], first_stream, n,
+                                                L.ptr(slots), slot, L.ptr(counts), L.stream()), "tiff_lzw_encode_tiles")
+    return slots, counts
+
+
+def tiff_pack_streams(slots, counts, slot_bytes, out=None):
+    """Packs encoded streams: (payload, offsets), stream i at ``payload[offsets[i] : offsets[i] + counts[i]]``, every offset a multiple of
+    16 (the exclusive sum of the rounded counts, int64 on the device), the bytes between two streams zero.  Without ``out`` the payload is
+    a new tensor of exactly the streams' rounded total, which costs one read of that total (a sync); ``out``, a flat uint8 device tensor
+    of at least ``n * slot_bytes`` bytes, is packed into without one and returned whole."""
+    n = int(counts.numel())
+    slot_bytes = int(slot_bytes)
+    if n < 1:
+        raise ValueError("tiff_pack_streams needs at least one stream")
+    if slots.dtype != torch.uint8 or counts.dtype != torch.int32 or slots.numel() != n * slot_bytes:
+        raise L.FlairHipError(f"tiff_pack_streams needs uint8 slots of {n} x {slot_bytes} bytes and int32 counts")
+    src, cnt = L.ptr(slots), L.ptr(counts)   # refuses host and non-contiguous tensors before anything is allocated
+    rounded = (counts.reshape(-1).to(torch.int64) + 15) & ~15
+    ends = torch.cumsum(rounded, 0)
+    offsets = ends - rounded
+    if out is None:
+        out = torch.empty(int(ends[-1]), dtype=torch.uint8, device=slots.device)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < n * slot_bytes:
+        raise L.FlairHipError(f"tiff_pack_streams: out must be a flat uint8 tensor of at least {n * slot_bytes} bytes")
+    L.check(L.lib().flair_tiff_pack_streams(src, slot_bytes, cnt, L.ptr(offsets), n, L.ptr(out), out.numel(), L.stream()),
+            "tiff_pack_streams")
+    return out, offsets
+
+
 def tiff_lzw_decode_max_strip():
     return int(L.lib().flair_tiff_lzw_decode_max_strip())
 

@@ -442,6 +442,26 @@ class ZoneDetector:
         self.window_confmats = confmats
         return out
 
+    def write(self, out: torch.Tensor, path, source=None, **kw) -> dict:
+        """What ``run`` returned, as the file the reference's pipeline ends in (main.py:206-232, :386-428): one tiled LZW BigTIFF with
+        tiles of ``img_pixels_detection``, encoded on the device (raster_writer.write_raster, which takes ``kw``: interleave, bigtiff,
+        group_bytes, tile).  'argmax': band 1 the class, band 2 the confidence as uint8(p * 255); 'class_prob': the
+        ``n_classes`` probability bytes.  ``source``: the input raster's file, whose GeoTIFF tags the output takes over."""
+        from . import raster_writer
+        bands, dtype = (2, torch.float32) if self.output_type == "argmax" else (self.n_classes, torch.uint8)
+        if not torch.is_tensor(out) or out.dim() != 3 or out.shape[0] != bands or out.dtype != dtype:
+            raise ValueError(f"output_type {self.output_type!r} writes a ({bands}, H, W) {dtype} raster, the one run returns")
+        kw.setdefault("tile", self.S)
+        if source is not None:
+            kw.setdefault("geo_tags", raster_writer.read_geo_tags(source))
+        return raster_writer.write_raster(path, out, scale=(1.0, 255.0) if self.output_type == "argmax" else None, **kw)
+
+    def run_to_file(self, raster_u8: torch.Tensor, path, truth_u8: torch.Tensor = None, source=None, **kw) -> torch.Tensor:
+        """``run`` followed by ``write``; returns the raster ``run`` returned"""
+        out = self.run(raster_u8, truth_u8)
+        self.write(out, path, source=source, **kw)
+        return out
+
 
 def compare(model, config: dict, raster_u8: torch.Tensor) -> dict:
     """The comparison loop of main.py:275-372 without raster files or metrics: one ZoneDetector per combination of

@@ -281,6 +281,32 @@ int flair_zone_error_map(const float* raster, const uint8_t* truth_u8, int raste
 long flair_tiff_lzw_slot_bytes(int rows_per_strip, int W);
 int flair_tiff_lzw_encode(const uint8_t* img, int B, int H, int W, int rows_per_strip, uint8_t* out, long slot_bytes, int32_t* counts,
                           void* stream);
+/* The same streams, one per TIFF tile of a raster resident on the device (the file of zone_detect, flair_amd/raster_writer.py).
+ * raster (bands, H, W) in band planes: uint8 (src_f32 = 0, scale unused) or fp32 (src_f32 = 1) with scale[bands] on the device,
+ *   byte = (uint8) trunc(min(max(v * scale[band], 0), 255)), NaN -> 0: one fp32 multiply, no FMA.
+ * Tiles are tile x tile pixels, tile a multiple of 16, ty = ceil(H / tile) by tx = ceil(W / tile) of them; pixels of a tile outside
+ *   the raster are 0 (TIFF tiles are always full size).
+ * interleave 0 (band, PlanarConfiguration 2): bands * ty * tx streams, stream (b * ty + y) * tx + x is the tile * tile bytes of band
+ *   b's tile (y, x), row-major.  interleave 1 (pixel, PlanarConfiguration 1): ty * tx streams of tile * tile * bands bytes, byte k is
+ *   row k / (tile * bands), column (k / bands) % tile, band k % bands.
+ * Streams [first_stream, first_stream + n_streams) are encoded: stream first_stream + i goes to out + i * slot_bytes, its length to
+ *   counts[i]; bytes of a slot past its count are unspecified, nothing is written outside a slot.
+ * flair_tiff_lzw_tile_slot_bytes: the smallest slot_bytes accepted, flair_tiff_lzw_slot_bytes' bound for tile * tile * samples bytes
+ *   (samples = 1 for band interleave, bands for pixel interleave); -1 for an argument < 1 or a stream above 2^30 bytes.
+ * flair_tiff_lzw_encode_tiles: -1 for a null pointer (scale with src_f32 = 1 included), an extent < 1, a tile that is no multiple of
+ *   16, a flag other than 0 / 1 or a window outside the streams; -100 for slot_bytes below flair_tiff_lzw_tile_slot_bytes; -2 unless
+ *   out is 16-byte aligned, slot_bytes a multiple of 16 and counts, scale and an fp32 raster 4-byte aligned. */
+long flair_tiff_lzw_tile_slot_bytes(int tile, int samples);
+int flair_tiff_lzw_encode_tiles(const void* raster, int src_f32, const float* scale, int bands, int H, int W, int tile, int interleave,
+                                long first_stream, long n_streams, uint8_t* out, long slot_bytes, int32_t* counts, void* stream);
+/* Compaction of encoded streams: the counts[i] bytes at slots + i * slot_bytes are copied to dst + dst_off[i], i < n_streams, one
+ * workgroup per stream, 16 bytes per lane.  dst_off (int64, on the device) holds multiples of 16; the bytes from the stream's end to
+ * the next multiple of 16 are written as zeros, nothing else of dst is written: stream i owns
+ * [dst_off[i], dst_off[i] + round_up(counts[i], 16)).  A stream with a count outside [0, slot_bytes], or whose offset is negative, no
+ * multiple of 16 or leaves that range outside [0, dst_bytes), is skipped.  -1 for a null pointer, n_streams < 1, slot_bytes < 16 or
+ * dst_bytes < 0; -2 unless slots and dst are 16-byte aligned, slot_bytes a multiple of 16, counts 4-byte and dst_off 8-byte aligned. */
+int flair_tiff_pack_streams(const uint8_t* slots, long slot_bytes, const int32_t* counts, const int64_t* dst_off, long n_streams, uint8_t* dst,
+                            long dst_bytes, void* stream);
 /* The inverse on the device (the read path of metrics()): strip i, the bytes [strip_src_off[i], + strip_src_len[i]) of src, is
  * decoded into [strip_dst_off[i], + strip_dst_len[i]) of dst; strip_mode[i] 0 = stored (Compression 1: a copy), 1 = LZW (Compression
  * 5).  All pointers are device pointers, the five tables have nstrips entries, status receives one code per strip.  One wave per
