@@ -46,7 +46,8 @@ const char* flair_strerror(int code) {
     case -1: return "null or invalid handle or argument (flair_unet_fwd_opts_t: maxprob_f32 needs preds_u8; ce_labels needs ce_loss, "
                     "ce_workspace and a ce_label_kind in 0..3; drows_f32 needs rows_f32)";
     case -2: return "channel count / pointer alignment not supported by the kernel";
-    case -3: return "output rows too short for whole 16-byte chunks (channel count / row stride)";
+    case -3: return "output rows too short for whole 16-byte chunks (channel count / row stride), or flair_ce_head(_nhwc): NHWC logits / "
+                    "gradient rows not 16-byte aligned, workspace not 4-byte aligned";
     case -4: return "fused upsample needs even extents";
     case -5: return "unsupported stride";
     case -6: return "requested fused epilogue / input transform is not available in the kernel this shape dispatches to";

@@ -46,10 +46,10 @@ __global__ __launch_bounds__(256) void ce_labels_kernel(const void* __restrict__
   __shared__ float sh[4];
   float acc = 0.f;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x) {
-    int y;
+    long long y;   // the range check is made on the label in its own width: 2^32 + 3 is not class 3
     if (kind == 0) y = ((const unsigned char*)labels)[i];
     else if (kind == 1) y = ((const int*)labels)[i];
-    else if (kind == 2) y = (int)((const long long*)labels)[i];
+    else if (kind == 2) y = ((const long long*)labels)[i];
     else {
       const long n = i / HW, pix = i - n * HW;
       const float* p = (const float*)labels + n * C * HW + pix;
@@ -60,9 +60,9 @@ __global__ __launch_bounds__(256) void ce_labels_kernel(const void* __restrict__
         if (v > best) { best = v; y = c; }
       }
     }
-    const bool ok = (unsigned)y < (unsigned)C;
+    const bool ok = (unsigned long long)y < (unsigned long long)C;
     lab8[i] = ok ? (unsigned char)y : (unsigned char)255;
-    if (targets_i32) targets_i32[i] = y;
+    if (targets_i32) targets_i32[i] = y == (long long)(int)y ? (int)y : -1;   // an ignored label int32 cannot hold: -1
     if (ok) acc += weight ? weight[y] : 1.f;
   }
   const float r = block_sum(acc, sh);
@@ -384,6 +384,15 @@ int ce_finish(float* ws, long npix, int nblk, float* loss, hipStream_t s) {
 int ce_head(const CeArgs& a, hipStream_t s) {
   if (a.C > MAXC || a.C < 1) return -2;
   if (a.dlogits_nhwc && (a.dlogits_ld < a.C || a.dlogits_ld > MAXC || a.dlogits_ld % (a.dlogits_dtype == DT_F32 ? 4 : 8))) return -3;
+  // every refusal comes before the first launch.  NHWC rows are read and written in 16-byte chunks whatever kernel runs; the
+  // workspace holds fp32 partials (and lab8 is read a 32-bit word at a time by the four-pixel kernel)
+  if (((uintptr_t)a.logits_nhwc | (uintptr_t)a.dlogits_nhwc) & 15) return -3;
+  if ((uintptr_t)a.workspace & 3) return -3;
+  if (a.logits_nhwc) {
+    const int ld = a.logits_ld;
+    if ((ld != 16 && ld != 24 && ld != 32) || ld < a.C || a.dlogits_nchw || a.preds_i64 || (a.dlogits_nhwc && (a.dlogits_ld != ld || a.dlogits_dtype != a.logits_dtype)))
+      return -3;
+  }
   const long HW = (long)a.H * a.W, npix = HW * a.B;
   const int nb = ce_blocks(npix);
   const CeWorkspace wsl = ce_workspace_layout(a.workspace, npix);
@@ -393,8 +402,6 @@ int ce_head(const CeArgs& a, hipStream_t s) {
   if (int rc = ce_labels(a.labels, a.label_kind, a.weight, a.B, a.C, a.H, a.W, a.targets_i32, a.workspace, s)) return rc;
   if (a.logits_nhwc) {
     const int ld = a.logits_ld;
-    if ((ld != 16 && ld != 24 && ld != 32) || ld < a.C || a.dlogits_nchw || a.preds_i64 || (a.dlogits_nhwc && (a.dlogits_ld != ld || a.dlogits_dtype != a.logits_dtype)))
-      return -3;
     ProfScope ps("ce_main", 0.0, (double)npix * (2.0 * ld * dtype_size(a.logits_dtype) + 2), s);
     if (a.logits_dtype == DT_F32) {
       auto kern = ld == 16 ? ce_main_nhwc_kernel<float, 16> : ld == 24 ? ce_main_nhwc_kernel<float, 24> : ce_main_nhwc_kernel<float, 32>;
@@ -575,10 +582,10 @@ int softmax_argmax(const float* logits, int B, int C, int H, int W, unsigned cha
   return 0;
 }
 
-__device__ __forceinline__ int load_label(const void* p, int kind, long i) {
+__device__ __forceinline__ long long load_label(const void* p, int kind, long i) {
   if (kind == 0) return ((const unsigned char*)p)[i];
   if (kind == 1) return ((const int*)p)[i];
-  return (int)((const long long*)p)[i];
+  return ((const long long*)p)[i];
 }
 
 // confmat[target][pred] += 1  (torchmetrics update; sklearn confusion_matrix(labels=range(C)) of
@@ -589,8 +596,9 @@ __global__ __launch_bounds__(256) void confmat_kernel(const void* __restrict__ t
   for (int i = threadIdx.x; i < C * C; i += 256) hist[i] = 0;
   __syncthreads();
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int t = load_label(target, tk, i), p = load_label(pred, pk, i);
-    if ((unsigned)t < (unsigned)C && (unsigned)p < (unsigned)C) atomicAdd(&hist[t * C + p], 1u);
+    const long long t = load_label(target, tk, i), p = load_label(pred, pk, i);   // range check before any narrowing
+    if ((unsigned long long)t < (unsigned long long)C && (unsigned long long)p < (unsigned long long)C)
+      atomicAdd(&hist[(int)t * C + (int)p], 1u);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < C * C; i += 256) {

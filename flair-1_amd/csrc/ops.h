@@ -84,7 +84,7 @@ struct CeArgs {
   int B, C, H, W;
   float* loss;                // out: scalar mean loss
   float* dlogits_nchw;        // optional out: fp32 NCHW gradient of the mean loss
-  void* dlogits_nhwc;         // optional out: NHWC T gradient, row stride ld (>= C), padded columns zeroed
+  void* dlogits_nhwc;         // optional out: NHWC T gradient, row stride ld (>= C), padded columns zeroed; like logits_nhwc 16-byte aligned (-3)
   int dlogits_dtype, dlogits_ld;
   unsigned char* preds_u8;    // optional out [B][H][W]
   long long* preds_i64;       // optional out [B][H][W]

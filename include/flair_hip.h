@@ -128,7 +128,12 @@ int flair_unet_encoder_backward(flair_unet_t* h, const float* params, const floa
  *   preds = argmax(softmax(logits, 1), 1)                                   task_module.py:75-76
  *   MulticlassJaccardIndex.update: confmat += bincount(target*C + pred)     task_module.py:85,107-108
  * label_kind: 0 uint8 (B,H,W), 1 int32, 2 int64, 3 fp32 one-hot (B,C,H,W) (the reference's batch["msk"]).
- * Outputs are optional (null = skip).  workspace: flair_ce_workspace_bytes(). */
+ * A label outside [0, C) is ignored (no loss, no gradient, no count), judged in the label's own width: the int64 label 2^32 + 3 is
+ * ignored, not class 3.  targets_i32 gets the label itself, or -1 for an ignored int64 label that int32 cannot hold.
+ * Outputs are optional (null = skip).  workspace: flair_ce_workspace_bytes(), 4-byte aligned.
+ * Returns, before anything is enqueued: -1 a required pointer is null or label_kind is outside 0..3; -2 C outside 1..32 (or, _nhwc,
+ * a dtype that is neither fp32 nor bf16); -3 NHWC rows: ld not 16 / 24 / 32 (_nhwc) or < C, dlogits_ld < C, > 32 or not whole
+ * 16-byte chunks (a multiple of 4 fp32 / 8 bf16), logits_nhwc or dlogits_nhwc not 16-byte aligned, workspace not 4-byte aligned. */
 size_t flair_ce_workspace_bytes(int B, int H, int W);
 int flair_ce_head(const float* logits_nchw, const void* labels, int label_kind, const float* class_weight, int B, int C,
                   int H, int W, float* loss, float* dlogits_nchw, void* dlogits_nhwc, int dlogits_dtype, int dlogits_ld,
