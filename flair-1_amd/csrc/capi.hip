@@ -845,6 +845,18 @@ int flair_tiff_lzw_decode(const uint8_t* src, long src_bytes, const int64_t* str
   return tiff_lzw_decode(src, src_bytes, (const long long*)strip_src_off, strip_src_len, (const long long*)strip_dst_off, strip_dst_len,
                          strip_mode, nstrips, dst, dst_bytes, status, (hipStream_t)stream);
 }
+int flair_tiff_lzw_decode_chunks_cap(void) { return tiff_lzw_decode_chunks_cap(); }
+int flair_tiff_lzw_decode_chunks_window(void) { return tiff_lzw_decode_chunks_window(); }
+int flair_tiff_lzw_decode_chunks(const uint8_t* src, long src_bytes, const int64_t* src_off, const int32_t* src_len, const int32_t* dst_len,
+                                 const int32_t* mode, long nchunks, uint8_t* scratch, long slot_bytes, int32_t* status, void* stream) {
+  return tiff_lzw_decode_chunks(src, src_bytes, (const long long*)src_off, src_len, dst_len, mode, nchunks, scratch, slot_bytes, status,
+                                (hipStream_t)stream);
+}
+int flair_tiff_chunks_to_planes(const uint8_t* scratch, long slot_bytes, const int32_t* chunks, const int32_t* status, long nchunks,
+                                int max_rows, int samples, int predictor, uint8_t* planes, int bands, int H, int W, void* stream) {
+  return tiff_chunks_to_planes(scratch, slot_bytes, chunks, status, nchunks, max_rows, samples, predictor, planes, bands, H, W,
+                               (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------ SegFormer (zone_detect, HuggingFace provider)
 int flair_segformer_create(flair_segformer_t** out, int in_channels, int num_labels, const int depths[4], const int hidden_sizes[4],

@@ -159,5 +159,13 @@ int tiff_lzw_decode_max_strip();
 int tiff_lzw_decode(const unsigned char* src, long src_bytes, const long long* strip_src_off, const int* strip_src_len,
                     const long long* strip_dst_off, const int* strip_dst_len, const int* strip_mode, long nstrips, unsigned char* dst,
                     long dst_bytes, int* status, hipStream_t s);
+// the chunks (tiles or strips) of a raster file into slots of a scratch buffer, any size up to the cap, and the slots into the band
+// planes with the horizontal predictor undone (csrc/tiff_read.hip)
+int tiff_lzw_decode_chunks_cap();
+int tiff_lzw_decode_chunks_window();
+int tiff_lzw_decode_chunks(const unsigned char* src, long src_bytes, const long long* src_off, const int* src_len, const int* dst_len,
+                           const int* mode, long nchunks, unsigned char* scratch, long slot_bytes, int* status, hipStream_t s);
+int tiff_chunks_to_planes(const unsigned char* scratch, long slot_bytes, const int* chunks, const int* status, long nchunks, int max_rows,
+                          int samples, int predictor, unsigned char* planes, int bands, int H, int W, hipStream_t s);
 
 }  // namespace flair

@@ -1,0 +1,256 @@
+// The read path of zone_detect's input raster (flair_amd/raster_reader.py): the chunks of a TIFF (tiles or strips, stored or LZW) are
+// decoded into slots of a scratch buffer, one wave per chunk, and a second kernel scatters the slots into the (bands, H, W) band-plane
+// raster, undoing the horizontal predictor on the way.  The stream rules and the status codes are those of tiff_lzw_decode_kernel
+// (csrc/tiff_lzw.hip); what differs is the size: a 512 x 512 tile of 5 interleaved bands is 1.3 MB, so the decoded output lives in
+// the slot, in global memory, and not in LDS.
+//
+// The decoder keeps the parent's idea: every string a code can name already lies contiguously in the decoded output, so the table
+// holds (position, length) and a code is emitted as a copy from earlier output, 64 bytes per step across the lanes; the serial chain
+// is per code, not per byte.  Positions are 32 bits now (RD_CAP = 16 MiB), lengths stay below RD_MAXSTR: an entry is one byte longer
+// than the string before it, so the longest of the 3838 entries between two clears has 3839 bytes.
+//
+// Where the copy reads from.  The most recent output lies in an LDS ring of RD_RING bytes, position p at ring[p % RD_RING].  After
+// every code the completed 128-byte blocks of the output (the slot is 128-byte aligned, so these are whole cache lines) are flushed
+// from the ring to the slot, 16 bytes per lane: flushed = op & ~127 at the start of every round, op the bytes produced so far.  A
+// code's source byte at position s is read from the ring if s >= op - RD_WINDOW and from the slot otherwise (only a Clear bounds how
+// far back a source lies: a run of equal bytes fills the table very slowly).  RD_WINDOW = RD_RING - RD_MAXSTR, because the copy
+// itself, at most RD_MAXSTR - 1 bytes at [op, op + n), overwrites the ring places of [op - RD_RING, op + n - RD_RING): all of them
+// older than the window, whatever step of the copy reads.  A source always lies below op and a destination at or above it, so no
+// step of a copy reads what another step of it wrote.
+//
+// The read-back is a cross-lane read of the wave's own global stores: lane a's flush store is lane b's load.  Its argument:
+//  (1) only positions below op - RD_WINDOW <= flushed are read from the slot, and flushed is a multiple of 128 on a 128-byte aligned
+//      slot: a cache line is read only after its last byte was stored, never while unflushed bytes of it are still to come, and it is
+//      never stored to again.  So no copy of a line that any cache can hold is ever older than the line's final content, provided
+//      the stores have left the wave and the L1's copy, if it has one, is dropped:
+//  (2) before a read-back whose source ends above `fenced` (the positions the last fence covered) the wave waits for its stores
+//      (vmcnt(0)), releases at agent scope (the flush stores reach L2), waits again, acquires at agent scope (this CU's L1 drops its
+//      lines) and sets fenced = flushed.  Sources are at least RD_WINDOW behind op and the fence covers all but the last < 128
+//      bytes, so the next fence is due after another RD_WINDOW - 128 bytes of output at the earliest: one fence pair per 12 KB of
+//      output in the worst case, none at all in a chunk whose references stay inside the window.  fenced starts at 0, so the first
+//      read-back of a chunk is always behind an acquire.
+//  (3) the read-back loads are per-lane byte loads through a pointer that is neither const nor __restrict__: vector loads, never
+//      the scalar cache.
+//
+// Bit parsing is the parent's: the input is held 256 bytes per register of the wave, one chunk ahead, a code is cut out of two words
+// read with v_readlane, every round consumes at least 9 bits of the chunk or ends.  Lane 0 alone writes the table.
+#include "ops.h"
+#include "prof.h"
+
+namespace flair {
+
+namespace {
+
+constexpr int RD_CLEAR = 256, RD_EOI = 257, RD_FIRST = 258;
+constexpr int RD_FETCH = 256;                        // input bytes per fetch: 64 lanes x 4
+constexpr int RD_ENTRIES = 4096 - RD_FIRST;
+constexpr int RD_RING = 16384;                       // a power of two
+constexpr int RD_MAXSTR = 4096;                      // above the longest string, RD_ENTRIES + 1
+constexpr int RD_WINDOW = RD_RING - RD_MAXSTR;
+constexpr int RD_BLOCK = 128;                        // the flush unit: one cache line
+constexpr int RD_CAP = 1 << 24;                      // decoded bytes of an LZW chunk
+static_assert((RD_RING & (RD_RING - 1)) == 0 && RD_ENTRIES + 1 < RD_MAXSTR && RD_WINDOW > RD_BLOCK, "ring geometry");
+
+// 4 bytes of the chunk at `off` (any alignment) as one big-endian word; offsets past the chunk's end are clamped to its last byte
+__device__ __forceinline__ unsigned rd_fetch_be(const unsigned char* __restrict__ src, long off, long n) {
+  unsigned w = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) w = (w << 8) | src[min(off + e, n - 1)];
+  return w;
+}
+
+// LDS stores of some lanes are read by other lanes afterwards: complete them, and keep the compiler from moving accesses across
+__device__ __forceinline__ void rd_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// (2) of the argument above; every lane of the wave executes it
+__device__ __forceinline__ void rd_publish_flushed() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+__global__ __launch_bounds__(64) void tiff_lzw_decode_chunks_kernel(const unsigned char* __restrict__ src, long src_bytes,
+                                                                    const long long* __restrict__ src_off, const int* __restrict__ src_len,
+                                                                    const int* __restrict__ dst_len, const int* __restrict__ mode,
+                                                                    unsigned char* scratch, long slot_bytes, int* __restrict__ status) {
+  __shared__ __attribute__((aligned(16))) unsigned char ring[RD_RING];
+  __shared__ unsigned tpos[RD_ENTRIES];          // entry of code k: its string is [tpos, tpos + tlen) of the output
+  __shared__ unsigned short tlen[RD_ENTRIES];
+  constexpr int M = RD_RING - 1;
+  const int lane = threadIdx.x;
+  const long chunk = blockIdx.x;
+  const long so = src_off[chunk];
+  const int sn = src_len[chunk], dn = dst_len[chunk], md = mode[chunk];
+  const bool ok = so >= 0 && sn >= 0 && dn >= 1 && so <= src_bytes - sn && dn <= slot_bytes && (md == 0 || (md == 1 && dn <= RD_CAP));
+  if (!ok) { if (lane == 0) status[chunk] = 5; return; }
+  const unsigned char* __restrict__ s = src + so;
+  unsigned char* g = scratch + chunk * slot_bytes;   // 128-byte aligned; read back below: no __restrict__
+  if (md == 0) {
+    // stored: the slot is aligned, the source is not; 4 bytes per lane, put together as one word
+    const int n = min(sn, dn), n4 = n & ~3;
+    for (int i = 4 * lane; i < n4; i += 256)
+      *reinterpret_cast<unsigned*>(g + i) = s[i] | (s[i + 1] << 8) | (s[i + 2] << 16) | ((unsigned)s[i + 3] << 24);
+    if (n4 + lane < n) g[n4 + lane] = s[n4 + lane];
+    if (lane == 0) status[chunk] = sn >= dn ? 0 : 1;
+    return;
+  }
+  if (sn == 0) { if (lane == 0) status[chunk] = 1; return; }
+
+  const long nbits = (long)sn * 8;
+  unsigned cur = rd_fetch_be(s, 4 * lane, sn), ahead = rd_fetch_be(s, RD_FETCH + 4 * lane, sn);
+  long base = 0;                       // the chunk offset of `cur`, bytes
+  int b = 0;                           // the next code's bit offset inside `cur`, < 2048
+  int nxt = RD_FIRST, width = 9, op = 0, st;
+  int flushed = 0, fenced = 0;         // multiples of RD_BLOCK: [0, flushed) is in the slot, [0, fenced) may be read back
+  int old_pos = 0, old_len = 0;        // where the previous code's string was emitted; length 0: no previous code
+  // every round consumes `width` >= 9 bits of the chunk or ends: at most src_len * 8 / 9 rounds whatever the bytes are
+  for (;;) {
+    if (op >= dn) { st = 0; break; }
+    if (base * 8 + b + width > nbits) { st = 1; break; }
+    const int wi = b >> 5;
+    const unsigned w0 = __builtin_amdgcn_readlane(cur, wi);
+    const unsigned w1 = wi < 63 ? __builtin_amdgcn_readlane(cur, (wi + 1) & 63) : __builtin_amdgcn_readlane(ahead, 0);
+    const int code = (int)(((((unsigned long long)w0 << 32) | w1) >> (64 - (b & 31) - width)) & ((1u << width) - 1));
+    b += width;
+    if (b >= 8 * RD_FETCH) {
+      b -= 8 * RD_FETCH;
+      base += RD_FETCH;
+      cur = ahead;
+      ahead = rd_fetch_be(s, base + RD_FETCH + 4 * lane, sn);
+    }
+    if (code == RD_CLEAR) { nxt = RD_FIRST; width = 9; old_len = 0; continue; }
+    if (code == RD_EOI) { st = 2; break; }
+    int n = 1;
+    if (old_len == 0) {
+      if (code >= 256) { st = 3; break; }
+      if (lane == 0) ring[op & M] = (unsigned char)code;
+    } else {
+      // the string of `code`: [from, from + len) of the output, except that at index `wrap` it starts over (code == nxt: string(old)
+      // and its own first byte again, which is where this copy's first byte lands; the source stays below `op` all the same)
+      int from = 0, len = 1, wrap = 0x7fffffff;
+      if (code >= 256) {
+        if (code < nxt) {
+          from = (int)__builtin_amdgcn_readfirstlane(tpos[code - RD_FIRST]);
+          len = (int)__builtin_amdgcn_readfirstlane((unsigned)tlen[code - RD_FIRST]);
+        } else if (code == nxt && nxt < 4096) {
+          from = old_pos; len = old_len + 1; wrap = old_len;
+        } else { st = 4; break; }
+      }
+      n = min(len, dn - op);
+      if (code < 256) {
+        if (lane == 0) ring[op & M] = (unsigned char)code;
+      } else {
+        const int lo = op - RD_WINDOW;            // sources below it come from the slot; lo <= flushed
+        if (from < lo && min(from + min(n, wrap), lo) > fenced) {
+          rd_publish_flushed();
+          fenced = flushed;
+        }
+        for (int j = lane; j < n; j += 64) {
+          const int sp = from + (j < wrap ? j : 0);
+          ring[(op + j) & M] = sp >= lo ? ring[sp & M] : g[sp];
+        }
+      }
+      if (nxt < 4096) {
+        if (lane == 0) { tpos[nxt - RD_FIRST] = (unsigned)old_pos; tlen[nxt - RD_FIRST] = (unsigned short)(old_len + 1); }
+        ++nxt;
+        if (nxt == 511 || nxt == 1023 || nxt == 2047) ++width;
+      }
+    }
+    rd_lds_order();
+    old_pos = op; old_len = n; op += n;
+    const int upto = op & ~(RD_BLOCK - 1);
+    if (upto > flushed) {                        // whole blocks: at most RD_MAXSTR bytes, all of them still in the ring
+      for (int i = flushed + 16 * lane; i < upto; i += 1024)
+        *reinterpret_cast<uint4*>(g + i) = *reinterpret_cast<const uint4*>(ring + (i & M));
+      flushed = upto;
+    }
+  }
+  // what was produced past the last whole block (all of the chunk's rest at status 0): fewer than RD_BLOCK bytes
+  for (int i = flushed + lane; i < op; i += 64) g[i] = ring[i & M];
+  if (lane == 0) status[chunk] = st;
+}
+
+// Chunk c's decoded bytes, rows x width pixels of `samples` bytes each, row-major, to the band planes: sample k of the pixel at
+// (r, x) goes to planes[band0 + k][y0 + r][x0 + x] when that lies inside the raster.  One wave per chunk row, a lane per pixel, 64
+// pixels a trip: the stores of a trip are 64 consecutive bytes of one plane row.  PRED: TIFF predictor 2, per sample the running
+// sum modulo 256 along the chunk row, as an inclusive wave scan per trip plus the carry of the trips before (lane 63's sum).
+template <bool PRED>
+__global__ __launch_bounds__(256) void tiff_chunks_to_planes_kernel(const unsigned char* __restrict__ scratch, long slot_bytes,
+                                                                    const int* __restrict__ chunks, const int* __restrict__ status,
+                                                                    int samples, unsigned char* __restrict__ planes, int bands, int H, int W) {
+  const long c = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (status[c] != 0) return;
+  const int x0 = chunks[5 * c], y0 = chunks[5 * c + 1], width = chunks[5 * c + 2], rows = chunks[5 * c + 3], band0 = chunks[5 * c + 4];
+  if (x0 < 0 || y0 < 0 || width < 1 || rows < 1 || band0 < 0 || band0 > bands - samples) return;
+  if ((long)width * rows * samples > slot_bytes) return;
+  const unsigned char* __restrict__ slot = scratch + c * slot_bytes;
+  const long plane = (long)H * W;
+  for (int r = blockIdx.y * 4 + wave; r < rows; r += gridDim.y * 4) {
+    const int y = y0 + r;
+    if (y >= H) return;                                     // rows of an edge tile below the raster, and every row after
+    const unsigned char* __restrict__ row = slot + (long)r * width * samples;
+    unsigned char* __restrict__ out = planes + (long)band0 * plane + (long)y * W + x0;
+    for (int k = 0; k < samples; ++k) {
+      unsigned carry = 0;
+      for (int xb = 0; xb < width; xb += 64) {
+        const int x = xb + lane;
+        unsigned v = x < width ? row[(long)x * samples + k] : 0u;
+        if (PRED) {
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            const unsigned t = __shfl_up(v, d, 64);
+            if (lane >= d) v += t;
+          }
+          v = (v + carry) & 0xffu;
+          carry = __shfl(v, 63, 64);
+        }
+        if (x < width && x0 + x < W) out[(long)k * plane + x] = (unsigned char)v;
+        if (x0 + xb + 64 >= W) break;                      // the rest of the row lies right of the raster
+      }
+    }
+  }
+}
+
+}  // namespace
+
+int tiff_lzw_decode_chunks_cap() { return RD_CAP; }
+int tiff_lzw_decode_chunks_window() { return RD_WINDOW; }
+
+int tiff_lzw_decode_chunks(const unsigned char* src, long src_bytes, const long long* src_off, const int* src_len, const int* dst_len,
+                           const int* mode, long nchunks, unsigned char* scratch, long slot_bytes, int* status, hipStream_t s) {
+  if (!src || !src_off || !src_len || !dst_len || !mode || !scratch || !status) return -1;
+  if (nchunks < 1 || nchunks > 0x7fffffffL || src_bytes < 0 || slot_bytes < 1) return -1;
+  if (((uintptr_t)scratch & (RD_BLOCK - 1)) || (slot_bytes & (RD_BLOCK - 1)) || ((uintptr_t)src_off & 7) || ((uintptr_t)src_len & 3) ||
+      ((uintptr_t)dst_len & 3) || ((uintptr_t)mode & 3) || ((uintptr_t)status & 3))
+    return -2;   // blocks of the slot are flushed as aligned cache lines
+  ProfScope ps("tiff_lzw_decode_chunks", 0.0, 0.0, s);
+  hipLaunchKernelGGL(tiff_lzw_decode_chunks_kernel, dim3((unsigned)nchunks), dim3(64), 0, s, src, src_bytes, src_off, src_len, dst_len, mode,
+                     scratch, slot_bytes, status);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+int tiff_chunks_to_planes(const unsigned char* scratch, long slot_bytes, const int* chunks, const int* status, long nchunks, int max_rows,
+                          int samples, int predictor, unsigned char* planes, int bands, int H, int W, hipStream_t s) {
+  if (!scratch || !chunks || !status || !planes) return -1;
+  if (nchunks < 1 || nchunks > 0x7fffffffL || slot_bytes < 1 || max_rows < 1 || bands < 1 || H < 1 || W < 1) return -1;
+  if ((samples != 1 && samples != bands) || (predictor != 1 && predictor != 2)) return -1;
+  if (((uintptr_t)chunks & 3) || ((uintptr_t)status & 3)) return -2;
+  const dim3 grid((unsigned)nchunks, (unsigned)min((max_rows + 3) / 4, 65535)), block(256);
+  ProfScope ps("tiff_chunks_to_planes", 0.0, 0.0, s);
+  if (predictor == 2)
+    hipLaunchKernelGGL((tiff_chunks_to_planes_kernel<true>), grid, block, 0, s, scratch, slot_bytes, chunks, status, samples, planes, bands, H, W);
+  else
+    hipLaunchKernelGGL((tiff_chunks_to_planes_kernel<false>), grid, block, 0, s, scratch, slot_bytes, chunks, status, samples, planes, bands, H, W);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace flair

@@ -487,6 +487,78 @@ def tiff_lzw_decode(src, src_off, src_len, dst_off, dst_len, mode, dst_bytes, ou
     return out, status
 
 
+def tiff_lzw_decode_chunks_cap():
+    return int(L.lib().flair_tiff_lzw_decode_chunks_cap())
+
+
+def tiff_lzw_decode_chunks_window():
+    return int(L.lib().flair_tiff_lzw_decode_chunks_window())
+
+
+TIFF_SLOT_ALIGN = 128   # slots of tiff_lzw_decode_chunks: the base and slot_bytes are multiples of it
+
+_CHUNK_TABLE_DTYPES = (("src_off", torch.int64), ("src_len", torch.int32), ("dst_len", torch.int32), ("mode", torch.int32))
+
+
+def tiff_lzw_decode_chunks(src, src_off, src_len, dst_len, mode, slot_bytes, out=None, status=None):
+    """Decodes the chunks (tiles or strips) of a TIFF on the device: chunk i, ``src[src_off[i] : src_off[i] + src_len[i]]``, goes to
+    ``scratch[i, :dst_len[i]]``; ``mode[i]`` 0 = stored, 1 = LZW, decoded lengths up to ``tiff_lzw_decode_chunks_cap()``.  ``src`` is a
+    flat uint8 device tensor, the four tables are device tensors of one length (offsets int64, the others int32), ``slot_bytes`` a
+    multiple of 128.  Returns (scratch uint8 (n, slot_bytes), status int32 per chunk; include/flair_hip.h lists the codes).  ``out``, a
+    uint8 device tensor of n * slot_bytes bytes whose address is a multiple of 128, is decoded into when given, and ``status``, a flat int32
+    device tensor of n entries, receives the codes."""
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise L.FlairHipError("tiff_lzw_decode_chunks needs a flat uint8 tensor of compressed bytes")
+    tables = (src_off, src_len, dst_len, mode)
+    n = int(src_off.numel())
+    for t, (name, dt) in zip(tables, _CHUNK_TABLE_DTYPES):
+        if t.dtype != dt or t.dim() != 1 or t.numel() != n:
+            raise L.FlairHipError(f"tiff_lzw_decode_chunks: {name} must be a flat {dt} tensor of {n} entries")
+    slot_bytes = int(slot_bytes)
+    if n < 1 or slot_bytes < TIFF_SLOT_ALIGN or slot_bytes % TIFF_SLOT_ALIGN:
+        raise ValueError(f"tiff_lzw_decode_chunks needs at least one chunk and slot_bytes a positive multiple of {TIFF_SLOT_ALIGN}")
+    ptrs = [L.ptr(src)] + [L.ptr(t) for t in tables]   # refuses host and non-contiguous tensors before anything is allocated
+    if out is None:
+        out = torch.empty(n, slot_bytes, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or out.numel() != n * slot_bytes or out.data_ptr() % TIFF_SLOT_ALIGN:
+        raise L.FlairHipError(f"tiff_lzw_decode_chunks: out must be a uint8 tensor of {n} x {slot_bytes} bytes at a multiple of "
+                              f"{TIFF_SLOT_ALIGN}")
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=src.device)
+    elif status.dtype != torch.int32 or status.dim() != 1 or status.numel() != n:
+        raise L.FlairHipError(f"tiff_lzw_decode_chunks: status must be a flat int32 tensor of {n} entries")
+    L.check(L.lib().flair_tiff_lzw_decode_chunks(ptrs[0], src.numel(), *ptrs[1:], n, L.ptr(out), slot_bytes, L.ptr(status), L.stream()),
+            "tiff_lzw_decode_chunks")
+    return out.view(n, slot_bytes), status
+
+
+def tiff_chunks_to_planes(scratch, chunks, status, planes, samples, predictor=1, max_rows=None):
+    """Scatters decoded chunks into the (bands, H, W) uint8 device raster ``planes``, in place: ``scratch`` (n, slot_bytes) uint8 as
+    ``tiff_lzw_decode_chunks`` returns it, ``chunks`` (n, 5) int32 rows {x0, y0, width, rows, band0} on the device, ``status`` int32 per
+    chunk (chunks whose status is not 0 are skipped).  ``samples`` bytes per pixel of a slot: 1 or bands; ``predictor`` 1 or 2 (TIFF
+    horizontal differencing, undone per chunk row and sample).  ``max_rows``: the largest ``rows`` of the table when the caller knows
+    it; otherwise it is read from the device, which waits for it.  Returns ``planes``."""
+    if scratch.dtype != torch.uint8 or scratch.dim() != 2:
+        raise L.FlairHipError("tiff_chunks_to_planes needs the (n, slot_bytes) uint8 scratch of tiff_lzw_decode_chunks")
+    n, slot_bytes = scratch.shape
+    if chunks.dtype != torch.int32 or tuple(chunks.shape) != (n, 5) or status.dtype != torch.int32 or tuple(status.shape) != (n,):
+        raise L.FlairHipError(f"tiff_chunks_to_planes: chunks must be ({n}, 5) int32 and status ({n},) int32")
+    if planes.dtype != torch.uint8 or planes.dim() != 3:
+        raise L.FlairHipError("tiff_chunks_to_planes writes a (bands, H, W) uint8 raster")
+    bands, H, W = planes.shape
+    samples, predictor = int(samples), int(predictor)
+    if samples not in (1, bands):
+        raise ValueError(f"samples must be 1 or the raster's {bands} bands, got {samples}")
+    if predictor not in (1, 2):
+        raise ValueError(f"predictor must be 1 or 2, got {predictor}")
+    ptrs = [L.ptr(scratch), L.ptr(chunks), L.ptr(status), L.ptr(planes)]
+    if max_rows is None:
+        max_rows = int(chunks[:, 3].max())
+    L.check(L.lib().flair_tiff_chunks_to_planes(ptrs[0], slot_bytes, ptrs[1], ptrs[2], n, max(1, int(max_rows)), samples, predictor,
+                                                ptrs[3], bands, H, W, L.stream()), "tiff_chunks_to_planes")
+    return planes
+
+
 def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
 

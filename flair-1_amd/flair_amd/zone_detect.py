@@ -462,6 +462,23 @@ class ZoneDetector:
         self.write(out, path, source=source, **kw)
         return out
 
+    def read(self, path, device=None) -> torch.Tensor:
+        """The (bands, H, W) uint8 raster of the file ``input_img_path`` names, decoded on the device (raster_reader.read_raster); a
+        file with fewer bands than ``channels`` asks for (band numbers from 1, as rasterio counts them) is refused here."""
+        from . import raster_reader
+        raster = raster_reader.read_raster(path, torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+        if raster.shape[0] < max(self.channels):
+            raise ValueError(f"{os.fspath(path)!r} has {raster.shape[0]} bands, config['channels'] asks for band {max(self.channels)}")
+        return raster
+
+    def run_files(self, src, dst, truth=None, **kw) -> torch.Tensor:
+        """From a file to a file: ``read(src)``, ``run``, ``write(dst, source=src)`` (``kw`` goes to ``write``).  ``truth``: a label raster
+        file of the same extent, whose first band is ``run``'s ``truth_u8``.  Returns the raster ``run`` returned."""
+        from . import raster_reader
+        raster = self.read(src)
+        truth_u8 = None if truth is None else raster_reader.read_raster(truth, raster.device)[0]
+        return self.run_to_file(raster, dst, truth_u8, source=src, **kw)
+
 
 def compare(model, config: dict, raster_u8: torch.Tensor) -> dict:
     """The comparison loop of main.py:275-372 without raster files or metrics: one ZoneDetector per combination of

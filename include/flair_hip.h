@@ -334,6 +334,38 @@ int flair_tiff_lzw_decode_max_strip(void);
 int flair_tiff_lzw_decode(const uint8_t* src, long src_bytes, const int64_t* strip_src_off, const int32_t* strip_src_len,
                           const int64_t* strip_dst_off, const int32_t* strip_dst_len, const int32_t* strip_mode, long nstrips, uint8_t* dst,
                           long dst_bytes, int32_t* status, void* stream);
+/* The read path of zone_detect's input raster (csrc/tiff_read.hip, flair_amd/raster_reader.py): the chunks of a TIFF, its tiles or
+ * strips, of any size.  Chunk i, the bytes [src_off[i], + src_len[i]) of src, is decoded as dst_len[i] bytes into the slot
+ * scratch + i * slot_bytes; mode[i] 0 = stored, 1 = LZW.  All pointers are device pointers, the four tables and status have nchunks
+ * entries, scratch holds nchunks slots and does not overlap src.  One wave per chunk, one launch, no device sync.
+ * The stream rules, the status codes 0 - 4 and the clipping of the last string are word for word those of flair_tiff_lzw_decode
+ * above.  status 5, a range or cap error: an offset or length below 0, src_off + src_len > src_bytes, dst_len < 1,
+ * dst_len > slot_bytes, a mode other than 0 / 1, an LZW dst_len above flair_tiff_lzw_decode_chunks_cap() (16 MiB; stored chunks have
+ * no cap): nothing of that slot is written.  At status 1 - 4 the bytes decoded before the error are written, at every status the
+ * bytes of a slot from dst_len on are left as they were.
+ * Whatever the input bytes are the kernel terminates (every round consumes at least 9 bits of the chunk), reads src only inside the
+ * chunk's own [src_off, src_off + src_len) and writes (and reads back) only [0, dst_len) of the chunk's own slot.
+ * flair_tiff_lzw_decode_chunks_window(): a code's source bytes less than this far behind the output position at which the code
+ *   begins come from the LDS ring of recent output, older ones are read back from the slot (tests place references on both sides).
+ * Returns -1 for a null pointer, nchunks < 1, src_bytes < 0 or slot_bytes < 1; -2 unless scratch is 128-byte aligned, slot_bytes a
+ * multiple of 128, src_off 8-byte and the int32 tables 4-byte aligned. */
+int flair_tiff_lzw_decode_chunks_cap(void);
+int flair_tiff_lzw_decode_chunks_window(void);
+int flair_tiff_lzw_decode_chunks(const uint8_t* src, long src_bytes, const int64_t* src_off, const int32_t* src_len, const int32_t* dst_len,
+                                 const int32_t* mode, long nchunks, uint8_t* scratch, long slot_bytes, int32_t* status, void* stream);
+/* The decoded slots into the raster planes (bands, H, W) uint8.  chunks (nchunks, 5) int32 on the device, row i = {x0, y0, width,
+ * rows, band0}: slot i holds rows x width pixels of `samples` bytes each, row-major, the samples of a pixel next to each other;
+ * sample k of the pixel at (r, x) is written to planes[band0 + k][y0 + r][x0 + x] if y0 + r < H and x0 + x < W and dropped otherwise
+ * (TIFF tiles are always full size: edge tiles are clipped on the right and at the bottom).  samples is 1 (PlanarConfiguration 2, or
+ * one band) or bands (PlanarConfiguration 1, band0 = 0).  predictor 1: the bytes as they are; 2 (TIFF horizontal differencing): per
+ * chunk row and per sample the running sum modulo 256 along the row, starting afresh at the chunk's left edge.
+ * A chunk whose status[i] is not 0 is skipped, and so is one with x0, y0 or band0 below 0, width or rows below 1,
+ * band0 + samples > bands or width * rows * samples > slot_bytes; nothing else of planes is written.  max_rows: the largest `rows`
+ * of the table, which the host knows; it sizes the launch only.
+ * Returns -1 for a null pointer, nchunks, slot_bytes, max_rows or an extent < 1, samples other than 1 / bands or a predictor other
+ * than 1 / 2; -2 unless chunks and status are 4-byte aligned.  No device sync. */
+int flair_tiff_chunks_to_planes(const uint8_t* scratch, long slot_bytes, const int32_t* chunks, const int32_t* status, long nchunks,
+                                int max_rows, int samples, int predictor, uint8_t* planes, int bands, int H, int W, void* stream);
 
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
