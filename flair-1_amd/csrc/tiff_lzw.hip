@@ -14,7 +14,9 @@
 // strips above are its contiguous instance, the T x T TIFF tiles of a (bands, H, W) raster resident on the device (zone_detect's output
 // file, flair_amd/raster_writer.py) the other, u8 or fp32 samples, band or pixel interleave; tiff_pack_streams_kernel then moves the
 // streams out of their worst-case slots back to back, so that only compressed bytes cross PCIe.
-// The decoder of the same streams (and of PIL's and libtiff's), the read path of metrics(), follows the encoder below.
+// The decoder of the same streams (and of PIL's and libtiff's), the read path of metrics(), follows the encoder below; its loop is
+// lzw_decode.h's, shared with the chunk decoder of tiff_read.hip.
+#include "lzw_decode.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -24,8 +26,7 @@ namespace {
 
 constexpr int LZW_TABLE = 8192;            // entries; a power of two
 constexpr unsigned LZW_EMPTY = 0xffffffffu;   // key 0xfffff = (prefix 4095, byte 255): never a key, prefixes stay below 4094
-constexpr int LZW_CLEAR = 256, LZW_EOI = 257, LZW_FIRST = 258, LZW_LIMIT = 4094;
-constexpr int LZW_CHUNK = 256;             // input bytes per fetch: 64 lanes x 4
+constexpr int LZW_LIMIT = 4094;            // the encoder's reset; the stream constants are lzw_decode.h's
 
 __device__ __forceinline__ void lzw_clear_table(unsigned* tab, int lane) {
   uint4* t4 = reinterpret_cast<uint4*>(tab);
@@ -265,34 +266,28 @@ __global__ __launch_bounds__(256) void tiff_pack_streams_kernel(const unsigned c
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the decoder
-// The read path of metrics(): one wave per strip again.  Every string a code can name already lies contiguously in the decoded
-// output: entry k, added after the code that follows `old`, is string(old) plus the first byte of what came next, i.e. the bytes at
-// [old_pos, old_pos + old_len + 1) of the strip.  So the table holds (position, length) packed in one u32 (16 + 16 bits: positions
-// stay below the 65 536-byte cap, lengths below 3840), 3838 entries (literals need none), and a code is emitted as a copy from
-// earlier output, 64 bytes per step across the lanes.  The serial chain is per code, not per byte.  The strip is decoded into
-// LDS and flushed to `dst` once, so the kernel never reads its own global stores back; the stage starts at the 16-byte phase of
-// the strip's global address, which makes the flush aligned 16-byte words on both sides.
-// Bit parsing is wave-uniform: the input is held 256 bytes per register of the wave (4 bytes per lane, big-endian words), one
-// chunk ahead, and a code is cut out of two words read with v_readlane.  Lane 0 alone writes the table.
+// The read path of metrics(): one wave per strip again, the loop is lzw_decode_stream (lzw_decode.h).  The strip is decoded into an
+// LDS stage and flushed to `dst` once, so the kernel never reads its own global stores back; the stage starts at the 16-byte phase of
+// the strip's global address, which makes the flush aligned 16-byte words on both sides.  A table entry is (position, length)
+// packed in one u32 (16 + 16 bits: positions stay below the 65 536-byte cap, lengths below 3840).
 constexpr int LZW_DEC_SMALL = 16384, LZW_DEC_CAP = 65536;   // decoded bytes of an LZW strip per size class
-constexpr int LZW_DEC_ENTRIES = 4096 - LZW_FIRST;
 constexpr int lzw_dec_lds(int cap) { return cap + 16 + LZW_DEC_ENTRIES * 4; }   // stage (+ 16: the alignment phase), table
 
-// 4 bytes of the strip at `off` (any alignment, 64-bit offsets) as one big-endian word; offsets past the strip's end are clamped to
-// its last byte (n >= 1)
-__device__ __forceinline__ unsigned lzw_fetch_be(const unsigned char* __restrict__ src, long off, long n) {
-  unsigned w = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) w = (w << 8) | src[min(off + e, n - 1)];
-  return w;
-}
-
-// LDS stores of some lanes are read by other lanes afterwards: complete them, and keep the compiler from moving accesses across
-__device__ __forceinline__ void lzw_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+struct LzwStageSink {
+  unsigned char* stage;      // LDS; stage[i] is byte i of the strip
+  unsigned* tab;             // LDS; entry k
+  int lane;
+  __device__ __forceinline__ void literal(int op, int c) { if (lane == 0) stage[op] = (unsigned char)c; }
+  __device__ __forceinline__ void copy(int op, int from, int n, int wrap) {
+    for (int j = lane; j < n; j += 64) stage[op + j] = stage[from + (j < wrap ? j : 0)];
+  }
+  __device__ __forceinline__ void entry(int k, int& pos, int& len) const {
+    const unsigned e = __builtin_amdgcn_readfirstlane(tab[k]);
+    pos = (int)(e >> 16); len = (int)(e & 0xffff);
+  }
+  __device__ __forceinline__ void set_entry(int k, int pos, int len) { tab[k] = ((unsigned)pos << 16) | (unsigned)len; }
+  __device__ __forceinline__ void after_code(int) {}
+};
 
 // Strips of one size class: LZW strips with lo < dst_len <= hi.  The launch with `first` set also serves the stored strips and
 // gives the out-of-range ones their status, so that every strip is served by exactly one launch.
@@ -323,63 +318,10 @@ __global__ __launch_bounds__(64) void tiff_lzw_decode_kernel(const unsigned char
 
   const int phase = (int)((uintptr_t)g & 15);
   unsigned char* stage = lzw_dec_smem + phase;                                  // stage[i] is g[i]
-  unsigned* tab = reinterpret_cast<unsigned*>(lzw_dec_smem + hi + 16);          // entry of code k at tab[k - LZW_FIRST]
+  LzwStageSink sink{stage, reinterpret_cast<unsigned*>(lzw_dec_smem + hi + 16), lane};
 
-  const long nbits = (long)sn * 8;
-  unsigned cur = lzw_fetch_be(s, 4 * lane, sn), ahead = lzw_fetch_be(s, LZW_CHUNK + 4 * lane, sn);
-  long base = 0;                       // the strip offset of `cur`, bytes
-  int b = 0;                           // the next code's bit offset inside `cur`, < 2048
-  int nxt = LZW_FIRST, width = 9, op = 0, st;
-  int old_pos = 0, old_len = 0;        // where the previous code's string was emitted; length 0: no previous code
-  // every round consumes `width` >= 9 bits of the strip or ends: at most src_len * 8 / 9 rounds whatever the bytes are
-  for (;;) {
-    if (op >= dn) { st = 0; break; }
-    if (base * 8 + b + width > nbits) { st = 1; break; }
-    const int wi = b >> 5;
-    const unsigned w0 = __builtin_amdgcn_readlane(cur, wi);
-    const unsigned w1 = wi < 63 ? __builtin_amdgcn_readlane(cur, (wi + 1) & 63) : __builtin_amdgcn_readlane(ahead, 0);
-    const int code = (int)(((((unsigned long long)w0 << 32) | w1) >> (64 - (b & 31) - width)) & ((1u << width) - 1));
-    b += width;
-    if (b >= 8 * LZW_CHUNK) {
-      b -= 8 * LZW_CHUNK;
-      base += LZW_CHUNK;
-      cur = ahead;
-      ahead = lzw_fetch_be(s, base + LZW_CHUNK + 4 * lane, sn);
-    }
-    if (code == LZW_CLEAR) { nxt = LZW_FIRST; width = 9; old_len = 0; continue; }
-    if (code == LZW_EOI) { st = 2; break; }
-    if (old_len == 0) {
-      if (code >= 256) { st = 3; break; }
-      if (lane == 0) stage[op] = (unsigned char)code;
-      lzw_lds_order();
-      old_pos = op; old_len = 1; ++op;
-      continue;
-    }
-    // the string of `code`: [from, from + len) of the stage, except that at index `wrap` it starts over (code == nxt: string(old)
-    // and its own first byte again, which is where this copy's first byte lands; the source stays below `op` all the same)
-    int from = 0, len = 1, wrap = 0x7fffffff;
-    if (code >= 256) {
-      if (code < nxt) {
-        const unsigned e = __builtin_amdgcn_readfirstlane(tab[code - LZW_FIRST]);
-        from = (int)(e >> 16); len = (int)(e & 0xffff);
-      } else if (code == nxt && nxt < 4096) {
-        from = old_pos; len = old_len + 1; wrap = old_len;
-      } else { st = 4; break; }
-    }
-    const int n = min(len, dn - op);
-    if (code < 256) {
-      if (lane == 0) stage[op] = (unsigned char)code;
-    } else {
-      for (int j = lane; j < n; j += 64) stage[op + j] = stage[from + (j < wrap ? j : 0)];
-    }
-    if (nxt < 4096) {
-      if (lane == 0) tab[nxt - LZW_FIRST] = ((unsigned)old_pos << 16) | (unsigned)(old_len + 1);
-      ++nxt;
-      if (nxt == 511 || nxt == 1023 || nxt == 2047) ++width;
-    }
-    lzw_lds_order();
-    old_pos = op; old_len = n; op += n;
-  }
+  int op;
+  const int st = lzw_decode_stream(s, sn, dn, lane, sink, op);
 
   // the flush: what was produced (all of the strip at status 0), bytes up to the first 16-byte boundary of g, words, bytes
   const int head = min(op, (16 - phase) & 15);

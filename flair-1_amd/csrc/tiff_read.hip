@@ -1,13 +1,10 @@
 // The read path of zone_detect's input raster (flair_amd/raster_reader.py): the chunks of a TIFF (tiles or strips, stored or LZW) are
 // decoded into slots of a scratch buffer, one wave per chunk, and a second kernel scatters the slots into the (bands, H, W) band-plane
-// raster, undoing the horizontal predictor on the way.  The stream rules and the status codes are those of tiff_lzw_decode_kernel
-// (csrc/tiff_lzw.hip); what differs is the size: a 512 x 512 tile of 5 interleaved bands is 1.3 MB, so the decoded output lives in
-// the slot, in global memory, and not in LDS.
-//
-// The decoder keeps the parent's idea: every string a code can name already lies contiguously in the decoded output, so the table
-// holds (position, length) and a code is emitted as a copy from earlier output, 64 bytes per step across the lanes; the serial chain
-// is per code, not per byte.  Positions are 32 bits now (RD_CAP = 16 MiB), lengths stay below RD_MAXSTR: an entry is one byte longer
-// than the string before it, so the longest of the 3838 entries between two clears has 3839 bytes.
+// raster, undoing the horizontal predictor on the way.  The stream rules, the loop and the status codes are lzw_decode_stream's
+// (csrc/lzw_decode.h), shared with tiff_lzw_decode_kernel (csrc/tiff_lzw.hip); what differs is the size: a 512 x 512 tile of 5
+// interleaved bands is 1.3 MB, so the decoded output lives in the slot, in global memory, and not in LDS.  Positions are 32 bits
+// (RD_CAP = 16 MiB), lengths stay below RD_MAXSTR: an entry is one byte longer than the string before it, so the longest of the 3838
+// entries between two clears has 3839 bytes.
 //
 // Where the copy reads from.  The most recent output lies in an LDS ring of RD_RING bytes, position p at ring[p % RD_RING].  After
 // every code the completed 128-byte blocks of the output (the slot is 128-byte aligned, so these are whole cache lines) are flushed
@@ -31,9 +28,7 @@
 //      read-back of a chunk is always behind an acquire.
 //  (3) the read-back loads are per-lane byte loads through a pointer that is neither const nor __restrict__: vector loads, never
 //      the scalar cache.
-//
-// Bit parsing is the parent's: the input is held 256 bytes per register of the wave, one chunk ahead, a code is cut out of two words
-// read with v_readlane, every round consumes at least 9 bits of the chunk or ends.  Lane 0 alone writes the table.
+#include "lzw_decode.h"
 #include "ops.h"
 #include "prof.h"
 
@@ -41,30 +36,12 @@ namespace flair {
 
 namespace {
 
-constexpr int RD_CLEAR = 256, RD_EOI = 257, RD_FIRST = 258;
-constexpr int RD_FETCH = 256;                        // input bytes per fetch: 64 lanes x 4
-constexpr int RD_ENTRIES = 4096 - RD_FIRST;
 constexpr int RD_RING = 16384;                       // a power of two
-constexpr int RD_MAXSTR = 4096;                      // above the longest string, RD_ENTRIES + 1
+constexpr int RD_MAXSTR = 4096;                      // above the longest string, LZW_DEC_ENTRIES + 1
 constexpr int RD_WINDOW = RD_RING - RD_MAXSTR;
 constexpr int RD_BLOCK = 128;                        // the flush unit: one cache line
 constexpr int RD_CAP = 1 << 24;                      // decoded bytes of an LZW chunk
-static_assert((RD_RING & (RD_RING - 1)) == 0 && RD_ENTRIES + 1 < RD_MAXSTR && RD_WINDOW > RD_BLOCK, "ring geometry");
-
-// 4 bytes of the chunk at `off` (any alignment) as one big-endian word; offsets past the chunk's end are clamped to its last byte
-__device__ __forceinline__ unsigned rd_fetch_be(const unsigned char* __restrict__ src, long off, long n) {
-  unsigned w = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) w = (w << 8) | src[min(off + e, n - 1)];
-  return w;
-}
-
-// LDS stores of some lanes are read by other lanes afterwards: complete them, and keep the compiler from moving accesses across
-__device__ __forceinline__ void rd_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+static_assert((RD_RING & (RD_RING - 1)) == 0 && LZW_DEC_ENTRIES + 1 < RD_MAXSTR && RD_WINDOW > RD_BLOCK, "ring geometry");
 
 // (2) of the argument above; every lane of the wave executes it
 __device__ __forceinline__ void rd_publish_flushed() {
@@ -75,14 +52,48 @@ __device__ __forceinline__ void rd_publish_flushed() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+struct LzwRingSink {
+  static constexpr int M = RD_RING - 1;
+  unsigned char* ring;       // LDS
+  unsigned* tpos;            // LDS; entry k: its string is [tpos, tpos + tlen) of the output
+  unsigned short* tlen;
+  unsigned char* g;          // the slot, 128-byte aligned; read back below: no __restrict__
+  int lane;
+  int flushed, fenced;       // multiples of RD_BLOCK: [0, flushed) is in the slot, [0, fenced) may be read back
+  __device__ __forceinline__ void literal(int op, int c) { if (lane == 0) ring[op & M] = (unsigned char)c; }
+  __device__ __forceinline__ void copy(int op, int from, int n, int wrap) {
+    const int lo = op - RD_WINDOW;              // sources below it come from the slot; lo <= flushed
+    if (from < lo && min(from + min(n, wrap), lo) > fenced) {
+      rd_publish_flushed();
+      fenced = flushed;
+    }
+    for (int j = lane; j < n; j += 64) {
+      const int sp = from + (j < wrap ? j : 0);
+      ring[(op + j) & M] = sp >= lo ? ring[sp & M] : g[sp];
+    }
+  }
+  __device__ __forceinline__ void entry(int k, int& pos, int& len) const {
+    pos = (int)__builtin_amdgcn_readfirstlane(tpos[k]);
+    len = (int)__builtin_amdgcn_readfirstlane((unsigned)tlen[k]);
+  }
+  __device__ __forceinline__ void set_entry(int k, int pos, int len) { tpos[k] = (unsigned)pos; tlen[k] = (unsigned short)len; }
+  __device__ __forceinline__ void after_code(int op) {
+    const int upto = op & ~(RD_BLOCK - 1);
+    if (upto > flushed) {                        // whole blocks: at most RD_MAXSTR bytes, all of them still in the ring
+      for (int i = flushed + 16 * lane; i < upto; i += 1024)
+        *reinterpret_cast<uint4*>(g + i) = *reinterpret_cast<const uint4*>(ring + (i & M));
+      flushed = upto;
+    }
+  }
+};
+
 __global__ __launch_bounds__(64) void tiff_lzw_decode_chunks_kernel(const unsigned char* __restrict__ src, long src_bytes,
                                                                     const long long* __restrict__ src_off, const int* __restrict__ src_len,
                                                                     const int* __restrict__ dst_len, const int* __restrict__ mode,
                                                                     unsigned char* scratch, long slot_bytes, int* __restrict__ status) {
   __shared__ __attribute__((aligned(16))) unsigned char ring[RD_RING];
-  __shared__ unsigned tpos[RD_ENTRIES];          // entry of code k: its string is [tpos, tpos + tlen) of the output
-  __shared__ unsigned short tlen[RD_ENTRIES];
-  constexpr int M = RD_RING - 1;
+  __shared__ unsigned tpos[LZW_DEC_ENTRIES];
+  __shared__ unsigned short tlen[LZW_DEC_ENTRIES];
   const int lane = threadIdx.x;
   const long chunk = blockIdx.x;
   const long so = src_off[chunk];
@@ -90,7 +101,7 @@ __global__ __launch_bounds__(64) void tiff_lzw_decode_chunks_kernel(const unsign
   const bool ok = so >= 0 && sn >= 0 && dn >= 1 && so <= src_bytes - sn && dn <= slot_bytes && (md == 0 || (md == 1 && dn <= RD_CAP));
   if (!ok) { if (lane == 0) status[chunk] = 5; return; }
   const unsigned char* __restrict__ s = src + so;
-  unsigned char* g = scratch + chunk * slot_bytes;   // 128-byte aligned; read back below: no __restrict__
+  unsigned char* g = scratch + chunk * slot_bytes;
   if (md == 0) {
     // stored: the slot is aligned, the source is not; 4 bytes per lane, put together as one word
     const int n = min(sn, dn), n4 = n & ~3;
@@ -102,77 +113,11 @@ __global__ __launch_bounds__(64) void tiff_lzw_decode_chunks_kernel(const unsign
   }
   if (sn == 0) { if (lane == 0) status[chunk] = 1; return; }
 
-  const long nbits = (long)sn * 8;
-  unsigned cur = rd_fetch_be(s, 4 * lane, sn), ahead = rd_fetch_be(s, RD_FETCH + 4 * lane, sn);
-  long base = 0;                       // the chunk offset of `cur`, bytes
-  int b = 0;                           // the next code's bit offset inside `cur`, < 2048
-  int nxt = RD_FIRST, width = 9, op = 0, st;
-  int flushed = 0, fenced = 0;         // multiples of RD_BLOCK: [0, flushed) is in the slot, [0, fenced) may be read back
-  int old_pos = 0, old_len = 0;        // where the previous code's string was emitted; length 0: no previous code
-  // every round consumes `width` >= 9 bits of the chunk or ends: at most src_len * 8 / 9 rounds whatever the bytes are
-  for (;;) {
-    if (op >= dn) { st = 0; break; }
-    if (base * 8 + b + width > nbits) { st = 1; break; }
-    const int wi = b >> 5;
-    const unsigned w0 = __builtin_amdgcn_readlane(cur, wi);
-    const unsigned w1 = wi < 63 ? __builtin_amdgcn_readlane(cur, (wi + 1) & 63) : __builtin_amdgcn_readlane(ahead, 0);
-    const int code = (int)(((((unsigned long long)w0 << 32) | w1) >> (64 - (b & 31) - width)) & ((1u << width) - 1));
-    b += width;
-    if (b >= 8 * RD_FETCH) {
-      b -= 8 * RD_FETCH;
-      base += RD_FETCH;
-      cur = ahead;
-      ahead = rd_fetch_be(s, base + RD_FETCH + 4 * lane, sn);
-    }
-    if (code == RD_CLEAR) { nxt = RD_FIRST; width = 9; old_len = 0; continue; }
-    if (code == RD_EOI) { st = 2; break; }
-    int n = 1;
-    if (old_len == 0) {
-      if (code >= 256) { st = 3; break; }
-      if (lane == 0) ring[op & M] = (unsigned char)code;
-    } else {
-      // the string of `code`: [from, from + len) of the output, except that at index `wrap` it starts over (code == nxt: string(old)
-      // and its own first byte again, which is where this copy's first byte lands; the source stays below `op` all the same)
-      int from = 0, len = 1, wrap = 0x7fffffff;
-      if (code >= 256) {
-        if (code < nxt) {
-          from = (int)__builtin_amdgcn_readfirstlane(tpos[code - RD_FIRST]);
-          len = (int)__builtin_amdgcn_readfirstlane((unsigned)tlen[code - RD_FIRST]);
-        } else if (code == nxt && nxt < 4096) {
-          from = old_pos; len = old_len + 1; wrap = old_len;
-        } else { st = 4; break; }
-      }
-      n = min(len, dn - op);
-      if (code < 256) {
-        if (lane == 0) ring[op & M] = (unsigned char)code;
-      } else {
-        const int lo = op - RD_WINDOW;            // sources below it come from the slot; lo <= flushed
-        if (from < lo && min(from + min(n, wrap), lo) > fenced) {
-          rd_publish_flushed();
-          fenced = flushed;
-        }
-        for (int j = lane; j < n; j += 64) {
-          const int sp = from + (j < wrap ? j : 0);
-          ring[(op + j) & M] = sp >= lo ? ring[sp & M] : g[sp];
-        }
-      }
-      if (nxt < 4096) {
-        if (lane == 0) { tpos[nxt - RD_FIRST] = (unsigned)old_pos; tlen[nxt - RD_FIRST] = (unsigned short)(old_len + 1); }
-        ++nxt;
-        if (nxt == 511 || nxt == 1023 || nxt == 2047) ++width;
-      }
-    }
-    rd_lds_order();
-    old_pos = op; old_len = n; op += n;
-    const int upto = op & ~(RD_BLOCK - 1);
-    if (upto > flushed) {                        // whole blocks: at most RD_MAXSTR bytes, all of them still in the ring
-      for (int i = flushed + 16 * lane; i < upto; i += 1024)
-        *reinterpret_cast<uint4*>(g + i) = *reinterpret_cast<const uint4*>(ring + (i & M));
-      flushed = upto;
-    }
-  }
+  LzwRingSink sink{ring, tpos, tlen, g, lane, 0, 0};
+  int op;
+  const int st = lzw_decode_stream(s, sn, dn, lane, sink, op);
   // what was produced past the last whole block (all of the chunk's rest at status 0): fewer than RD_BLOCK bytes
-  for (int i = flushed + lane; i < op; i += 64) g[i] = ring[i & M];
+  for (int i = sink.flushed + lane; i < op; i += 64) g[i] = ring[i & LzwRingSink::M];
   if (lane == 0) status[chunk] = st;
 }
 

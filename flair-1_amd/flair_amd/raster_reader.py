@@ -1,36 +1,29 @@
 """The file zone_detect starts from (reference src/zone_detect/main.py, ``input_img_path``): a multi-band 8-bit orthophoto TIFF, read
-into the (bands, H, W) uint8 device tensor ``ZoneDetector.run`` takes.  The host parses the first IFD (``raster_layout``) and reads
-the compressed chunks, the tiles or strips of the file, group by group into pinned memory; the device decodes them
-(``ops.tiff_lzw_decode_chunks``, csrc/tiff_read.hip: stored or LZW, one wave per chunk, any chunk size up to ``CHUNK_CAP``) and scatters
-them into the band planes with the horizontal predictor undone (``ops.tiff_chunks_to_planes``).  Only compressed bytes cross PCIe.
-This is the family of files ``raster_writer.write_raster`` and GDAL (``COMPRESS=LZW``, ``PREDICTOR=2``, ``INTERLEAVE=BAND`` / ``PIXEL``,
-tiled or striped) write; DESIGN §10 has the layout.  There is no fallback reader: a file outside the family is refused by name
-(``UnsupportedRaster``), because nothing else in the package reads a 5-band file either.
+into the (bands, H, W) uint8 device tensor ``ZoneDetector.run`` takes.  The host parses the first IFD (``raster_layout``, a policy
+over ``tiff_ifd.Directory``) and reads the compressed chunks, the tiles or strips of the file, group by group into pinned memory; the
+device decodes them (``ops.tiff_lzw_decode_chunks``, csrc/tiff_read.hip: stored or LZW, one wave per chunk, any chunk size up to
+``CHUNK_CAP``) and scatters them into the band planes with the horizontal predictor undone (``ops.tiff_chunks_to_planes``).  Only
+compressed bytes cross PCIe.  This is the family of files ``raster_writer.write_raster`` and GDAL (``COMPRESS=LZW``, ``PREDICTOR=2``,
+``INTERLEAVE=BAND`` / ``PIXEL``, tiled or striped) write; DESIGN §10 has the layout.  There is no fallback reader: a file outside the
+family is refused by name (``UnsupportedRaster``), because nothing else in the package reads a 5-band file either.
 """
 from __future__ import annotations
 
 import mmap
 import os
-import struct
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from .raster_writer import GROUP_BYTES, stream_groups
+from .tiff_ifd import BYTE, INT_FORMAT, TAG, TAG_NAMES, TYPE_SIZE, Directory, DirectoryError, old_style_lzw
+from .tiff_staging import GROUP_BYTES, PinnedPair, stream_groups
 
 CHUNK_CAP = 1 << 24      # decoded bytes of one LZW chunk the kernel takes (flair_tiff_lzw_decode_chunks_cap)
 CHUNK_WINDOW = 12288     # the decoder's LDS window of recent output (flair_tiff_lzw_decode_chunks_window): older sources are read back
 FLUSH_BLOCK = 128        # ... from the slot, which is written in whole blocks of this size; slots are multiples of it
 MERGE_GAP = 1 << 16      # chunks of a group that lie this close in the file are read with one read()
 
-_SHORT, _LONG, _LONG8 = 3, 4, 16
-_INT_TYPES = {1: "u1", _SHORT: "u2", _LONG: "u4", _LONG8: "u8"}
-_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4, 16: 8, 17: 8, 18: 8}
-TAG_NAMES = {254: "NewSubfileType", 256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression",
-             266: "FillOrder", 273: "StripOffsets", 274: "Orientation", 277: "SamplesPerPixel", 278: "RowsPerStrip",
-             279: "StripByteCounts", 284: "PlanarConfiguration", 317: "Predictor", 322: "TileWidth", 323: "TileLength",
-             324: "TileOffsets", 325: "TileByteCounts", 339: "SampleFormat"}
 STATUS_TEXT = {1: "the compressed bytes ran out", 2: "EOI came before the chunk was complete", 3: "a table code first after a clear",
                4: "a code the table does not hold", 5: "a range or cap error"}
 
@@ -45,6 +38,11 @@ class RasterDecodeError(RuntimeError):
     def __init__(self, message, chunk, status):
         super().__init__(message)
         self.chunk, self.status = chunk, status
+
+
+_NO_DIRECTORY = {"order": "not a TIFF: the file does not begin with II or MM", "magic": "not a TIFF: magic number {magic}",
+                 "ifd": "the IFD at {ifd} lies outside the file of {n} bytes",
+                 "entries": "the IFD at {ifd} with {count} entries lies outside the file of {n} bytes"}   # by DirectoryError.what
 
 
 def _name(tag):
@@ -110,44 +108,24 @@ def raster_layout(data) -> RasterLayout:
     FillOrder 1, Orientation 1, PlanarConfiguration 1 or 2; tiles whose sides are multiples of 16, or strips of any RowsPerStrip;
     offsets and counts as SHORT, LONG or LONG8, in exactly the expected number, all inside the file."""
     n = len(data)
-    order = bytes(data[:2])
-    if n < 8 or order not in (b"II", b"MM"):
-        raise UnsupportedRaster("not a TIFF: the file does not begin with II or MM")
-    e = "<" if order == b"II" else ">"
-    (magic,) = struct.unpack_from(e + "H", data, 2)
-    if magic == 42:
-        big, (ifd,) = False, struct.unpack_from(e + "I", data, 4)
-        cnt_fmt, entry_fmt, entry_size, inline, off_fmt = "H", "HHI", 12, 4, "I"
-    elif magic == 43 and n >= 16 and struct.unpack_from(e + "HH", data, 4) == (8, 0):
-        big, (ifd,) = True, struct.unpack_from(e + "Q", data, 8)
-        cnt_fmt, entry_fmt, entry_size, inline, off_fmt = "Q", "HHQ", 20, 8, "Q"
-    else:
-        raise UnsupportedRaster(f"not a TIFF: magic number {magic}")
-    head = struct.calcsize(cnt_fmt)
-    if ifd < 8 or ifd + head > n:
-        raise UnsupportedRaster(f"the IFD at {ifd} lies outside the file of {n} bytes")
-    (count,) = struct.unpack_from(e + cnt_fmt, data, ifd)
-    if ifd + head + entry_size * count + inline > n:
-        raise UnsupportedRaster(f"the IFD at {ifd} with {count} entries lies outside the file of {n} bytes")
-    tags = {}
-    for i in range(count):
-        at = ifd + head + entry_size * i
-        tag, typ, cnt = struct.unpack_from(e + entry_fmt, data, at)
-        tags[tag] = (typ, cnt, at + entry_size - inline)
+    try:
+        d = Directory(data)
+        if d.end + d.inline > n:   # the offset of the next IFD belongs to this one
+            raise DirectoryError("entries", ifd=d.ifd, count=d.count)
+    except DirectoryError as err:
+        raise UnsupportedRaster(_NO_DIRECTORY[err.what].format(n=n, **vars(err))) from None
+    tags = d.entries
 
     def values(tag):
         """the entry's integers as an array, None when it is absent"""
-        if tag not in tags:
-            return None
-        typ, cnt, at = tags[tag]
-        if typ not in _INT_TYPES or cnt < 1:
-            raise UnsupportedRaster(f"{_name(tag)} has type {typ} and count {cnt}, not BYTE, SHORT, LONG or LONG8 values")
-        size = _TYPE_SIZE[typ] * cnt
-        if size > inline:
-            (at,) = struct.unpack_from(e + off_fmt, data, at)
-            if at + size > n:
-                raise UnsupportedRaster(f"the {cnt} values of {_name(tag)} at {at} lie outside the file of {n} bytes")
-        return np.frombuffer(data, dtype=e + _INT_TYPES[typ], count=cnt, offset=at).copy()   # no view of an mmap outlives the call
+        try:
+            v = d.ints(tag, INT_FORMAT)
+        except DirectoryError as err:
+            typ, cnt, _ = tags[tag]
+            if err.what == "type":
+                raise UnsupportedRaster(f"{_name(tag)} has type {typ} and count {cnt}, not BYTE, SHORT, LONG or LONG8 values") from None
+            raise UnsupportedRaster(f"the {cnt} values of {_name(tag)} at {err.at} lie outside the file of {n} bytes") from None
+        return None if v is None else np.array(v, dtype=f"u{TYPE_SIZE[tags[tag][0]]}")
 
     def one(tag, default):
         v = values(tag)
@@ -168,57 +146,57 @@ def raster_layout(data) -> RasterLayout:
         if len(v) != bands or (v != want).any():
             raise UnsupportedRaster(f"{_name(tag)} is {[int(x) for x in v[:8]]}, expected {want} for each of the {bands} samples")
 
-    W, H = one(256, None), one(257, None)
+    W, H = one(TAG.ImageWidth, None), one(TAG.ImageLength, None)
     if not 1 <= W < 1 << 31:
-        raise UnsupportedRaster(f"{_name(256)} is {W}")
+        raise UnsupportedRaster(f"{_name(TAG.ImageWidth)} is {W}")
     if not 1 <= H < 1 << 31:
-        raise UnsupportedRaster(f"{_name(257)} is {H}")
-    subfile = one(254, 0)
+        raise UnsupportedRaster(f"{_name(TAG.ImageLength)} is {H}")
+    subfile = one(TAG.NewSubfileType, 0)
     if subfile & 5:
-        raise UnsupportedRaster(f"{_name(254)} is {subfile}: the first IFD is a reduced-resolution image or a mask, not the raster")
-    bands = one(277, 1)
+        raise UnsupportedRaster(f"{_name(TAG.NewSubfileType)} is {subfile}: the first IFD is a reduced-resolution image or a mask, not the raster")
+    bands = one(TAG.SamplesPerPixel, 1)
     if bands < 1:
-        raise UnsupportedRaster(f"{_name(277)} is {bands}")
-    all_equal(258, 8, False, bands)
-    all_equal(339, 1, True, bands)
-    compression = one(259, 1)
+        raise UnsupportedRaster(f"{_name(TAG.SamplesPerPixel)} is {bands}")
+    all_equal(TAG.BitsPerSample, 8, False, bands)
+    all_equal(TAG.SampleFormat, 1, True, bands)
+    compression = one(TAG.Compression, 1)
     if compression not in (1, 5):
-        raise UnsupportedRaster(f"{_name(259)} is {compression}: only 1 (stored) and 5 (LZW) are read")
-    predictor = one(317, 1)
+        raise UnsupportedRaster(f"{_name(TAG.Compression)} is {compression}: only 1 (stored) and 5 (LZW) are read")
+    predictor = one(TAG.Predictor, 1)
     if predictor not in (1, 2) or (predictor == 2 and compression == 1):
-        raise UnsupportedRaster(f"{_name(317)} is {predictor} with Compression {compression}: 1, or 2 with LZW, are read")
-    for tag in (266, 274):
+        raise UnsupportedRaster(f"{_name(TAG.Predictor)} is {predictor} with Compression {compression}: 1, or 2 with LZW, are read")
+    for tag in (TAG.FillOrder, TAG.Orientation):
         v = one(tag, 1)
         if v != 1:
             raise UnsupportedRaster(f"{_name(tag)} is {v}, expected 1")
-    planar = one(284, 1)
+    planar = one(TAG.PlanarConfiguration, 1)
     if planar not in (1, 2):
-        raise UnsupportedRaster(f"{_name(284)} is {planar}, expected 1 or 2")
+        raise UnsupportedRaster(f"{_name(TAG.PlanarConfiguration)} is {planar}, expected 1 or 2")
     if bands == 1:
         planar = 1   # the two mean the same bytes
-    tiled = 322 in tags or 323 in tags
+    tiled = TAG.TileWidth in tags or TAG.TileLength in tags
     if tiled:
-        cw, ch = one(322, None), one(323, None)
-        for tag, v in ((322, cw), (323, ch)):
+        cw, ch = one(TAG.TileWidth, None), one(TAG.TileLength, None)
+        for tag, v in ((TAG.TileWidth, cw), (TAG.TileLength, ch)):
             if v < 16 or v % 16 or v >= 1 << 31:
                 raise UnsupportedRaster(f"{_name(tag)} is {v}, no positive multiple of 16")
-        off_tag, cnt_tag = 324, 325
+        off_tag, cnt_tag = TAG.TileOffsets, TAG.TileByteCounts
     else:
-        cw, ch = W, min(one(278, (1 << 32) - 1), H)
+        cw, ch = W, min(one(TAG.RowsPerStrip, (1 << 32) - 1), H)
         if ch < 1:
-            raise UnsupportedRaster(f"{_name(278)} is {ch}")
-        off_tag, cnt_tag = 273, 279
+            raise UnsupportedRaster(f"{_name(TAG.RowsPerStrip)} is {ch}")
+        off_tag, cnt_tag = TAG.StripOffsets, TAG.StripByteCounts
     samples = bands if planar == 1 else 1
     chunk_bytes = cw * ch * samples
     if chunk_bytes >= 1 << 31 or (compression == 5 and chunk_bytes > CHUNK_CAP):
-        raise UnsupportedRaster(f"{_name(323 if tiled else 278)} makes chunks of {cw} x {ch} x {samples} = {chunk_bytes} bytes, more "
-                                f"than the decoder's {CHUNK_CAP}")
+        raise UnsupportedRaster(f"{_name(TAG.TileLength if tiled else TAG.RowsPerStrip)} makes chunks of {cw} x {ch} x {samples} = "
+                                f"{chunk_bytes} bytes, more than the decoder's {CHUNK_CAP}")
     n_chunks = (1 if planar == 1 else bands) * -(-H // ch) * -(-W // cw)
     offsets, counts = values(off_tag), values(cnt_tag)
     for tag, v in ((off_tag, offsets), (cnt_tag, counts)):
         if v is None:
             raise UnsupportedRaster(f"{_name(tag)} is missing")
-        if tags[tag][0] == 1 or len(v) != n_chunks:
+        if tags[tag][0] == BYTE or len(v) != n_chunks:
             raise UnsupportedRaster(f"{_name(tag)} holds {len(v)} values of type {tags[tag][0]}, expected {n_chunks} SHORT, LONG or LONG8")
     offsets, counts = offsets.astype(np.int64), counts.astype(np.int64)
     if (offsets < 0).any() or (counts < 0).any() or (counts >= 1 << 31).any():
@@ -227,13 +205,10 @@ def raster_layout(data) -> RasterLayout:
     if len(outside):
         i = int(outside[0])
         raise UnsupportedRaster(f"{_name(off_tag)}: chunk {i} at [{int(offsets[i])}, + {int(counts[i])}) lies outside the file of {n} bytes")
-    if compression == 5:
-        # libtiff recognises the pre-6.0 LSB-first LZW streams by these two bytes and decodes them its own way
-        for i in np.flatnonzero(counts >= 2):
-            o = int(offsets[i])
-            if data[o] == 0 and data[o + 1] & 1:
-                raise UnsupportedRaster(f"{_name(259)} is 5, but chunk {int(i)} is an old-style (LSB-first) LZW stream")
-    return RasterLayout(H, W, bands, planar, compression, predictor, tiled, cw, ch, offsets, counts, big, e)
+    old = old_style_lzw(data, offsets.tolist(), counts.tolist()) if compression == 5 else None
+    if old is not None:
+        raise UnsupportedRaster(f"{_name(TAG.Compression)} is 5, but chunk {old} is an old-style (LSB-first) LZW stream")
+    return RasterLayout(H, W, bands, planar, compression, predictor, tiled, cw, ch, offsets, counts, d.bigtiff, d.order)
 
 
 def read_plan(layout: RasterLayout, group_bytes: int = GROUP_BYTES):
@@ -263,14 +238,7 @@ def read_plan(layout: RasterLayout, group_bytes: int = GROUP_BYTES):
     return groups, slot, src_off, reads
 
 
-_pinned = [None, None]   # the two staging buffers of read_raster, kept between calls
-
-
-def _pinned_bytes(slot, n):
-    if _pinned[slot] is None or _pinned[slot].numel() < n:
-        _pinned[slot] = None
-        _pinned[slot] = torch.empty(max(n, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-    return _pinned[slot]
+_staging = PinnedPair()   # read_raster's own, kept between calls
 
 
 def _read_runs(f, runs, staging):
@@ -316,7 +284,7 @@ def read_raster(path, device, group_bytes: int = GROUP_BYTES) -> torch.Tensor:
                     k = g & 1
                     if uploaded[k] is not None:
                         uploaded[k].synchronize()        # the pinned buffer's last copy has left it
-                    staging = _pinned_bytes(k, nbytes)
+                    staging = _staging.take(k, nbytes)
                     _read_runs(f, runs, staging)
                     if decoded[k] is not None:
                         copy_stream.wait_event(decoded[k])   # the device buffer's last decode has read it

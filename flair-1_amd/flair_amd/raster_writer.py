@@ -3,14 +3,15 @@ raster, BigTIFF by default, tiles of ``img_pixels_detection``, 2 bands (class, c
 ``n_classes`` bands for ``class_prob``.  The raster stays on the device: ``ops.tiff_lzw_encode_tiles`` (csrc/tiff_lzw.hip) makes one
 LZW stream per TIFF tile, ``ops.tiff_pack_streams`` packs the streams of a group back to back, and only those bytes cross PCIe,
 into one of two pinned buffers on a side stream, while the next group is encoded and a worker thread appends the previous one to
-the file.  The host frames (``tiled_tiff_header``, ``tiled_tiff_ifd``) and calls ``write()``; DESIGN §10 has the layout.
+the file.  The host frames (``tiled_tiff_header``, ``tiled_tiff_ifd`` over ``tiff_ifd.build_ifd``) and calls ``write()``; DESIGN §10.
 
-``read_geo_tags`` lifts the GeoTIFF tags of the source raster as raw bytes and ``tiled_tiff_ifd(geo_tags=...)`` puts them into the
-output, so the result overlays its input (what ``profile.copy()`` does in the reference's ``prepare_output``); nothing here interprets
-them, and rasterio is not involved.
+``read_geo_tags`` lifts the GeoTIFF tags of the source raster as raw bytes (``tiff_ifd.Directory.raw_le``) and
+``tiled_tiff_ifd(geo_tags=...)`` puts them into the output, so the result overlays its input (what ``profile.copy()`` does in the
+reference's ``prepare_output``); nothing here interprets them, and rasterio is not involved.
 """
 from __future__ import annotations
 
+import mmap
 import os
 import queue
 import struct
@@ -19,15 +20,13 @@ import threading
 import numpy as np
 import torch
 
+from .tiff_ifd import LONG, LONG8, SHORT, TAG, TYPE_SIZE, Directory, DirectoryError, build_ifd, entry
+from .tiff_staging import GROUP_BYTES, PinnedPair, stream_groups  # noqa: F401 - both names stay importable from here
+
 INTERLEAVE = ("band", "pixel")     # PlanarConfiguration 2 / 1, GDAL's INTERLEAVE=BAND / PIXEL
 GEO_TAGS = (33550, 33922, 34264, 34735, 34736, 34737, 42113)   # pixel scale, tiepoints, transformation, key directory, double and
 #                                                                 ASCII parameters, GDAL_NODATA
 DATA_START = 16                    # where the first stream lies: the BigTIFF header's size, the classic header's rounded up to 16
-GROUP_BYTES = 256 << 20
-
-_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8, 13: 4, 16: 8, 17: 8, 18: 8}
-_UNIT_SIZE = {**_TYPE_SIZE, 5: 4, 10: 4}   # what is byte-swapped as one unit: a RATIONAL is two LONGs
-_SHORT, _LONG, _LONG8 = 3, 4, 16
 
 
 def _check_layout(H, W, bands, tile, interleave):
@@ -61,116 +60,49 @@ def tiled_tiff_ifd(H: int, W: int, bands: int, tile: int, interleave: str, offse
         raise ValueError(f"{len(offsets)} offsets and {len(counts)} counts for {n} tiles")
     if ifd_offset < 8 or ifd_offset % 2:
         raise ValueError(f"an IFD cannot lie at {ifd_offset}")
-    wide = "Q" if bigtiff else "I"
     planar = 2 if interleave == "band" and bands > 1 else 1
+    if not bigtiff and max(o + c for o, c in zip(offsets, counts)) > 1 << 32:
+        raise ValueError("a classic TIFF holds offsets below 2^32 only: use bigtiff=True")
+    wide = LONG8 if bigtiff else LONG
     # what GDAL makes of 8-bit bands, and what libtiff-based readers need to see every band: three are RGB, of any other number
     # the first is grey and the others are extra samples of unspecified meaning
     rgb = bands == 3
-    entries = [(256, _LONG, 1, struct.pack("<I", W)), (257, _LONG, 1, struct.pack("<I", H)),
-               (258, _SHORT, bands, struct.pack(f"<{bands}H", *[8] * bands)), (259, _SHORT, 1, struct.pack("<H", 5)),
-               (262, _SHORT, 1, struct.pack("<H", 2 if rgb else 1)), (277, _SHORT, 1, struct.pack("<H", bands)),
-               (284, _SHORT, 1, struct.pack("<H", planar)),
-               (322, _LONG, 1, struct.pack("<I", tile)), (323, _LONG, 1, struct.pack("<I", tile)),
-               (324, _LONG8 if bigtiff else _LONG, n, None), (325, _LONG8 if bigtiff else _LONG, n, None)]
+    entries = [entry(TAG.ImageWidth, LONG, [W]), entry(TAG.ImageLength, LONG, [H]), entry(TAG.BitsPerSample, SHORT, [8] * bands),
+               entry(TAG.Compression, SHORT, [5]), entry(TAG.PhotometricInterpretation, SHORT, [2 if rgb else 1]),
+               entry(TAG.SamplesPerPixel, SHORT, [bands]), entry(TAG.PlanarConfiguration, SHORT, [planar]),
+               entry(TAG.TileWidth, LONG, [tile]), entry(TAG.TileLength, LONG, [tile]),
+               entry(TAG.TileOffsets, wide, offsets), entry(TAG.TileByteCounts, wide, counts),
+               entry(TAG.SampleFormat, SHORT, [1] * bands)]
     if bands > 1 and not rgb:
-        entries.append((338, _SHORT, bands - 1, struct.pack(f"<{bands - 1}H", *[0] * (bands - 1))))
-    entries.append((339, _SHORT, bands, struct.pack(f"<{bands}H", *[1] * bands)))
+        entries.append(entry(TAG.ExtraSamples, SHORT, [0] * (bands - 1)))
     for tag, (typ, cnt, raw) in (geo_tags or {}).items():
         tag, typ, cnt, raw = int(tag), int(typ), int(cnt), bytes(raw)
-        if tag not in GEO_TAGS or typ not in _TYPE_SIZE or len(raw) != _TYPE_SIZE[typ] * cnt:
+        if tag not in GEO_TAGS or typ not in TYPE_SIZE or len(raw) != TYPE_SIZE[typ] * cnt:
             raise ValueError(f"geo tag {tag}: type {typ}, count {cnt}, {len(raw)} bytes")
         entries.append((tag, typ, cnt, raw))
-    entries.sort(key=lambda e: e[0])
-    limit = (1 << 64) if bigtiff else (1 << 32)
-    inline, entry_size = (8, 20) if bigtiff else (4, 12)
-    ifd_size = (8 if bigtiff else 2) + entry_size * len(entries) + inline
-    if not bigtiff and max(o + c for o, c in zip(offsets, counts)) > limit:
-        raise ValueError("a classic TIFF holds offsets below 2^32 only: use bigtiff=True")
-    head = [struct.pack("<" + ("Q" if bigtiff else "H"), len(entries))]
-    tail, at = [], ifd_offset + ifd_size
-    for tag, typ, cnt, raw in entries:
-        if raw is None:
-            raw = struct.pack(f"<{n}{wide}", *(offsets if tag == 324 else counts))
-        if len(raw) <= inline:
-            value = raw.ljust(inline, b"\0")
-        else:
-            pad = -at % 8
-            tail.append(b"\0" * pad + raw)
-            at += pad
-            if at + len(raw) > limit:
-                raise ValueError("a classic TIFF holds offsets below 2^32 only: use bigtiff=True")
-            value = struct.pack("<" + wide, at)
-            at += len(raw)
-        head.append(struct.pack("<HH" + wide, tag, typ, cnt) + value)
-    head.append(b"\0" * inline)   # no next IFD
-    return b"".join(head + tail)
+    return build_ifd(sorted(entries, key=lambda e: e[0]), ifd_offset, bigtiff, align=8)
 
 
 def read_geo_tags(path) -> dict:
     """{tag: (type, count, value bytes)} of the GeoTIFF tags (``GEO_TAGS``) in the first IFD of a classic or BigTIFF file, ``{}`` when
     it has none; the bytes are the file's own, in little-endian order (those of a big-endian file are swapped per value, nothing is
     interpreted).  ValueError for bytes that are no TIFF."""
+    name = os.fspath(path)
     with open(path, "rb") as f:
-        head = f.read(16)
-        order = head[:2]
-        if len(head) < 8 or order not in (b"II", b"MM"):
-            raise ValueError(f"{os.fspath(path)!r} is not a TIFF")
-        e = "<" if order == b"II" else ">"
-        (magic,) = struct.unpack_from(e + "H", head, 2)
-        if magic == 42:
-            big, (ifd,) = False, struct.unpack_from(e + "I", head, 4)
-        elif magic == 43 and len(head) == 16 and struct.unpack_from(e + "HH", head, 4) == (8, 0):
-            big, (ifd,) = True, struct.unpack_from(e + "Q", head, 8)
-        else:
-            raise ValueError(f"{os.fspath(path)!r} is not a TIFF")
-        size = f.seek(0, os.SEEK_END)
-        fmt, entry_size, inline, cnt_fmt = ("HHQ8s", 20, 8, "Q") if big else ("HHI4s", 12, 4, "H")
-        f.seek(ifd)
-        raw_n = f.read(struct.calcsize(cnt_fmt))
-        if ifd < 8 or len(raw_n) != struct.calcsize(cnt_fmt):
-            raise ValueError(f"{os.fspath(path)!r}: the IFD lies outside the file")
-        (n,) = struct.unpack(e + cnt_fmt, raw_n)
-        table = f.read(entry_size * n)
-        if len(table) != entry_size * n:
-            raise ValueError(f"{os.fspath(path)!r}: the IFD lies outside the file")
-        tags = {}
-        for i in range(n):
-            tag, typ, cnt, value = struct.unpack_from(e + fmt, table, entry_size * i)
-            if tag not in GEO_TAGS or typ not in _TYPE_SIZE:
-                continue
-            nbytes = _TYPE_SIZE[typ] * cnt
-            if nbytes <= inline:
-                raw = value[:nbytes]
-            else:
-                (at,) = struct.unpack(e + ("Q" if big else "I"), value)
-                if at + nbytes > size:
-                    raise ValueError(f"{os.fspath(path)!r}: tag {tag} lies outside the file")
-                f.seek(at)
-                raw = f.read(nbytes)
-            unit = _UNIT_SIZE[typ]
-            if e == ">" and unit > 1:
-                raw = np.frombuffer(raw, dtype=f">u{unit}").astype(f"<u{unit}").tobytes()
-            tags[tag] = (typ, cnt, raw)
-    return tags
+        if os.fstat(f.fileno()).st_size < 8:
+            raise ValueError(f"{name!r} is not a TIFF")
+        with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+            try:
+                d = Directory(mm)
+                return {tag: d.raw_le(tag) for tag, (typ, _, _) in d.entries.items() if tag in GEO_TAGS and typ in TYPE_SIZE}
+            except DirectoryError as err:
+                if err.what in ("order", "magic"):
+                    raise ValueError(f"{name!r} is not a TIFF") from None
+                where = f"tag {err.tag}" if err.what == "outside" else "the IFD"
+                raise ValueError(f"{name!r}: {where} lies outside the file") from None
 
 
-_pinned = [None, None]   # the two staging buffers of write_raster, kept between calls
-
-
-def _pinned_bytes(slot, n):
-    if _pinned[slot] is None or _pinned[slot].numel() < n:
-        _pinned[slot] = None
-        _pinned[slot] = torch.empty(max(n, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-    return _pinned[slot]
-
-
-def stream_groups(n_streams: int, tiles_x: int, stream_bytes: int, group_bytes: int):
-    """(first, n) of the groups write_raster encodes at a time: as many streams as ``group_bytes`` of raw tile bytes hold, whole tile
-    rows where a row fits, one stream at least"""
-    per = max(1, int(group_bytes) // stream_bytes)
-    if per >= tiles_x:
-        per -= per % tiles_x
-    return [(first, min(per, n_streams - first)) for first in range(0, n_streams, per)]
+_staging = PinnedPair()   # write_raster's own, kept between calls
 
 
 def write_raster(path, raster, tile, interleave="band", scale=None, bigtiff=True, geo_tags=None, group_bytes=GROUP_BYTES) -> dict:
@@ -207,7 +139,7 @@ def write_raster(path, raster, tile, interleave="band", scale=None, bigtiff=True
             try:
                 if not errors:
                     copied.synchronize()
-                    f.write(_pinned[k].numpy()[:nbytes])
+                    f.write(_staging.buffers[k].numpy()[:nbytes])
             except Exception as e:  # noqa: BLE001 - surfaces from write_raster below
                 errors.append(e)
             finally:
@@ -229,7 +161,7 @@ def write_raster(path, raster, tile, interleave="band", scale=None, bigtiff=True
                 k = free.get()   # blocks while both buffers are waiting to be written
                 if errors:
                     break
-                staging = _pinned_bytes(k, nbytes)
+                staging = _staging.take(k, nbytes)
                 copy_stream.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(copy_stream):
                     staging[:nbytes].copy_(payload[:nbytes], non_blocking=True)

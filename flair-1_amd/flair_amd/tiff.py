@@ -1,6 +1,6 @@
 """The device read path of mask TIFFs (metrics(decode="device")): the host reads the file bytes and parses the
-IFD, the compressed strips of a whole chunk of files go up in one copy, one call of ``ops.tiff_lzw_decode`` (csrc/tiff_lzw.hip)
-decodes every strip of the chunk, and the pixels stay on the device.
+IFD (``tiff_ifd.Directory``), the compressed strips of a whole chunk of files go up in one copy, one call of ``ops.tiff_lzw_decode``
+(csrc/tiff_lzw.hip) decodes every strip of the chunk, and the pixels stay on the device.
 
 ``tiff_strip_layout`` accepts the files PIL, libtiff / GDAL and ``writer.tiff_lzw_file`` write for 8-bit single-band masks and
 nothing else; every other file, and every file one of whose strips the kernel gives a status other than 0, is decoded by PIL
@@ -11,7 +11,6 @@ chunk's status, fall back where needed); ``metrics`` begins the next chunk befor
 from __future__ import annotations
 
 import os
-import struct
 from collections import namedtuple
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
@@ -19,90 +18,51 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from .tiff_ifd import LONG, SHORT, TAG, Directory, DirectoryError, old_style_lzw
+from .tiff_staging import PinnedPair
+
 StripLayout = namedtuple("StripLayout", "H W rows_per_strip offsets counts compression")
 
 MAX_LZW_STRIP = 65536   # decoded bytes of one LZW strip the kernel takes (flair_tiff_lzw_decode_max_strip): PIL's 64 KB strip
 READ_THREADS = 8        # file reads of a chunk in flight
 
-_TYPE_SIZE = {1: 1, 2: 1, 3: 2, 4: 4, 5: 8, 6: 1, 7: 1, 8: 2, 9: 4, 10: 8, 11: 4, 12: 8}
-_SHORT, _LONG = 3, 4
-# tags that decide what the bytes of a strip mean; every other tag (GeoTIFF keys, resolution, software, ...) is ignored
-_WIDTH, _LENGTH, _BITS, _COMPRESSION, _PHOTOMETRIC, _FILL_ORDER, _OFFSETS, _ORIENTATION, _SAMPLES, _ROWS, _COUNTS, _PLANAR = \
-    256, 257, 258, 259, 262, 266, 273, 274, 277, 278, 279, 284
-_PREDICTOR, _TILE_WIDTH, _TILE_LENGTH, _SAMPLE_FORMAT = 317, 322, 323, 339
-
 
 def _layout(data) -> StripLayout | None:
-    n = len(data)
-    if n < 8:
-        return None
-    order = bytes(data[:2])
-    if order == b"II":
-        e = "<"
-    elif order == b"MM":
-        e = ">"
-    else:
-        return None
-    magic, ifd = struct.unpack_from(e + "HI", data, 2)
-    if magic != 42 or ifd < 8 or ifd + 2 > n:
-        return None
-    (count,) = struct.unpack_from(e + "H", data, ifd)
-    if ifd + 2 + 12 * count > n:
-        return None
-    tags = {}
-    for i in range(count):
-        tag, typ, cnt, raw = struct.unpack_from(e + "HHI4s", data, ifd + 2 + 12 * i)
-        tags[tag] = (typ, cnt, raw, ifd + 2 + 12 * i + 8)
-
-    def values(tag, types=(_SHORT, _LONG)):
-        """the entry's values, () when it is absent, None when its type is not one of ``types`` or its data lies outside the file"""
-        if tag not in tags:
-            return ()
-        typ, cnt, raw, at = tags[tag]
-        if typ not in types or cnt < 1:
-            return None
-        size = _TYPE_SIZE[typ] * cnt
-        if size > 4:
-            (at,) = struct.unpack(e + "I", raw)
-            if at + size > n:
-                return None
-        return struct.unpack_from(e + str(cnt) + ("H" if typ == _SHORT else "I"), data, at)
-
+    """tiff_strip_layout's policy over the directory: only the tags that decide what the bytes of a strip mean are looked at"""
     def one(tag, default):
-        v = values(tag)
-        if v == ():
-            return default
-        return v[0] if v is not None and len(v) == 1 else None
+        v = d.ints(tag, (SHORT, LONG))
+        return default if v is None else v[0] if len(v) == 1 else None
 
-    if _TILE_WIDTH in tags or _TILE_LENGTH in tags:
-        return None
-    W, H = one(_WIDTH, None), one(_LENGTH, None)
-    if not W or not H:
-        return None
-    compression = one(_COMPRESSION, 1)
-    # PIL reads an absent PhotometricInterpretation as WhiteIsZero and inverts those pixels, and applies an Orientation: only what
-    # it returns as stored is taken here (BlackIsZero, palette indices)
-    if (one(_BITS, 1) != 8 or one(_SAMPLES, 1) != 1 or compression not in (1, 5) or one(_PREDICTOR, 1) != 1 or
-            one(_FILL_ORDER, 1) != 1 or one(_PLANAR, 1) != 1 or one(_PHOTOMETRIC, None) not in (1, 3) or
-            one(_ORIENTATION, 1) != 1 or one(_SAMPLE_FORMAT, 1) != 1):
-        return None
-    rows = one(_ROWS, H)
-    if not rows:
-        return None
-    rows = min(rows, H)
-    offsets, counts = values(_OFFSETS), values(_COUNTS)
-    nstrips = -(-H // rows)
-    if not offsets or not counts or len(offsets) != nstrips or len(counts) != nstrips:
-        return None
-    for off, cnt in zip(offsets, counts):
-        if off + cnt > n:
+    try:   # DirectoryError: no directory, a value of another type than SHORT or LONG, or one outside the file
+        d = Directory(data)
+        n, tags = len(data), d.entries
+        if d.bigtiff or TAG.TileWidth in tags or TAG.TileLength in tags:
             return None
-        # libtiff recognises the pre-6.0 LSB-first LZW streams by these two bytes and decodes them its own way
-        if compression == 5 and cnt >= 2 and data[off] == 0 and data[off + 1] & 1:
+        W, H = one(TAG.ImageWidth, None), one(TAG.ImageLength, None)
+        if not W or not H:
             return None
-    if compression == 5 and rows * W > MAX_LZW_STRIP:
+        compression = one(TAG.Compression, 1)
+        # PIL reads an absent PhotometricInterpretation as WhiteIsZero and inverts those pixels, and applies an Orientation: only what
+        # it returns as stored is taken here (BlackIsZero, palette indices)
+        if (one(TAG.BitsPerSample, 1) != 8 or one(TAG.SamplesPerPixel, 1) != 1 or compression not in (1, 5) or one(TAG.Predictor, 1) != 1 or
+                one(TAG.FillOrder, 1) != 1 or one(TAG.PlanarConfiguration, 1) != 1 or one(TAG.PhotometricInterpretation, None) not in (1, 3) or
+                one(TAG.Orientation, 1) != 1 or one(TAG.SampleFormat, 1) != 1):
+            return None
+        rows = one(TAG.RowsPerStrip, H)
+        if not rows:
+            return None
+        rows = min(rows, H)
+        offsets, counts = d.ints(TAG.StripOffsets, (SHORT, LONG)), d.ints(TAG.StripByteCounts, (SHORT, LONG))
+        nstrips = -(-H // rows)
+        if not offsets or not counts or len(offsets) != nstrips or len(counts) != nstrips:
+            return None
+        if any(off + cnt > n for off, cnt in zip(offsets, counts)):
+            return None
+        if compression == 5 and (rows * W > MAX_LZW_STRIP or old_style_lzw(data, offsets, counts) is not None):
+            return None
+        return StripLayout(H, W, rows, offsets, counts, compression)
+    except DirectoryError:
         return None
-    return StripLayout(H, W, rows, tuple(offsets), tuple(counts), compression)
 
 
 def tiff_strip_layout(data) -> StripLayout | None:
@@ -137,9 +97,7 @@ def _pil_pixels(path, truth: bool) -> np.ndarray:
 
 
 _pool = None
-_pinned = [None, None]       # two staging buffers, taken in turn: one chunk's copy may be in flight while the next chunk is read
-_pinned_busy = [None, None]  # the event behind the last copy out of each
-_pinned_turn = 0
+_staging = PinnedPair()   # taken in turn: one chunk's copy may be in flight while the next chunk is read
 
 
 def _read_pool():
@@ -147,24 +105,6 @@ def _read_pool():
     if _pool is None:
         _pool = ThreadPoolExecutor(max_workers=READ_THREADS, thread_name_prefix="flair-tiff-read")
     return _pool
-
-
-def _pinned_bytes(n):
-    """(a pinned staging buffer of at least n bytes, its slot): kept between calls, free of any earlier copy out of it"""
-    global _pinned_turn
-    slot = _pinned_turn = 1 - _pinned_turn
-    if _pinned_busy[slot] is not None:
-        _pinned_busy[slot].synchronize()
-        _pinned_busy[slot] = None
-    if _pinned[slot] is None or _pinned[slot].numel() < n:
-        _pinned[slot] = torch.empty(max(n, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-    return _pinned[slot], slot
-
-
-def _pinned_copied(slot):
-    """call after queueing the copy out of the slot's buffer"""
-    _pinned_busy[slot] = torch.cuda.Event()
-    _pinned_busy[slot].record()
 
 
 def _read_into(args):
@@ -224,7 +164,7 @@ def begin_read_masks(paths, device, decode="device", truth=False) -> PendingMask
         for s in sizes:
             bases.append(total)
             total += _align16(max(s, 0))
-        staging, slot = _pinned_bytes(total)
+        staging, slot = _staging.take_next(total)
         raw = staging.numpy()
         jobs = [(p, memoryview(raw[b:b + s])) for p, b, s in zip(paths, bases, sizes) if s > 0]
         complete = iter(list(_read_pool().map(_read_into, jobs)))
@@ -262,7 +202,7 @@ def begin_read_masks(paths, device, decode="device", truth=False) -> PendingMask
         t64 = torch.tensor([src_off, dst_off], dtype=torch.int64).to(job.device)
         t32 = torch.tensor([src_len, dst_len, mode], dtype=torch.int32).to(job.device)
         src = staging[:total].to(job.device, non_blocking=True)
-        _pinned_copied(slot)
+        _staging.copied(slot)
         _, status = ops.tiff_lzw_decode(src, t64[0], t32[0], t64[1], t32[1], t32[2], job.pixels.numel(), out=job.pixels)
         # the status comes down behind this chunk's kernel, ahead of whatever the caller queues next
         job.status = torch.empty(status.shape, dtype=torch.int32, pin_memory=True)

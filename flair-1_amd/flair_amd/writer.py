@@ -8,19 +8,21 @@ side stream (1 byte/pixel), and encoding runs on a worker thread while the next 
 same ``PRED_<name>`` LZW TIFFs through PIL as the reference does (writer.py:45-50).
 
 ``encode="device"`` moves the LZW encode to the GPU as well (csrc/tiff_lzw.hip): the worker then only frames the finished
-strips (``tiff_lzw_file``) and writes them.  ``encode="host"``, the default, is the PIL path above.
+strips (``tiff_lzw_file``, over ``tiff_ifd.build_ifd``) and writes them.  ``encode="host"``, the default, is the PIL path above.
 """
 from __future__ import annotations
 
 import atexit
 import os
 import queue
-import struct
 import threading
 import weakref
 from pathlib import Path
 
 import torch
+
+from .raster_writer import tiled_tiff_header
+from .tiff_ifd import LONG, SHORT, TAG, build_ifd, entry, ifd_size
 
 try:  # pragma: no cover - lightning is absent in the build image
     from pytorch_lightning.callbacks import BasePredictionWriter as _Base
@@ -45,24 +47,14 @@ def tiff_lzw_file(H: int, W: int, rows_per_strip: int, strips) -> bytes:
     n = len(strips)
     if n != -(-H // rows_per_strip):
         raise ValueError(f"{n} strips for {H} rows at {rows_per_strip} rows per strip")
-    SHORT, LONG = 3, 4
-    ifd_end = 8 + 2 + 10 * 12 + 4
-    data0 = ifd_end + (8 * n if n > 1 else 0)
     counts = [len(st) for st in strips]
-    offsets = [data0]
-    for c in counts[:-1]:
-        offsets.append(offsets[-1] + c)
-    entries = [(256, LONG, 1, W), (257, LONG, 1, H), (258, SHORT, 1, 8), (259, SHORT, 1, 5), (262, SHORT, 1, 1),
-               (273, LONG, n, offsets[0] if n == 1 else ifd_end), (277, SHORT, 1, 1), (278, LONG, 1, rows_per_strip),
-               (279, LONG, n, counts[0] if n == 1 else ifd_end + 4 * n), (284, SHORT, 1, 1)]
-    parts = [b"II*\0", struct.pack("<I", 8), struct.pack("<H", len(entries))]
-    parts += [struct.pack("<HHIHH" if typ == SHORT else "<HHII", tag, typ, cnt, *((val, 0) if typ == SHORT else (val,)))
-              for tag, typ, cnt, val in entries]
-    parts.append(struct.pack("<I", 0))
-    if n > 1:
-        parts += [struct.pack(f"<{n}I", *offsets), struct.pack(f"<{n}I", *counts)]
-    parts += strips
-    return b"".join(parts)
+    data0 = 8 + ifd_size(10, False) + (8 * n if n > 1 else 0)   # behind the two arrays, which a single strip does not need
+    offsets = [data0 + sum(counts[:k]) for k in range(n)]
+    entries = [entry(TAG.ImageWidth, LONG, [W]), entry(TAG.ImageLength, LONG, [H]), entry(TAG.BitsPerSample, SHORT, [8]),
+               entry(TAG.Compression, SHORT, [5]), entry(TAG.PhotometricInterpretation, SHORT, [1]), entry(TAG.StripOffsets, LONG, offsets),
+               entry(TAG.SamplesPerPixel, SHORT, [1]), entry(TAG.RowsPerStrip, LONG, [rows_per_strip]),
+               entry(TAG.StripByteCounts, LONG, counts), entry(TAG.PlanarConfiguration, SHORT, [1])]
+    return b"".join([tiled_tiff_header(8, bigtiff=False), build_ifd(entries, 8, False), *strips])
 
 
 class predictionwriter(_Base):

@@ -101,7 +101,7 @@ def device_split(files, dev, chunk_files=128, reps=5):
         t0 = time.perf_counter()
         sizes = [os.stat(p).st_size for p in chunk]
         bases = np.concatenate([[0], np.cumsum([(s + 15) & ~15 for s in sizes])])
-        staging, _ = tiff._pinned_bytes(int(bases[-1]))
+        staging, _ = tiff._staging.take_next(int(bases[-1]))
         raw = staging.numpy()
         assert all(tiff._read_pool().map(tiff._read_into, [(p, memoryview(raw[b:b + s])) for p, b, s in zip(chunk, bases, sizes)]))
         layouts = [tiff.tiff_strip_layout(raw[b:b + s]) for b, s in zip(bases, sizes)]

@@ -99,7 +99,7 @@ def boundary_counts(refs, window):
     """how many sources lie on each side of the kernel's two boundaries at their code's output position op.  The window, op - window:
     'back' wholly below it (read back from the slot), 'ring' wholly at or above it, 'across' both.  The flush block, op rounded down
     to BLOCK (what is below is in the slot already): 'flushed', 'unflushed', 'half'.  'far': sources more than 65 536 bytes back, the
-    parent kernel's whole reach; 'longest': the longest source."""
+    strip decoder's whole reach (tiff_lzw_decode_kernel's 16-bit positions); 'longest': the longest source."""
     c = dict(back=0, ring=0, across=0, flushed=0, unflushed=0, half=0, far=0, longest=0)
     for op, frm, n in refs:
         lo, fl = op - window, op // BLOCK * BLOCK
