@@ -857,6 +857,10 @@ int flair_tiff_chunks_to_planes(const uint8_t* scratch, long slot_bytes, const i
   return tiff_chunks_to_planes(scratch, slot_bytes, chunks, status, nchunks, max_rows, samples, predictor, planes, bands, H, W,
                                (hipStream_t)stream);
 }
+int flair_tiff_chunks_to_batch(const uint8_t* scratch, long slot_bytes, const int32_t* chunks, const int32_t* status, long nchunks,
+                               int max_rows, uint8_t* planes, int n_planes, int H, int W, void* stream) {
+  return tiff_chunks_to_batch(scratch, slot_bytes, chunks, status, nchunks, max_rows, planes, n_planes, H, W, (hipStream_t)stream);
+}
 
 // ------------------------------------------------------------------------------------------ SegFormer (zone_detect, HuggingFace provider)
 int flair_segformer_create(flair_segformer_t** out, int in_channels, int num_labels, const int depths[4], const int hidden_sizes[4],

@@ -167,5 +167,8 @@ int tiff_lzw_decode_chunks(const unsigned char* src, long src_bytes, const long 
                            const int* mode, long nchunks, unsigned char* scratch, long slot_bytes, int* status, hipStream_t s);
 int tiff_chunks_to_planes(const unsigned char* scratch, long slot_bytes, const int* chunks, const int* status, long nchunks, int max_rows,
                           int samples, int predictor, unsigned char* planes, int bands, int H, int W, hipStream_t s);
+// the same scatter for the chunks of a batch of files, samples and predictor per chunk (the tile loader)
+int tiff_chunks_to_batch(const unsigned char* scratch, long slot_bytes, const int* chunks, const int* status, long nchunks, int max_rows,
+                         unsigned char* planes, int n_planes, int H, int W, hipStream_t s);
 
 }  // namespace flair

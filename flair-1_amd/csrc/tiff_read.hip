@@ -121,27 +121,22 @@ __global__ __launch_bounds__(64) void tiff_lzw_decode_chunks_kernel(const unsign
   if (lane == 0) status[chunk] = st;
 }
 
-// Chunk c's decoded bytes, rows x width pixels of `samples` bytes each, row-major, to the band planes: sample k of the pixel at
-// (r, x) goes to planes[band0 + k][y0 + r][x0 + x] when that lies inside the raster.  One wave per chunk row, a lane per pixel, 64
-// pixels a trip: the stores of a trip are 64 consecutive bytes of one plane row.  PRED: TIFF predictor 2, per sample the running
-// sum modulo 256 along the chunk row, as an inclusive wave scan per trip plus the carry of the trips before (lane 63's sum).
+// The row walk of both scatter kernels.  A chunk's decoded bytes, rows x width pixels of `samples` bytes each, row-major, to planes
+// of H x W bytes: sample k of the pixel at (r, x) goes to first[k][y0 + r][x0 + x] (`first` the plane of sample 0) when that lies
+// inside H x W.  The block's four waves take the rows blockIdx.y * 4 + wave, + gridDim.y * 4, ...: one wave per chunk row, a lane per
+// pixel, 64 pixels a trip, so the stores of a trip are 64 consecutive bytes of one plane row.  PRED: TIFF predictor 2, per sample
+// the running sum modulo 256 along the chunk row, as an inclusive wave scan per trip plus the carry of the trips before (lane 63's
+// sum).  The caller has checked the chunk: x0, y0 >= 0, width, rows, samples >= 1, the slot holds the chunk, the planes exist.
 template <bool PRED>
-__global__ __launch_bounds__(256) void tiff_chunks_to_planes_kernel(const unsigned char* __restrict__ scratch, long slot_bytes,
-                                                                    const int* __restrict__ chunks, const int* __restrict__ status,
-                                                                    int samples, unsigned char* __restrict__ planes, int bands, int H, int W) {
-  const long c = blockIdx.x;
+__device__ __forceinline__ void chunk_rows_to_planes(const unsigned char* __restrict__ slot, int x0, int y0, int width, int rows, int samples,
+                                                     unsigned char* __restrict__ first, int H, int W) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (status[c] != 0) return;
-  const int x0 = chunks[5 * c], y0 = chunks[5 * c + 1], width = chunks[5 * c + 2], rows = chunks[5 * c + 3], band0 = chunks[5 * c + 4];
-  if (x0 < 0 || y0 < 0 || width < 1 || rows < 1 || band0 < 0 || band0 > bands - samples) return;
-  if ((long)width * rows * samples > slot_bytes) return;
-  const unsigned char* __restrict__ slot = scratch + c * slot_bytes;
   const long plane = (long)H * W;
   for (int r = blockIdx.y * 4 + wave; r < rows; r += gridDim.y * 4) {
     const int y = y0 + r;
     if (y >= H) return;                                     // rows of an edge tile below the raster, and every row after
     const unsigned char* __restrict__ row = slot + (long)r * width * samples;
-    unsigned char* __restrict__ out = planes + (long)band0 * plane + (long)y * W + x0;
+    unsigned char* __restrict__ out = first + (long)y * W + x0;
     for (int k = 0; k < samples; ++k) {
       unsigned carry = 0;
       for (int xb = 0; xb < width; xb += 64) {
@@ -161,6 +156,40 @@ __global__ __launch_bounds__(256) void tiff_chunks_to_planes_kernel(const unsign
       }
     }
   }
+}
+
+// One raster: every chunk has the launch's `samples` and predictor; chunks (n, 5) {x0, y0, width, rows, band0}.
+template <bool PRED>
+__global__ __launch_bounds__(256) void tiff_chunks_to_planes_kernel(const unsigned char* __restrict__ scratch, long slot_bytes,
+                                                                    const int* __restrict__ chunks, const int* __restrict__ status,
+                                                                    int samples, unsigned char* __restrict__ planes, int bands, int H, int W) {
+  const long c = blockIdx.x;
+  if (status[c] != 0) return;
+  const int x0 = chunks[5 * c], y0 = chunks[5 * c + 1], width = chunks[5 * c + 2], rows = chunks[5 * c + 3], band0 = chunks[5 * c + 4];
+  if (x0 < 0 || y0 < 0 || width < 1 || rows < 1 || band0 < 0 || band0 > bands - samples) return;
+  if ((long)width * rows * samples > slot_bytes) return;
+  chunk_rows_to_planes<PRED>(scratch + c * slot_bytes, x0, y0, width, rows, samples, planes + (long)band0 * H * W, H, W);
+}
+
+// A batch of files: chunks (n, 8) {x0, y0, width, rows, plane0, samples, predictor, 0}, every chunk with the samples and the
+// predictor of its own file; planes (n_planes, H, W), the planes of all files one behind the other.  What decides a chunk's path is
+// its table row, the same for the whole block: the branch on the predictor does not diverge.
+__global__ __launch_bounds__(256) void tiff_chunks_to_batch_kernel(const unsigned char* __restrict__ scratch, long slot_bytes,
+                                                                   const int* __restrict__ chunks, const int* __restrict__ status,
+                                                                   unsigned char* __restrict__ planes, int n_planes, int H, int W) {
+  const long c = blockIdx.x;
+  if (status[c] != 0) return;
+  const int* __restrict__ t = chunks + 8 * c;
+  const int x0 = t[0], y0 = t[1], width = t[2], rows = t[3], plane0 = t[4], samples = t[5], predictor = t[6];
+  if (x0 < 0 || y0 < 0 || width < 1 || rows < 1 || samples < 1 || plane0 < 0 || plane0 > n_planes - samples) return;
+  if (predictor != 1 && predictor != 2) return;
+  if ((long)width * rows > slot_bytes / samples) return;   // width * rows * samples > slot_bytes, without the product of three
+  const unsigned char* __restrict__ slot = scratch + c * slot_bytes;
+  unsigned char* __restrict__ first = planes + (long)plane0 * H * W;
+  if (predictor == 2)
+    chunk_rows_to_planes<true>(slot, x0, y0, width, rows, samples, first, H, W);
+  else
+    chunk_rows_to_planes<false>(slot, x0, y0, width, rows, samples, first, H, W);
 }
 
 }  // namespace
@@ -194,6 +223,18 @@ int tiff_chunks_to_planes(const unsigned char* scratch, long slot_bytes, const i
     hipLaunchKernelGGL((tiff_chunks_to_planes_kernel<true>), grid, block, 0, s, scratch, slot_bytes, chunks, status, samples, planes, bands, H, W);
   else
     hipLaunchKernelGGL((tiff_chunks_to_planes_kernel<false>), grid, block, 0, s, scratch, slot_bytes, chunks, status, samples, planes, bands, H, W);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
+int tiff_chunks_to_batch(const unsigned char* scratch, long slot_bytes, const int* chunks, const int* status, long nchunks, int max_rows,
+                         unsigned char* planes, int n_planes, int H, int W, hipStream_t s) {
+  if (!scratch || !chunks || !status || !planes) return -1;
+  if (nchunks < 1 || nchunks > 0x7fffffffL || slot_bytes < 1 || max_rows < 1 || n_planes < 1 || H < 1 || W < 1) return -1;
+  if (((uintptr_t)chunks & 3) || ((uintptr_t)status & 3)) return -2;
+  const dim3 grid((unsigned)nchunks, (unsigned)min((max_rows + 3) / 4, 65535)), block(256);
+  ProfScope ps("tiff_chunks_to_batch", 0.0, 0.0, s);
+  hipLaunchKernelGGL(tiff_chunks_to_batch_kernel, grid, block, 0, s, scratch, slot_bytes, chunks, status, planes, n_planes, H, W);
   FLAIR_CHECK_LAUNCH();
   return 0;
 }

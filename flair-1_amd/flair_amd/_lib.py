@@ -135,6 +135,7 @@ PROTOTYPES = {
     "flair_tiff_lzw_decode_chunks_window": (i32, []),
     "flair_tiff_lzw_decode_chunks": (i32, [vp, C.c_long, vp, vp, vp, vp, C.c_long, vp, C.c_long, vp, vp]),
     "flair_tiff_chunks_to_planes": (i32, [vp, C.c_long, vp, vp, C.c_long, i32, i32, i32, vp, i32, i32, i32, vp]),
+    "flair_tiff_chunks_to_batch": (i32, [vp, C.c_long, vp, vp, C.c_long, i32, vp, i32, i32, i32, vp]),
     "flair_segformer_create": (i32, [C.POINTER(vp), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, i32]),
     "flair_segformer_destroy": (None, [vp]),
     "flair_segformer_param_count": (i64, [vp]),

@@ -559,6 +559,30 @@ def tiff_chunks_to_planes(scratch, chunks, status, planes, samples, predictor=1,
     return planes
 
 
+def tiff_chunks_to_batch(scratch, chunks, status, planes, max_rows=None):
+    """Scatters the decoded chunks of a batch of files into ``planes``, a uint8 device tensor whose last two axes are (H, W) and whose
+    leading axes count the planes ((B, bands, H, W) images, (B, H, W) masks), in place: ``scratch`` (n, slot_bytes) uint8 as
+    ``tiff_lzw_decode_chunks`` returns it, ``chunks`` (n, 8) int32 rows {x0, y0, width, rows, plane0, samples, predictor, 0} on the
+    device, ``status`` int32 per chunk (chunks whose status is not 0 are skipped).  Samples and predictor are per chunk: the files of
+    a batch may differ in layout.  ``max_rows``: the largest ``rows`` of the table when the caller knows it; otherwise it is read from
+    the device, which waits for it.  Returns ``planes``."""
+    if scratch.dtype != torch.uint8 or scratch.dim() != 2:
+        raise L.FlairHipError("tiff_chunks_to_batch needs the (n, slot_bytes) uint8 scratch of tiff_lzw_decode_chunks")
+    n, slot_bytes = scratch.shape
+    if chunks.dtype != torch.int32 or tuple(chunks.shape) != (n, 8) or status.dtype != torch.int32 or tuple(status.shape) != (n,):
+        raise L.FlairHipError(f"tiff_chunks_to_batch: chunks must be ({n}, 8) int32 and status ({n},) int32")
+    if planes.dtype != torch.uint8 or planes.dim() < 3:
+        raise L.FlairHipError("tiff_chunks_to_batch writes a (..., H, W) uint8 tensor of planes")
+    H, W = planes.shape[-2:]
+    n_planes = planes.numel() // max(1, H * W)
+    ptrs = [L.ptr(scratch), L.ptr(chunks), L.ptr(status), L.ptr(planes)]
+    if max_rows is None:
+        max_rows = int(chunks[:, 3].max())
+    L.check(L.lib().flair_tiff_chunks_to_batch(ptrs[0], slot_bytes, ptrs[1], ptrs[2], n, max(1, int(max_rows)), ptrs[3], n_planes, H, W,
+                                               L.stream()), "tiff_chunks_to_batch")
+    return planes
+
+
 def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
 

@@ -94,6 +94,19 @@ class RasterLayout:
         rows = np.full_like(i, self.chunk_h) if self.tiled else np.minimum(self.chunk_h, self.H - y0)
         return np.stack([x * self.chunk_w, y0, np.full_like(i, self.chunk_w), rows, band0], axis=1).astype(np.int32)
 
+    @property
+    def slot_bytes(self) -> int:
+        """a decoded chunk rounded up to the decoder's flush block: the slot a chunk of this file needs"""
+        return -(-self.chunk_w * self.chunk_h * self.samples // FLUSH_BLOCK) * FLUSH_BLOCK
+
+    def decode_tables(self):
+        """(table, src_len, dst_len, mode): ``chunk_table()`` and the three int32 arrays flair_tiff_lzw_decode_chunks takes next to
+        the source offsets: the compressed and the decoded bytes of every chunk, and 0 = stored / 1 = LZW"""
+        table = self.chunk_table()
+        dst_len = (table[:, 2].astype(np.int64) * table[:, 3] * self.samples).astype(np.int32)
+        mode = np.full(self.n_chunks, 1 if self.compression == 5 else 0, dtype=np.int32)
+        return table, self.counts.astype(np.int32), dst_len, mode
+
     def chunk_name(self, i: int) -> str:
         x0, y0, _, _, band0 = self.chunk_table()[i]
         kind = "tile" if self.tiled else "strip"
@@ -216,7 +229,7 @@ def read_plan(layout: RasterLayout, group_bytes: int = GROUP_BYTES):
     fit ``group_bytes`` (whole chunk rows where they fit, ``raster_writer.stream_groups``); ``slot_bytes``: a decoded chunk rounded up to
     the flush block; ``src_off[i]``: where chunk i lies in its group's staging buffer; ``reads[g]``: (buffer bytes, [(file offset,
     length, buffer offset)]) - chunks are read in file order and neighbours closer than ``MERGE_GAP`` with one read()."""
-    slot = -(-layout.chunk_w * layout.chunk_h * layout.samples // FLUSH_BLOCK) * FLUSH_BLOCK
+    slot = layout.slot_bytes
     groups = stream_groups(layout.n_chunks, layout.chunks_x, slot, group_bytes)
     src_off = np.zeros(layout.n_chunks, dtype=np.int64)
     reads = []
@@ -266,12 +279,10 @@ def read_raster(path, device, group_bytes: int = GROUP_BYTES) -> torch.Tensor:
         with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
             layout = raster_layout(mm)
         groups, slot, src_off, reads = read_plan(layout, group_bytes)
-        table = layout.chunk_table()
-        dst_len = (table[:, 2].astype(np.int64) * table[:, 3] * layout.samples).astype(np.int32)
+        table, src_len, dst_len, mode = layout.decode_tables()
         with torch.cuda.device(dev):
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
-            d_src_off, d_src_len, d_dst_len, d_table = up(src_off), up(layout.counts.astype(np.int32)), up(dst_len), up(table)
-            d_mode = torch.full((layout.n_chunks,), 1 if layout.compression == 5 else 0, dtype=torch.int32, device=dev)
+            d_src_off, d_src_len, d_dst_len, d_mode, d_table = up(src_off), up(src_len), up(dst_len), up(mode), up(table)
             status = torch.empty(layout.n_chunks, dtype=torch.int32, device=dev)
             planes = torch.empty(layout.bands, layout.H, layout.W, dtype=torch.uint8, device=dev)
             scratch = torch.empty(max(n for _, n in groups) * slot, dtype=torch.uint8, device=dev)
@@ -302,10 +313,15 @@ def read_raster(path, device, group_bytes: int = GROUP_BYTES) -> torch.Tensor:
             finally:
                 copy_stream.synchronize()   # no buffer is freed under a copy
             status_h = status.cpu().numpy()   # the one wait
-    bad = np.flatnonzero(status_h)
+    raise_if_failed(path, layout, status_h)
+    return planes
+
+
+def raise_if_failed(path, layout: RasterLayout, status):
+    """``RasterDecodeError`` for the first chunk of the file whose status (one code per chunk, in the file's chunk order) is not 0"""
+    bad = np.flatnonzero(status)
     if len(bad):
         i = int(bad[0])
-        code = int(status_h[i])
+        code = int(status[i])
         raise RasterDecodeError(f"{os.fspath(path)!r}: {layout.chunk_name(i)} did not decode: status {code} "
                                 f"({STATUS_TEXT.get(code, 'unknown')}); {len(bad)} of {layout.n_chunks} chunks failed", i, code)
-    return planes

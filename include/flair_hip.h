@@ -366,6 +366,22 @@ int flair_tiff_lzw_decode_chunks(const uint8_t* src, long src_bytes, const int64
  * than 1 / 2; -2 unless chunks and status are 4-byte aligned.  No device sync. */
 int flair_tiff_chunks_to_planes(const uint8_t* scratch, long slot_bytes, const int32_t* chunks, const int32_t* status, long nchunks,
                                 int max_rows, int samples, int predictor, uint8_t* planes, int bands, int H, int W, void* stream);
+/* The same scatter for the chunks of a batch of files (flair_amd/tile_loader.py), each chunk with the layout of its own file: planes
+ * (n_planes, H, W) uint8 holds the planes of all files one behind the other, chunks (nchunks, 8) int32 on the device, row i = {x0, y0,
+ * width, rows, plane0, samples, predictor, 0}.  Slot i holds rows x width pixels of samples[i] bytes each, row-major, the samples of a
+ * pixel next to each other; sample k of the pixel at (r, x) is written to planes[plane0 + k][y0 + r][x0 + x] if y0 + r < H and
+ * x0 + x < W and dropped otherwise.  For image b of a (B, bands, H, W) batch the host sets plane0 = b * bands + band0 (samples = bands
+ * and band0 = 0 for PlanarConfiguration 1, samples = 1 for PlanarConfiguration 2), for mask b of a (B, H, W) batch plane0 = b and
+ * samples = 1.  predictor[i] 1: the bytes as they are; 2: per chunk row and per sample the running sum modulo 256 along the row,
+ * starting afresh at the chunk's left edge.  The eighth entry of a row is not read.  One launch takes tiles and strips, both
+ * interleaves, both predictors and files that differ in all of them; that a slot came from a stored or an LZW chunk does not show.
+ * A chunk whose status[i] is not 0 is skipped, and so is one with x0, y0 or plane0 below 0, width, rows or samples below 1,
+ * plane0 + samples > n_planes, a predictor other than 1 / 2 or width * rows * samples > slot_bytes; nothing else of planes is written.
+ * max_rows: the largest `rows` of the table, which the host knows; it sizes the launch only.
+ * Returns -1 for a null pointer, nchunks, slot_bytes, max_rows, n_planes or an extent < 1; -2 unless chunks and status are 4-byte
+ * aligned.  No device sync. */
+int flair_tiff_chunks_to_batch(const uint8_t* scratch, long slot_bytes, const int32_t* chunks, const int32_t* status, long nchunks,
+                               int max_rows, uint8_t* planes, int n_planes, int H, int W, void* stream);
 
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
