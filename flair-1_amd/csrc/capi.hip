@@ -37,6 +37,23 @@ static int tf_tensor_info(const std::vector<SfTensor>& tensors, int i, char* nam
   return 0;
 }
 
+// the arguments flair_feed_tiles and flair_feed_tiles_ptrs share, checked and packed; have_img: the call names image sources
+static int feed_args(FeedArgs& a, bool have_img, const uint8_t* d4_flags, int B, int bands, int H, int W, const int* channels, int n_channels,
+                     int norm_type, const double* means, const double* stds, int num_classes, float* img_out, uint8_t* labels_out) {
+  if (!img_out && !labels_out) return -1;
+  if (n_channels < 0 || n_channels > FeedArgs::MAXCH) return -2;
+  if (img_out && (!have_img || !channels || n_channels < 1)) return -1;
+  if (norm_type == 2 && (!means || !stds)) return -1;
+  a.d4 = d4_flags; a.out = img_out; a.labels = labels_out;
+  a.B = B; a.Cb = bands; a.Cout = img_out ? n_channels : 0; a.H = H; a.W = W; a.mode = norm_type; a.num_classes = num_classes;
+  for (int c = 0; c < a.Cout; ++c) {
+    a.band[c] = channels[c] - 1;  // config "channels" start at 1 (rasterio band numbering)
+    a.mean[c] = norm_type == 2 ? means[c] : 0.0;
+    a.stdv[c] = norm_type == 2 ? stds[c] : 1.0;
+  }
+  return 0;
+}
+
 extern "C" {
 
 const char* flair_strerror(int code) {
@@ -196,19 +213,21 @@ int flair_jaccard(const int64_t* confmat, int C, float* per_class, float* weight
 int flair_feed_tiles(const uint8_t* img_u8, const uint8_t* msk_raw, const uint8_t* d4_flags, int B, int bands, int H, int W,
                      const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
                      int num_classes, float* img_out, uint8_t* labels_out, void* stream) {
-  if (!img_out && !labels_out) return -1;
-  if (n_channels < 0 || n_channels > FeedArgs::MAXCH) return -2;
-  if (img_out && (!img_u8 || !channels || n_channels < 1)) return -1;
-  if (norm_type == 2 && (!means || !stds)) return -1;
   FeedArgs a{};
-  a.img = img_u8; a.msk = msk_raw; a.d4 = d4_flags; a.out = img_out; a.labels = labels_out;
-  a.B = B; a.Cb = bands; a.Cout = img_out ? n_channels : 0; a.H = H; a.W = W; a.mode = norm_type; a.num_classes = num_classes;
-  for (int c = 0; c < a.Cout; ++c) {
-    a.band[c] = channels[c] - 1;  // config "channels" start at 1 (rasterio band numbering)
-    a.mean[c] = norm_type == 2 ? means[c] : 0.0;
-    a.stdv[c] = norm_type == 2 ? stds[c] : 1.0;
-  }
+  const int rc = feed_args(a, img_u8 != nullptr, d4_flags, B, bands, H, W, channels, n_channels, norm_type, means, stds, num_classes,
+                           img_out, labels_out);
+  if (rc) return rc;
+  a.img = img_u8; a.msk = msk_raw;
   return feed_tiles(a, (hipStream_t)stream);
+}
+int flair_feed_tiles_ptrs(const uint64_t* img_ptrs, const uint64_t* msk_ptrs, const uint8_t* d4_flags, int B, int bands, int H, int W,
+                          const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
+                          int num_classes, float* img_out, uint8_t* labels_out, void* stream) {
+  FeedArgs a{};
+  const int rc = feed_args(a, img_ptrs != nullptr, d4_flags, B, bands, H, W, channels, n_channels, norm_type, means, stds, num_classes,
+                           img_out, labels_out);
+  if (rc) return rc;
+  return feed_tiles_ptrs(a, (const unsigned long long*)img_ptrs, (const unsigned long long*)msk_ptrs, (hipStream_t)stream);
 }
 int flair_detect_convert(const float* logits_nchw, int B, int C, int S, int margin, int output_type, void* out, void* stream) {
   if (!logits_nchw || !out) return -1;

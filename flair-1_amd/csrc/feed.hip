@@ -3,6 +3,8 @@
 //                   selection, normalisation ('custom' in fp64 like numpy, 'scaling', 'without'), the D4
 //                   augmentation (V-flip, H-flip, rot90^k) and label decoding, in one pass.
 //                   src/flair/data_loader.py:9-30,65-95; src/flair/tasks_utils.py:37-41.
+//   feed_tiles_ptrs the same pass over samples found through two tables of addresses (flair_amd/tile_cache.py): one loop
+//                   body, instantiated for the two ways of finding a sample's source.
 //   detect_convert  softmax -> margin crop -> convert('argmax' | 'class_prob') of zone_detect.
 //                   src/zone_detect/compare.py:35,71-76; src/zone_detect/dataset.py:11-34.
 //   confmat_masks   offline evaluation: confusion matrix of (truth raster - 1) against a prediction raster.
@@ -35,13 +37,37 @@ __device__ __forceinline__ float norm_byte(int mode, unsigned char v, double mea
   return (float)v;
 }
 
-__global__ __launch_bounds__(256) void feed_tiles_kernel(FeedArgs a) {
+// Where sample b of a feed launch lies.  PackedTiles: the batch tensors of FeedArgs, one sample behind the other.
+struct PackedTiles {
+  const unsigned char* img;
+  const unsigned char* msk;
+  long img_stride, msk_stride;
+  __device__ __forceinline__ bool skip(int) const { return false; }
+  __device__ __forceinline__ const unsigned char* image(int b) const { return img + (long)b * img_stride; }
+  __device__ __forceinline__ const unsigned char* mask(int b) const { return msk + (long)b * msk_stride; }
+};
+
+// TilesByAddress: two tables of device addresses, one entry per sample, in any order and with repeats (tiles resident in cache
+// slots next to tiles a decode just wrote).  Image address 0: the sample is skipped whole; mask address 0: it gets no labels.
+struct TilesByAddress {
+  const unsigned long long* img;
+  const unsigned long long* msk;
+  __device__ __forceinline__ bool skip(int b) const { return img[b] == 0; }
+  __device__ __forceinline__ const unsigned char* image(int b) const { return reinterpret_cast<const unsigned char*>(img[b]); }
+  __device__ __forceinline__ const unsigned char* mask(int b) const {
+    return msk ? reinterpret_cast<const unsigned char*>(msk[b]) : nullptr;
+  }
+};
+
+template <class SRC>
+__global__ __launch_bounds__(256) void feed_tiles_kernel(FeedArgs a, SRC from) {
   const int W4 = a.W / 4;
   const long per_img = (long)a.H * W4;
   const long total = per_img * a.B;
   const long HW = (long)a.H * a.W;
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
     const int b = (int)(t / per_img);
+    if (from.skip(b)) continue;
     const long r = t - (long)b * per_img;
     const int i = (int)(r / W4), j0 = (int)(r - (long)i * W4) * 4;
     const int flags = a.d4 ? a.d4[b] : 0;
@@ -53,8 +79,9 @@ __global__ __launch_bounds__(256) void feed_tiles_kernel(FeedArgs a) {
       src[e] = (long)si * a.W + sj;
     }
     if (a.out) {
+      const unsigned char* tile = from.image(b);
       for (int c = 0; c < a.Cout; ++c) {
-        const unsigned char* p = a.img + ((long)b * a.Cb + a.band[c]) * HW;
+        const unsigned char* p = tile + (long)a.band[c] * HW;
         const double m = a.mean[c], sd = a.stdv[c];
         float4 o;
         o.x = norm_byte(a.mode, p[src[0]], m, sd);
@@ -64,8 +91,8 @@ __global__ __launch_bounds__(256) void feed_tiles_kernel(FeedArgs a) {
         *reinterpret_cast<float4*>(a.out + ((long)b * a.Cout + c) * HW + (long)i * a.W + j0) = o;
       }
     }
-    if (a.labels) {
-      const unsigned char* p = a.msk + (long)b * HW;
+    const unsigned char* p = a.labels ? from.mask(b) : nullptr;
+    if (p) {
       unsigned int packed = 0;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -223,20 +250,39 @@ inline int stream_blocks(long items) {
   return (int)(b < 1 ? 1 : b);
 }
 
+// what a feed launch asks of its shapes, wherever its samples lie; have_img / have_msk: the launch has image / mask sources
+bool feed_shapes_ok(const FeedArgs& a, bool have_img, bool have_msk) {
+  if (a.B < 1 || a.H < 1 || a.W < 4 || (a.W & 3) || a.Cout < 0 || a.Cout > FeedArgs::MAXCH || a.mode < 0 || a.mode > 2) return false;
+  if (a.out && (!have_img || a.Cout < 1)) return false;
+  if (a.labels && (!have_msk || a.num_classes < 1 || a.num_classes > 255)) return false;
+  if (a.d4 && a.H != a.W) return false;  // rot90 of a non-square tile changes its shape
+  for (int c = 0; c < a.Cout; ++c)
+    if (a.band[c] < 0 || a.band[c] >= a.Cb) return false;
+  return true;
+}
+
+template <class SRC>
+int launch_feed_tiles(const char* name, const FeedArgs& a, const SRC& from, hipStream_t s) {
+  const long px = (long)a.B * a.H * a.W;
+  ProfScope ps(name, 0.0, (double)px * ((a.out ? 5.0 * a.Cout : 0.0) + (a.labels ? 2.0 : 0.0)), s);
+  hipLaunchKernelGGL(feed_tiles_kernel<SRC>, dim3(stream_blocks(px / 4)), dim3(256), 0, s, a, from);
+  FLAIR_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 int feed_tiles(const FeedArgs& a, hipStream_t s) {
-  if (a.B < 1 || a.H < 1 || a.W < 4 || (a.W & 3) || a.Cout < 0 || a.Cout > FeedArgs::MAXCH || a.mode < 0 || a.mode > 2) return -2;
-  if (a.out && (!a.img || a.Cout < 1)) return -2;
-  if (a.labels && (!a.msk || a.num_classes < 1 || a.num_classes > 255)) return -2;
-  if (a.d4 && a.H != a.W) return -2;  // rot90 of a non-square tile changes its shape
-  for (int c = 0; c < a.Cout; ++c)
-    if (a.band[c] < 0 || a.band[c] >= a.Cb) return -2;
-  const long px = (long)a.B * a.H * a.W;
-  ProfScope ps("feed_tiles", 0.0, (double)px * ((a.out ? 5.0 * a.Cout : 0.0) + (a.labels ? 2.0 : 0.0)), s);
-  hipLaunchKernelGGL(feed_tiles_kernel, dim3(stream_blocks(px / 4)), dim3(256), 0, s, a);
-  FLAIR_CHECK_LAUNCH();
-  return 0;
+  if (!feed_shapes_ok(a, a.img != nullptr, a.msk != nullptr)) return -2;
+  const long HW = (long)a.H * a.W;
+  return launch_feed_tiles("feed_tiles", a, PackedTiles{a.img, a.msk, (long)a.Cb * HW, HW}, s);
+}
+
+int feed_tiles_ptrs(const FeedArgs& a, const unsigned long long* img_ptrs, const unsigned long long* msk_ptrs, hipStream_t s) {
+  if (!img_ptrs || (a.labels && !msk_ptrs)) return -1;
+  if (((uintptr_t)img_ptrs | (uintptr_t)msk_ptrs) & 7) return -2;
+  if (!feed_shapes_ok(a, true, msk_ptrs != nullptr)) return -2;
+  return launch_feed_tiles("feed_tiles_ptrs", a, TilesByAddress{img_ptrs, msk_ptrs}, s);
 }
 
 int detect_convert(const float* logits, int up, int B, int C, int S, int margin, int mode, void* out, const int* tiles, int Hr, int Wr,

@@ -124,6 +124,8 @@ struct FeedArgs {
   double mean[MAXCH], stdv[MAXCH];
 };
 int feed_tiles(const FeedArgs& a, hipStream_t s);
+// a.img / a.msk unused: sample b's (Cb, H, W) planes lie at img_ptrs[b] (0: the sample is skipped), its (H, W) mask at msk_ptrs[b]
+int feed_tiles_ptrs(const FeedArgs& a, const unsigned long long* img_ptrs, const unsigned long long* msk_ptrs, hipStream_t s);
 int gather_tiles(const FeedArgs& a, const int* tiles, int Hr, int Wr, hipStream_t s);  // a.img: one (Cb, Hr, Wr) raster
 int detect_stitch_preds(const unsigned char* preds, const float* maxprob, int B, int S, int margin, const int* tiles, float* out,
                         int Hr, int Wr, hipStream_t s);

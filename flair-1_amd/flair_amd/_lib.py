@@ -50,6 +50,8 @@ PROTOTYPES = {
     "flair_confmat_masks": (i32, [vp, vp, i64, i32, i32, vp, vp]),
     "flair_feed_tiles": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_double),
                                C.POINTER(C.c_double), i32, vp, vp, vp]),
+    "flair_feed_tiles_ptrs": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), i32, vp, vp, vp]),
     "flair_detect_convert": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "flair_gather_tiles": (i32, [vp, i32, i32, i32, vp, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(C.c_double),
                                  C.POINTER(C.c_double), vp, vp]),

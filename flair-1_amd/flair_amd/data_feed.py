@@ -75,14 +75,7 @@ class TileFeed:
             raise ValueError("img_u8 must be (B, bands, H, W) uint8")
         img_u8 = img_u8.contiguous()
         B, bands, H, W = img_u8.shape
-        if max(self.channels) > bands or min(self.channels) < 1:
-            raise ValueError(f"channels {self.channels} outside the raster's 1..{bands} bands")
-        if d4 is None and self.use_augmentations:
-            d4 = draw_d4(B, self.generator)
-        if d4 is not None:
-            d4 = d4.to(device=img_u8.device, dtype=torch.uint8).contiguous()
-            if d4.numel() != B:
-                raise ValueError("d4 needs one draw per sample")
+        d4 = self._draws(B, bands, d4, img_u8.device)
         out = torch.empty(B, len(self.channels), H, W, dtype=torch.float32, device=img_u8.device)
         labels = None
         if msk_raw is not None:
@@ -94,6 +87,48 @@ class TileFeed:
                                          L.ptr(d4) if d4 is not None else None, B, bands, H, W, self._ch, len(self.channels),
                                          NORM_CODES[self.norm_type], self._means, self._stds, self.num_classes, L.ptr(out),
                                          L.ptr(labels) if labels is not None else None, L.stream()), "flair_feed_tiles")
+        return self._batch(out, labels, mtd, ids)
+
+    def from_sources(self, img_ptrs: torch.Tensor, msk_ptrs: torch.Tensor | None, shape, d4: torch.Tensor | None = None,
+                     mtd: torch.Tensor | None = None, ids=None, keep=()) -> dict:
+        """The batch dict of ``__call__`` for samples that do not lie in one tensor (tile_cache.py): ``img_ptrs`` and ``msk_ptrs``
+        are (B,) int64 device tensors of device addresses, entry b that of sample b's (bands, H, W) uint8 planes and of its (H, W)
+        raw mask (``msk_ptrs`` None: no labels), ``shape`` = (B, bands, H, W).  The same checks, the same one ``draw_d4(B)`` per
+        batch.  ``keep``: the tensors the addresses point into that the caller is about to let go; each is marked as used on the
+        current stream, so that its memory outlives the launch."""
+        B, bands, H, W = (int(v) for v in shape)
+        if not img_ptrs.is_cuda:
+            raise RuntimeError("TileFeed needs device tensors (no CPU fallback)")
+        for name, t in (("img_ptrs", img_ptrs), ("msk_ptrs", msk_ptrs)):
+            if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != (B,) or t.device != img_ptrs.device):
+                raise ValueError(f"{name} must hold (B,) int64 device addresses on the image table's device")
+        dev = img_ptrs.device
+        d4 = self._draws(B, bands, d4, dev)
+        out = torch.empty(B, len(self.channels), H, W, dtype=torch.float32, device=dev)
+        labels = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if msk_ptrs is not None else None
+        L.check(L.lib().flair_feed_tiles_ptrs(L.ptr(img_ptrs), L.ptr(msk_ptrs), L.ptr(d4) if d4 is not None else None, B, bands, H, W,
+                                              self._ch, len(self.channels), NORM_CODES[self.norm_type], self._means, self._stds,
+                                              self.num_classes, L.ptr(out), L.ptr(labels), L.stream()), "flair_feed_tiles_ptrs")
+        for t in keep:
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+        return self._batch(out, labels, mtd, ids)
+
+    def _draws(self, B: int, bands: int, d4, device):
+        """what both entries check and draw per batch: the channels against the bands, and the D4 flags (given, or one ``draw_d4(B)``
+        when augmenting, or None) on ``device``"""
+        if max(self.channels) > bands or min(self.channels) < 1:
+            raise ValueError(f"channels {self.channels} outside the raster's 1..{bands} bands")
+        if d4 is None and self.use_augmentations:
+            d4 = draw_d4(B, self.generator)
+        if d4 is not None:
+            d4 = d4.to(device=device, dtype=torch.uint8).contiguous()
+            if d4.numel() != B:
+                raise ValueError("d4 needs one draw per sample")
+        return d4
+
+    @staticmethod
+    def _batch(out, labels, mtd, ids) -> dict:
         batch = {"img": out}
         if mtd is not None:
             batch["mtd"] = mtd.to(device=out.device, dtype=torch.float32)

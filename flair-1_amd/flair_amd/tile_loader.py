@@ -4,7 +4,8 @@ Here the IMG and MSK files of a whole batch are read into one pinned buffer, go 
 of ``ops.tiff_lzw_decode_chunks`` per kind (stored and LZW chunks, tiles and strips, one wave per chunk) and scattered by one launch
 of ``ops.tiff_chunks_to_batch`` (csrc/tiff_read.hip) into the ``(B, bands, H, W)`` and ``(B, H, W)`` uint8 tensors ``TileFeed`` takes.
 Only the files' bytes cross PCIe.  ``TileLoader`` begins batch n + 1 before it hands out batch n, so the host's file reads and the
-upload run under the caller's step.
+upload run under the caller's step.  With ``cache_bytes`` the decoded tiles stay in HBM (``tile_cache.py``) and later epochs are fed
+from there.
 
 The files are those ``raster_reader.raster_layout`` accepts, and they may differ in layout inside a batch.  There is no fallback
 reader: a file outside the family is refused by name (``UnsupportedRaster``) before any device work.
@@ -20,6 +21,7 @@ import torch
 
 from .raster_reader import FLUSH_BLOCK, RasterLayout, UnsupportedRaster, raise_if_failed, raster_layout
 from .tiff_staging import GROUP_BYTES, PinnedPair, stream_groups
+from .tile_cache import TileCache
 
 READ_THREADS = 16   # file reads of a batch in flight; a fixed number, whatever the machine's CPU count
 
@@ -267,11 +269,21 @@ class TileLoader:
     ``gather_paths`` makes it: iterating yields the batch dicts of ``fit_dataset`` (``img`` fp32 NCHW, ``msk`` as class indices,
     ``mtd``) or, without 'MSK', of ``predict_dataset`` (``img``, ``mtd``, ``id`` the image paths), made by ``feed`` (a ``TileFeed``)
     from the files' bytes on ``device``.  Batch n + 1 is begun (read, uploaded, decode queued) before batch n is yielded; every
-    yielded batch owns its tensors."""
+    yielded batch owns its tensors.
+
+    ``cache_bytes`` > 0 keeps the decoded uint8 tiles in HBM (``tile_cache.TileCache``, at most that many bytes; ``feed`` must then
+    have ``TileFeed.from_sources``): an item is read and decoded the first time it is asked for, copied into a slot when its batch
+    has finished cleanly, and fed from the slot ever after, without a look at its files; items that find no free slot are decoded
+    every time.  ``cache_stats`` counts it, ``cache.clear()`` (between epochs) forgets every item.  A slot is assigned when a job
+    begins and committed when its batch is yielded; the slots of a batch that raised, or that was begun and never yielded because
+    the caller left the loop, are free again, and one iteration over a loader at a time is all a cache supports.  Stream rule: the
+    slabs are written and read only on the stream that is current when a batch is finished (inside ``next()``), so the writes of
+    a slot and all later reads of it are in stream order; a caller that iterates under changing streams must synchronise them
+    itself."""
 
     def __init__(self, dict_files: dict, feed, batch_size: int = 2, shuffle: bool = False, drop_last: bool = False,
                  generator: torch.Generator | None = None, device="cuda", use_metadata: bool | None = None,
-                 group_bytes: int = GROUP_BYTES):
+                 group_bytes: int = GROUP_BYTES, cache_bytes: int = 0):
         self.imgs = [os.fspath(p) for p in dict_files["IMG"]]
         self.msks = [os.fspath(p) for p in dict_files["MSK"]] if dict_files.get("MSK") is not None and len(dict_files["MSK"]) else None
         if self.msks is not None and len(self.msks) != len(self.imgs):
@@ -285,43 +297,139 @@ class TileLoader:
                 raise ValueError(f"'MTD' must hold one vector per image, got {tuple(self.mtd.shape)} for {len(self.imgs)} images")
         self.feed, self.batch_size, self.shuffle, self.drop_last = feed, int(batch_size), bool(shuffle), bool(drop_last)
         self.generator, self.device, self.group_bytes = generator, torch.device(device), group_bytes
+        self.cache = None
+        if int(cache_bytes) < 0:
+            raise ValueError(f"cache_bytes must not be negative, got {cache_bytes}")
+        if int(cache_bytes) > 0:
+            if not hasattr(feed, "from_sources"):
+                raise TypeError("a tile cache feeds batches through feed.from_sources (TileFeed), which this feed does not have")
+            self.cache = TileCache(len(self.imgs), int(cache_bytes), self.device)
 
     @classmethod
-    def from_config(cls, config: dict, dict_files: dict, split: str, device="cuda", generator=None) -> "TileLoader":
+    def from_config(cls, config: dict, dict_files: dict, split: str, device="cuda", generator=None,
+                    cache_bytes: int | None = None) -> "TileLoader":
         """The loader of ``split`` ('train' | 'val' | 'predict') as data_module.py:79-104 and tasks_utils.get_data_module set it:
         config['batch_size'] shuffled (train) or in file order (val), both with drop_last=True; predict: one tile a batch, in file
-        order, nothing dropped."""
+        order, nothing dropped.  ``cache_bytes`` as in the constructor; not given, it is the environment's ``FLAIR_TILE_CACHE_GB``
+        (gigabytes of 10^9 bytes, fractions allowed) or 0."""
         from .data_feed import TileFeed
         if split not in ("train", "val", "predict"):
             raise ValueError(f"split must be 'train', 'val' or 'predict', got {split!r}")
+        if cache_bytes is None:
+            cache_bytes = int(float(os.environ.get("FLAIR_TILE_CACHE_GB") or 0) * 1e9)
         feed = TileFeed.from_config(config, train=split == "train", generator=generator)
         fit = split != "predict"
         files = dict_files if fit else {k: v for k, v in dict_files.items() if k != "MSK"}
         return cls(files, feed, batch_size=config["batch_size"] if fit else 1, shuffle=split == "train", drop_last=fit,
-                   generator=generator, device=device, use_metadata=bool(config.get("use_metadata", False)))
+                   generator=generator, device=device, use_metadata=bool(config.get("use_metadata", False)), cache_bytes=cache_bytes)
+
+    @property
+    def cache_stats(self):
+        """{'hits', 'misses', 'files_read', 'resident', 'capacity'} counted per item (``files_read`` per file) since construction or
+        ``cache.clear()``; None without a cache"""
+        return None if self.cache is None else self.cache.stats
 
     def __len__(self) -> int:
         n = len(self.imgs)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def _begin(self, idx):
+        if self.cache is not None:
+            return self._begin_cached(idx)
         job = begin_read_tiles([self.imgs[i] for i in idx], None if self.msks is None else [self.msks[i] for i in idx], self.device,
                                self.group_bytes)
         return idx, job
 
     def _finish(self, pending) -> dict:
+        if self.cache is not None:
+            return self._finish_cached(pending)
         idx, job = pending
         img_u8, msk_raw = finish_read_tiles(job)
         with torch.cuda.device(self.device):
             return self.feed(img_u8, msk_raw, mtd=None if self.mtd is None else self.mtd[idx],
                              ids=[self.imgs[i] for i in idx] if self.msks is None else None)
 
+    def _begin_cached(self, idx):
+        """(idx, slots of the resident items (-1: absent), positions of the absent ones, the slots those were assigned (-1: none left),
+        their job or None): only the absent items are read and decoded, and a batch without one queues nothing"""
+        cache = self.cache
+        slots = cache.lookup(idx)
+        absent = np.flatnonzero(slots < 0)
+        if not len(absent):
+            return idx, slots, absent, np.empty(0, dtype=np.int64), None
+        items = [idx[p] for p in absent]
+        job = begin_read_tiles([self.imgs[i] for i in items], None if self.msks is None else [self.msks[i] for i in items], self.device,
+                               self.group_bytes)
+        cache.files_read += len(items) * (1 if self.msks is None else 2)
+        plan = job.kinds[0][1]
+        if not cache.is_open:    # the first batch: the shape of an item, and with it the capacity, is known now
+            with torch.cuda.device(self.device):
+                cache.allocate(plan.bands, plan.H, plan.W, self.msks is not None)
+        elif (plan.bands, plan.H, plan.W) != cache.shape:
+            raise ValueError(f"{_label(self.imgs, items[0])} is {plan.bands} x {plan.H} x {plan.W} (bands x H x W), not "
+                             f"{cache.shape[0]} x {cache.shape[1]} x {cache.shape[2]} like the cached tiles: a cache holds one shape")
+        return idx, slots, absent, np.asarray(cache.assign(items), dtype=np.int64), job
+
+    def _finish_cached(self, pending) -> dict:
+        idx, slots, absent, assigned, job = pending
+        cache = self.cache
+        items = [idx[p] for p in absent]
+        mtd = None if self.mtd is None else self.mtd[idx]
+        ids = [self.imgs[i] for i in idx] if self.msks is None else None
+        try:
+            img_u8 = msk_raw = None
+            if job is not None:
+                img_u8, msk_raw = finish_read_tiles(job)    # a failed chunk raises here: nothing of the batch has reached a slab
+            with torch.cuda.device(self.device):
+                if len(absent) == len(idx) and not (assigned >= 0).any():   # nothing of the batch is or becomes resident: as without a cache
+                    return self.feed(img_u8, msk_raw, mtd=mtd, ids=ids)
+                B, (bands, H, W) = len(idx), cache.shape
+                kept = np.flatnonzero(assigned >= 0)       # the rows of the job's tensors that go into a slot
+                slots = slots.copy()
+                slots[absent] = assigned
+                in_slab = slots >= 0
+                # [image addresses (B) | mask addresses (B) | slots of the kept rows | the kept rows], up from pinned memory in one copy
+                table = torch.empty(2 * B + 2 * len(kept), dtype=torch.int64, pin_memory=True)
+                t = table.numpy()
+                t[:2 * B] = 0
+                img_at, msk_at = cache.addresses(slots[in_slab])
+                t[:B][in_slab] = img_at
+                if msk_at is not None:
+                    t[B:2 * B][in_slab] = msk_at
+                loose = assigned < 0                        # decoded and without a slot: fed from the job's own tensors
+                if loose.any():
+                    rows = np.flatnonzero(loose)
+                    t[:B][absent[loose]] = img_u8.data_ptr() + rows * (bands * H * W)
+                    if msk_raw is not None:
+                        t[B:2 * B][absent[loose]] = msk_raw.data_ptr() + rows * (H * W)
+                t[2 * B:2 * B + len(kept)] = assigned[kept]
+                t[2 * B + len(kept):] = kept
+                d = table.to(self.device, non_blocking=True)
+                if len(kept):
+                    whole = len(kept) == len(absent)
+                    rows_d = d[2 * B + len(kept):]
+                    cache.store(d[2 * B:2 * B + len(kept)], img_u8 if whole else img_u8.index_select(0, rows_d),
+                                msk_raw if whole or msk_raw is None else msk_raw.index_select(0, rows_d))
+                batch = self.feed.from_sources(d[:B], None if self.msks is None else d[B:2 * B], (B, bands, H, W), mtd=mtd, ids=ids,
+                                               keep=(img_u8, msk_raw))
+        except BaseException:
+            cache.release(items)
+            raise
+        cache.commit(items)
+        return batch
+
     def __iter__(self):
+        if self.cache is not None:
+            self.cache.abandon()      # jobs of an earlier iteration that were begun and never finished
         pending = None
-        for idx in epoch_batches(len(self.imgs), self.batch_size, self.shuffle, self.drop_last, self.generator):
-            job = self._begin(idx)
+        try:
+            for idx in epoch_batches(len(self.imgs), self.batch_size, self.shuffle, self.drop_last, self.generator):
+                job = self._begin(idx)
+                if pending is not None:
+                    yield self._finish(pending)
+                pending = job
             if pending is not None:
                 yield self._finish(pending)
-            pending = job
-        if pending is not None:
-            yield self._finish(pending)
+        finally:
+            if self.cache is not None:
+                self.cache.abandon()

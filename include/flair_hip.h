@@ -185,6 +185,16 @@ int flair_jaccard(const int64_t* confmat, int C, float* per_class, float* weight
 int flair_feed_tiles(const uint8_t* img_u8, const uint8_t* msk_raw, const uint8_t* d4_flags, int B, int bands, int H, int W,
                      const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
                      int num_classes, float* img_out, uint8_t* labels_out, void* stream);
+/* flair_feed_tiles over samples that do not lie one behind the other (flair_amd/tile_cache.py: tiles resident in cache slots next
+ * to tiles a decode just wrote): the same arithmetic, the sources from two device tables of B 64-bit device addresses each.
+ *   img_ptrs[b]: sample b's (bands, H, W) uint8 planes, contiguous, any byte alignment; 0: the sample is skipped, nothing of its
+ *     img_out / labels_out is written
+ *   msk_ptrs[b]: its (H, W) raw mask; msk_ptrs may be null without labels_out; an entry 0 leaves the sample's labels unwritten
+ * The same address may stand for several samples.  The other arguments and their checks are flair_feed_tiles'.
+ * Returns -1 for a null img_ptrs and for labels_out without msk_ptrs, -2 for a table that is not 8-byte aligned. */
+int flair_feed_tiles_ptrs(const uint64_t* img_ptrs, const uint64_t* msk_ptrs, const uint8_t* d4_flags, int B, int bands, int H, int W,
+                          const int* channels, int n_channels, int norm_type, const double* means, const double* stds,
+                          int num_classes, float* img_out, uint8_t* labels_out, void* stream);
 /* zone_detect: softmax over classes (src/zone_detect/compare.py:35), margin crop (compare.py:71-75) and
  * convert (src/zone_detect/dataset.py:11-34) without the probability tensor ever leaving the device.
  * output_type 0 'argmax': out fp32 (B, 2, S-2m, S-2m) = [first argmax, max probability];
