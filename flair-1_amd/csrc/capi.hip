@@ -662,6 +662,62 @@ int flair_bn_backward_ex(const flair_bn_bwd_ex_t* p, void* workspace, size_t wsb
                      p->premasked, (hipStream_t)stream);
 }
 
+static size_t bwd16_ex_pack_bytes() { return (size_t)round_up(16L * conv_kpad(DT_BF16, 9 * 16) * 2, 256); }
+
+// the separate weight gradient of the same layer: its grid is the fused kernel's default
+static void bwd16_ex_wgrad(const flair_bwd16_ex_t* p, WgradArgs& w) {
+  wgrad_args(w, ConvInput{p->x, nullptr, 16, 0, 0, p->N, p->H, p->W}, 3, 1, 1, p->g, 16, p->Cout, p->dw, 16);
+  w.in_scale = p->in_scale; w.in_shift = p->in_shift;
+}
+
+size_t flair_bwd16_ex_workspace_bytes(const flair_bwd16_ex_t* p) {
+  if (!p || p->N < 1 || p->H < 1 || p->W < 1 || (p->H % 8) || (p->W % 32)) return 0;
+  WgradArgs w;
+  bwd16_ex_wgrad(p, w);
+  return bwd16_ex_pack_bytes() + (size_t)round_up((long)bwd16_workspace_bytes(bwd16_grid(w)), 256) +
+         (size_t)round_up((long)WGRAD_DBIAS_ROWS * 16 * 4, 256) + 256;
+}
+
+int flair_bwd16_ex_grid_rows(const flair_bwd16_ex_t* p) {
+  if (!p || p->N < 1 || p->H < 1 || p->W < 1) return -1;
+  if ((p->H % 8) || (p->W % 32)) return -2;
+  WgradArgs w;
+  bwd16_ex_wgrad(p, w);
+  return bwd16_grid(w);
+}
+
+int flair_bwd16_ex(const flair_bwd16_ex_t* p, void* workspace, size_t wsb, void* stream) {
+  if (!p || !p->g || !p->x || !p->in_scale || !p->in_shift || !p->w_oihw || !p->dx || !p->bnr_scale || !p->bnr_shift || !p->bnr_partial ||
+      !p->dw || !workspace || p->N < 1 || p->H < 1 || p->W < 1)
+    return -1;
+  if (p->gy && (!p->gcoef || !p->gmsc || !p->gmsh || p->dbias)) return -1;
+  if (p->Cout < 1 || p->Cout > 16 || (p->H % 8) || (p->W % 32)) return -2;
+  hipStream_t s = (hipStream_t)stream;
+  WgradArgs w;
+  bwd16_ex_wgrad(p, w);
+  const int grid = bwd16_grid(w);
+  if (p->bnr_rows < grid) return -100;
+  OpArena ar(workspace, wsb);
+  const int Kpad = conv_kpad(DT_BF16, 9 * 16);
+  void* wp = ar.get((size_t)16 * Kpad * 2);
+  Bwd16Args f;
+  memset(&f, 0, sizeof(f));
+  f.slabs = (float*)ar.get(bwd16_workspace_bytes(grid));
+  f.grid = grid;
+  if (p->dbias) f.dbias_partial = (float*)ar.get((size_t)WGRAD_DBIAS_ROWS * 16 * 4);
+  if (ar.bad) return -100;
+  // the forward layer's [Cout][16][3][3] as the flipped / transposed data-gradient pack, 16 rows of 9 x 16 (padded) gradient channels
+  const int rc = pack_weight(DT_BF16, p->w_oihw, wp, p->Cout, 16, 3, 3, 16, 16, Kpad, 1, s);
+  if (rc) return rc;
+  f.g = p->g; f.gy = p->gy; f.gcoef = p->gcoef; f.gmsc = p->gmsc; f.gmsh = p->gmsh;
+  f.x = p->x; f.in_scale = p->in_scale; f.in_shift = p->in_shift;
+  f.w = wp; f.Kpad = Kpad; f.dx = p->dx;
+  f.bnr_scale = p->bnr_scale; f.bnr_shift = p->bnr_shift; f.bnr_partial = p->bnr_partial; f.bnr_C = 16; f.bnr_cols = grid;
+  f.dw = p->dw; f.Cout = p->Cout; f.Cin_real = 16; f.dbias = p->dbias;
+  f.N = p->N; f.H = p->H; f.W = p->W;
+  return launch_bwd16(f, s);
+}
+
 int flair_maxpool_backward_ex(int dtype, const void* dy, const uint8_t* idx, void* dx, int accumulate, int N, int H, int W, int C,
                               const void* bnr_y, const float* bnr_msc, const float* bnr_msh, float* bnr_partial, void* stream) {
   if (!dy || !idx || !dx || N < 1 || H < 1 || W < 1 || C < 1) return -1;

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "bwd_halo16.h"
 #include "ops.h"
 
 namespace flair {
@@ -200,6 +201,9 @@ class UNet {
   int sole_producer(const Act& a) const;
   int residual_producer(const Act& a) const;
   void attach_bn_reduce(ConvArgs& a, const Act& target);
+  // the fused backward of a 16 -> 16 layer (bwd16_fusable): `a` / `w` as the separate path would launch them, x the layer input
+  bool bwd16_ok(int flavour, const ConvArgs& a, const WgradArgs& w, const Act& x) const;
+  void bwd16_run(Bwd16Args& f, const ConvArgs& a, const WgradArgs& w, const Act& x);
   std::vector<GradBuf> gbufs_;
   // set by the BasicBlock walk just before the backward of a block's conv1: its data gradient adds this tensor (the masked
   // gradient of the block's output = the identity branch's share) instead of reading a copy of it from its own output buffer
@@ -211,6 +215,7 @@ class UNet {
   void* grad_peek(const Act& a);
 
   size_t plan_bytes(int B, int H, int W, int training);   // the dry run itself (clobbers per-call state)
+  size_t plan_step_bytes(int B, int H, int W);            // the same for forward(training) + backward() as they run (training == 2)
   void build_table();
   int add_conv(const std::string& name, int cin, int cout, int k, int stride, int pad, bool bias, int stage);
   int add_bn(const std::string& name, int c, int stage);

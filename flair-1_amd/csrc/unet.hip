@@ -642,7 +642,6 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   const ConvDesc& c = convs[u.conv];
   const BnDesc& b = bns[u.bn];
   const long rows = u.y.rows();
-  void* dy = alloc((size_t)u.y.elems() * dtype_size(dtype));
   const int pre_nblk = u.bnr_nblk;
   const bool masked = u.bnr_masked && pre_nblk > 0;
   float* partial = pre_nblk > 0 ? u.bnr_partial : alloc_f((long)bn_bwd_blocks(rows) * 2 * b.C);
@@ -653,6 +652,12 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   // ReLU mask: units without a residual recompute it from y (out > 0 <=> y*scale + shift > 0) and skip
   // reading the activation tensor in both backward passes
   const bool mask_from_y = u.relu && u.res_unit < 0 && !u.res.p;
+  // A 16 -> 16 unit whose backward may run as ONE kernel (bwd_halo16.hip), which forms dy while it stages dz and y: no dy tensor
+  // then.  Decided below (bwd16_fusable), once the data gradient is described; until then dout stands in for dy in the descriptors
+  const bool cand16 = dtype == DT_BF16 && need_dgrad && !dres && !upcat && !dx_override && mask_from_y && pre_nblk > 0 && !masked &&
+                      !acc_src && c.R == 3 && c.stride == 1 && c.pad == 1 && u.y.C == 16 && b.C == 16 && c.Cin_p == 16 && !u.in1.p &&
+                      !u.up0 && u.in0.lz_scale;
+  void* dy = cand16 ? const_cast<void*>(dout) : alloc((size_t)u.y.elems() * dtype_size(dtype));
   // weight gradient (described first: a unit without a data gradient may fold the BatchNorm-backward apply into it)
   WgradArgs w;
   wgrad_args(w, conv_input(u.in0, u.in1, u.up0), c.R, c.stride, c.pad, dy, u.y.C, c.Cout, grads_ + c.w_off, c.Cin);
@@ -723,15 +728,27 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
       }
     }
   }
+  w.in_scale = u.in0.lz_scale; w.in_shift = u.in0.lz_shift;
+  const bool fuse16 = cand16 && dg == DG_PLAIN && bwd16_ok(BWD16_UNIT, a, w, u.in0);
+  if (cand16 && !fuse16) {   // the separate kernels after all: they need the tensor
+    dy = alloc((size_t)u.y.elems() * dtype_size(dtype));
+    w.dy = dy; a.src0 = dy;
+  }
   // a masked gradient needs no mask source in the apply pass: the residual units' read of `out` and the others' recomputation
   // of relu'(y) go (bn_backward still needs one on paper when it runs the reduction itself, which it does not here: pre_nblk > 0)
   const bool nomask = masked && !dres && bwd_fuse();
   RUN(bn_backward(dtype, dout, (u.relu && !mask_from_y && !nomask) ? u.out.p : nullptr, u.y.p, u.mean, u.invstd, params_ + b.g_off,
-                  rows, b.C, partial, coef, grads_ + b.g_off, grads_ + b.b_off, 0, fuse_apply ? nullptr : dy, dres,
+                  rows, b.C, partial, coef, grads_ + b.g_off, grads_ + b.b_off, 0, (fuse_apply || fuse16) ? nullptr : dy, dres,
                   dres_acc ? 1 : 0, (mask_from_y && !nomask) ? u.scale : nullptr, (mask_from_y && !nomask) ? u.shift : nullptr,
                   pre_nblk, nomask ? 1 : 0, s_));
+  if (fuse16) {   // bn_backward above ran the finalize only: the kernel applies k1*dz*m + k2*y + k3 itself
+    Bwd16Args f;
+    memset(&f, 0, sizeof(f));
+    f.g = dout; f.gy = u.y.p; f.gcoef = coef; f.gmsc = u.scale; f.gmsh = u.shift;
+    bwd16_run(f, a, w, u.in0);
+    return;
+  }
   if (fuse_apply) { w.dy = dout; w.fuse_y = u.y.p; w.fuse_coef = coef; w.fuse_msc = u.scale; w.fuse_msh = u.shift; }
-  w.in_scale = u.in0.lz_scale; w.in_shift = u.in0.lz_shift;
   w.cus = side_cus();
   w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
   {
@@ -749,25 +766,58 @@ void UNet::unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bo
   }
 }
 
+// The fused backward of a 16 -> 16 layer (bwd_halo16.hip) in place of its data-gradient, weight-gradient and (unit flavour)
+// BatchNorm-backward apply launches.  It carries the data gradient, so it runs on the caller's stream, and the slab reduce follows
+// it there: the weight gradient is complete on s_ and the side stream is not touched.
+// bwd16_fusable, and the fused kernel forms every per-workgroup sum as the separate kernels would: its grid is the separate weight
+// gradient's, and the partial columns the separate data gradient was sized for (attach_bn_reduce) are that grid's or one per tile.
+// Where the two separate grids disagree the layer keeps its three kernels, unless FLAIR_BWD16_WGS asks for a grid of its own.
+bool UNet::bwd16_ok(int flavour, const ConvArgs& a, const WgradArgs& w, const Act& x) const {
+  if (!bwd16_fusable(dtype, flavour, a, w)) return false;
+  if (tune("FLAIR_BWD16_WGS", 0) > 0) return true;
+  const int p = sole_producer(x);
+  if (p < 0) return false;
+  const int nblk = units_[p].bnr_nblk, grid = bwd16_grid(w);
+  if (nblk == grid || nblk == (long)a.N * a.Hout * a.Wout / 256) return true;
+  // the two separate kernels' occupancy answers disagree (another compiler or runtime): the layer keeps its three kernels, and says so
+  // once, since a speed-up that turns itself off silently is a regression nobody sees (tests/test_gpu_bwd16_fuse.py runs a step at
+  // default grids above the grid size and asserts that the fused kernels are in it)
+  static bool told = false;
+  if (!told && !dry_) {
+    told = true;
+    fprintf(stderr, "flair: fused 16-channel backward not used: the data gradient's %d partial columns are not the weight gradient's grid "
+                    "of %d workgroups (FLAIR_BWD16_WGS overrides)\n", nblk, grid);
+  }
+  return false;
+}
+
+void UNet::bwd16_run(Bwd16Args& f, const ConvArgs& a, const WgradArgs& w, const Act& x) {
+  const int p = sole_producer(x);   // attach_bn_reduce found it
+  if (p < 0) { if (!err_) err_ = -6; return; }
+  Unit& up = units_[p];
+  // the reduction's partial columns: one per workgroup of THIS kernel; one per tile where the separate data gradient would have run
+  // one tile per workgroup (small inputs) keeps that layout
+  const int grid = bwd16_grid(w);
+  const long ntiles = (long)a.N * a.Hout * a.Wout / 256;
+  // (only under FLAIR_BWD16_WGS: by default bwd16_ok() has seen to it that the columns attach_bn_reduce sized are these)
+  if (up.bnr_nblk != grid && up.bnr_nblk != ntiles) { up.bnr_partial = alloc_f((long)grid * 2 * up.y.C); up.bnr_nblk = grid; }
+  f.x = x.p; f.in_scale = w.in_scale; f.in_shift = w.in_shift;
+  f.w = a.w; f.Kpad = a.Kpad; f.dx = a.out;
+  f.bnr_scale = a.bnr_scale; f.bnr_shift = a.bnr_shift; f.bnr_partial = up.bnr_partial; f.bnr_C = a.bnr_C; f.bnr_cols = up.bnr_nblk;
+  f.slabs = (float*)alloc(bwd16_workspace_bytes(grid));
+  f.grid = grid;
+  f.dw = w.dw; f.Cout = w.Cout; f.Cin_real = w.Cin_real;
+  f.N = a.N; f.H = a.Hout; f.W = a.Wout;
+  RUN(launch_bwd16(f, s_));
+}
+
 void UNet::head_bwd_impl(const void* dl) {
   const ConvDesc& c = convs.back();
   Act none;
   WgradArgs w;
   wgrad_args(w, conv_input(dec_out_, none, false), c.R, c.stride, c.pad, dl, c.Cout_p, c.Cout, grads_ + c.w_off, c.Cin);
   w.in_scale = dec_out_.lz_scale; w.in_shift = dec_out_.lz_shift;
-  w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
-  // bias gradient = column sums of dl: inside the weight-gradient kernel where it stages dl anyway, else a pass of its own
-  const bool fuse_db = wgrad_dbias_fusable(dtype, w);
-  if (fuse_db) { w.dbias = grads_ + c.b_off; w.dbias_partial = alloc_f((long)WGRAD_DBIAS_ROWS * c.Cout_p); }
-  {
-    hipStream_t ws = wgrad_stream();
-    RUN(launch_wgrad(dtype, w, ws));
-  }
-  if (!fuse_db) {
-    const long rows = dec_out_.rows();
-    float* partial = alloc_f((long)bn_bwd_blocks(rows) * c.Cout_p);
-    RUN(colsum(dtype, dl, rows, c.Cout_p, c.Cout, partial, grads_ + c.b_off, s_));
-  }
+  // the data gradient, described before anything is launched
   ConvArgs a;
   conv_dgrad_args(a, dtype, ConvInput{dl, nullptr, c.Cout_p, 0, 0, dec_out_.N, dec_out_.H, dec_out_.W}, c.R, c.stride, c.pad, dec_out_.H,
                   dec_out_.W, c.Cin_p);
@@ -776,7 +826,26 @@ void UNet::head_bwd_impl(const void* dl) {
   a.out = grad_of(dec_out_, &acc);
   a.out_ld = c.Cin_p; a.accumulate = acc ? 1 : 0;
   attach_bn_reduce(a, dec_out_);
-  RUN(launch_conv(dtype, a, s_));
+  // bias gradient = column sums of dl: inside the weight-gradient kernel where it stages dl anyway, else a pass of its own
+  const bool fuse_db = wgrad_dbias_fusable(dtype, w);
+  const bool fuse16 = bwd16_ok(BWD16_HEAD, a, w, dec_out_);
+  if (fuse_db) { w.dbias = grads_ + c.b_off; w.dbias_partial = alloc_f((long)WGRAD_DBIAS_ROWS * c.Cout_p); }
+  if (fuse16) {
+    Bwd16Args f;
+    memset(&f, 0, sizeof(f));
+    f.g = dl; f.dbias = w.dbias; f.dbias_partial = w.dbias_partial;
+    bwd16_run(f, a, w, dec_out_);
+  } else {
+    w.partial = (float*)alloc(wgrad_workspace_bytes(dtype, w));
+    hipStream_t ws = wgrad_stream();
+    RUN(launch_wgrad(dtype, w, ws));
+  }
+  if (!fuse_db) {
+    const long rows = dec_out_.rows();
+    float* partial = alloc_f((long)bn_bwd_blocks(rows) * c.Cout_p);
+    RUN(colsum(dtype, dl, rows, c.Cout_p, c.Cout, partial, grads_ + c.b_off, s_));
+  }
+  if (!fuse16) RUN(launch_conv(dtype, a, s_));
 }
 
 void UNet::decoder_bwd_impl() {
@@ -971,9 +1040,37 @@ int UNet::encoder_backward(const float* params, const float* const dfeats[5], fl
 // Upper bound of the arena: dry run of the split sequence (superset of the fused one) on a SCRATCH executor, so that
 // sizing a workspace between a training forward and its backward (an eval forward does that) leaves the recorded graph
 // of the live handle alone.
+// training == 2: the arena of the whole-model training step as forward() + backward() run it under the current tune state (lazy
+// BatchNorm, fused 16-channel backward: no dy tensor for the layers that take it) — a tight bound for a caller that runs nothing
+// else on the workspace; training == 0 / 1: the split sequence, the upper bound for every entry point
 size_t UNet::workspace_bytes(int B, int H, int W, int training) const {
   UNet scratch(in_channels, classes, dtype);
-  return scratch.plan_bytes(B, H, W, training);
+  return training == 2 ? scratch.plan_step_bytes(B, H, W) : scratch.plan_bytes(B, H, W, training);
+}
+
+// Dry run of forward(training, no fp32 logits) and backward() in their own order.  Counted whether the call uses them or not: the
+// second bottleneck tensor of a forward with metadata rows, and the NHWC copy backward() makes of an fp32 NCHW logit gradient.
+size_t UNet::plan_step_bytes(int B, int H, int W) {
+  begin(nullptr, 0, nullptr, true);
+  fwd_common_begin(nullptr, nullptr, B, H, W, 1);
+  const int lazy_env = tune("FLAIR_LAZY_BN", 1);
+  lazy_ok_ = lazy_env != 0;
+  lazy_max_c_ = lazy_env >= 2 ? 32 : 16;
+  encoder_fwd_impl(nullptr);
+  alloc_act(f_[5].N, f_[5].H, f_[5].W, f_[5].C);
+  decoder_fwd_impl();
+  head_fwd_impl(nullptr, FwdOpts());
+  alloc((size_t)dec_out_.rows() * convs.back().Cout_p * dtype_size(dtype));
+  grads_ = nullptr;
+  head_bwd_impl(nullptr);
+  decoder_bwd_impl();
+  encoder_bwd_impl();
+  const size_t need = top_ + (1 << 20);
+  dry_ = false;
+  base_ = nullptr;
+  units_.clear();
+  gbufs_.clear();
+  return need;
 }
 
 size_t UNet::plan_bytes(int B, int H, int W, int training) {

@@ -74,6 +74,9 @@ PROTOTYPES = {
     "flair_bn_relu_forward": (i32, [i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, sz, vp]),
     "flair_bn_relu_backward": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]),
     "flair_bn_backward_ex": (i32, [vp, vp, sz, vp]),
+    "flair_bwd16_ex_workspace_bytes": (sz, [vp]),
+    "flair_bwd16_ex_grid_rows": (i32, [vp]),
+    "flair_bwd16_ex": (i32, [vp, vp, sz, vp]),
     "flair_maxpool_backward_ex": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "flair_bn_act": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, vp]),
     "flair_bn_act_maxpool": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -198,6 +201,13 @@ class BnBwdEx(C.Structure):
                 ("rows", i64), ("C", i32), ("partial", vp), ("pre_nblk", i32), ("premasked", i32),
                 ("mscale", vp), ("mshift", vp), ("dgamma", vp), ("dbeta", vp), ("accumulate_param", i32),
                 ("dy", vp), ("dres", vp), ("dres_accumulate", i32), ("coef", vp)]
+
+
+class Bwd16Ex(C.Structure):
+    """flair_bwd16_ex_t"""
+    _fields_ = [("g", vp), ("gy", vp), ("gcoef", vp), ("gmsc", vp), ("gmsh", vp), ("x", vp), ("in_scale", vp), ("in_shift", vp),
+                ("w_oihw", vp), ("Cout", i32), ("N", i32), ("H", i32), ("W", i32), ("dx", vp),
+                ("bnr_scale", vp), ("bnr_shift", vp), ("bnr_partial", vp), ("bnr_rows", i32), ("dw", vp), ("dbias", vp)]
 
 
 class PackDesc(C.Structure):

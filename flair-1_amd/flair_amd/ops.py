@@ -217,6 +217,30 @@ def bn_backward_ex(dout, y, mean, invstd, gamma=None, out=None, mscale=None, msh
     return _ret(r, "bn_backward_ex", {"dy": dy, "dres": dres, "dgamma": dgamma, "dbeta": dbeta, "coef": coef}, rc)
 
 
+def bwd16_ex(g, x, in_scale, in_shift, w, bnr_scale, bnr_shift, gy=None, gcoef=None, gmsc=None, gmsh=None, want_dbias=False, rc=False):
+    """flair_bwd16_ex: the fused backward of a 16 -> <= 16 channel 3x3 layer (bf16 NHWC tensors of 16 channels; w the forward layer's
+    [Cout][16][3][3]).  gy / gcoef / gmsc / gmsh: the unit flavour (g is then the gradient w.r.t. the unit's ReLU output).
+    Returns a dict: dx, dw, dbias (None unless want_dbias), partial [2][16][rows] (the fused BatchNorm-backward sums), rows."""
+    import ctypes as C
+    N, H, W, _ = g.shape
+    dev = g.device
+    Cout = w.shape[0]
+    a = L.Bwd16Ex(g=L.ptr(g), gy=L.ptr(gy), gcoef=L.ptr(gcoef), gmsc=L.ptr(gmsc), gmsh=L.ptr(gmsh), x=L.ptr(x), in_scale=L.ptr(in_scale),
+                  in_shift=L.ptr(in_shift), w_oihw=L.ptr(w), Cout=Cout, N=N, H=H, W=W, bnr_scale=L.ptr(bnr_scale), bnr_shift=L.ptr(bnr_shift))
+    l = L.lib()
+    rows = l.flair_bwd16_ex_grid_rows(C.addressof(a))
+    if rows < 0:
+        return _ret(rows, "bwd16_ex_grid_rows", None, rc)
+    dx = torch.full_like(g, float("nan"))
+    dw = torch.full((Cout, 16, 3, 3), float("nan"), dtype=torch.float32, device=dev)
+    db = torch.full((Cout,), float("nan"), dtype=torch.float32, device=dev) if want_dbias else None
+    part = torch.full((2, 16, rows), float("nan"), dtype=torch.float32, device=dev)
+    a.dx, a.dw, a.dbias, a.bnr_partial, a.bnr_rows = L.ptr(dx), L.ptr(dw), L.ptr(db), L.ptr(part), rows
+    ws = _ws(l.flair_bwd16_ex_workspace_bytes(C.addressof(a)), dev)
+    r = l.flair_bwd16_ex(C.addressof(a), L.ptr(ws), ws.numel(), L.stream())
+    return _ret(r, "bwd16_ex", {"dx": dx, "dw": dw, "dbias": db, "partial": part, "rows": rows}, rc)
+
+
 def maxpool_backward_ex(dy, idx, H, W, dx=None, accumulate=False, bnr_y=None, bnr_msc=None, bnr_msh=None, bnr_partial=None, rc=False):
     """flair_maxpool_backward_ex: dx (+= with accumulate); bnr_partial fp32 [2][C][N * H] receives the fused reduction."""
     N, _, _, Cc = dy.shape

@@ -41,6 +41,10 @@ int flair_unet_num_tensors(const flair_unet_t* h);
 int flair_unet_tensor_info(const flair_unet_t* h, int i, char* name, int name_cap, int64_t shape[4], int* ndim,
                            int64_t* offset, int* kind, int* stage);
 int flair_unet_stage_range(const flair_unet_t* h, int stage, int64_t* begin, int64_t* end);
+/* training = 0 / 1: the bound that holds for every entry point (the split sequence with every activation materialised).
+ * training = 2: the arena of one whole-model training step, flair_unet_forward(training = 1, no fp32 logits) + flair_unet_backward,
+ * as they run under the current flair_tune_set settings: smaller (lazy BatchNorm; no dy tensor for a layer whose backward runs as
+ * the fused 16-channel kernel).  Valid for that pair of calls only, and only while the settings stay what they were. */
 int64_t flair_unet_workspace_bytes(flair_unet_t* h, int B, int H, int W, int training);
 
 /* Options of ONE flair_unet_forward.  The struct is read during the call and nothing of it is kept: what a forward does depends on
@@ -513,6 +517,28 @@ typedef struct flair_bn_bwd_ex {
   float* coef;
 } flair_bn_bwd_ex_t;
 int flair_bn_backward_ex(const flair_bn_bwd_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
+/* The fused backward of a 3x3 / stride-1 / pad-1 convolution with 16 input and <= 16 output channels, bf16 (csrc/bwd_halo16.hip),
+ * as the network launches it for the segmentation head and decoder block 4's second convolution: one kernel for the data gradient
+ * with the BatchNorm-backward sums of the unit that produced the layer input, the weight gradient and (head flavour) the bias
+ * gradient.  All tensors NHWC bf16, 16 channels.
+ *   g: the output gradient [N][H][W][16].  gy != NULL (unit flavour): g is the gradient w.r.t. the unit's ReLU output, gy the unit's
+ *     pre-BatchNorm tensor, and the kernel forms dy = k1 dz + k2 y + k3, dz = g * [gy * gmsc + gmsh > 0], gcoef = k1 | k2 | k3.
+ *   x: the producing unit's pre-BatchNorm tensor; the layer input is relu(x * in_scale + in_shift).
+ *   w_oihw: the forward layer's [Cout][16][3][3]; dx [N][H][W][16]; dw [Cout][16][3][3]; dbias [Cout] (optional, head flavour).
+ *   bnr_partial [2][16][rows], rows = flair_bwd16_ex_grid_rows(): sum(dx * m), sum(dx * m * x), m = [x * bnr_scale + bnr_shift > 0].
+ * -2: H % 8 or W % 32; -100: workspace or bnr_rows too small. */
+typedef struct flair_bwd16_ex {
+  const void* g; const void* gy; const float* gcoef; const float* gmsc; const float* gmsh;
+  const void* x; const float* in_scale; const float* in_shift;
+  const float* w_oihw; int Cout;
+  int N, H, W;
+  void* dx;
+  const float* bnr_scale; const float* bnr_shift; float* bnr_partial; int bnr_rows;
+  float* dw; float* dbias;
+} flair_bwd16_ex_t;
+size_t flair_bwd16_ex_workspace_bytes(const flair_bwd16_ex_t* p);
+int flair_bwd16_ex_grid_rows(const flair_bwd16_ex_t* p);   /* workgroups of the launch under the current flair_tune_set settings */
+int flair_bwd16_ex(const flair_bwd16_ex_t* p, void* workspace, size_t workspace_bytes, void* stream);
 int flair_maxpool_forward(int dtype, const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, void* stream);
 int flair_maxpool_backward(int dtype, const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C,
                            void* stream);
