@@ -366,16 +366,6 @@ int flair_rowvec_grad_nhwc(int dtype, const void* dx, float* dv, int N, int H, i
 }
 
 // ------------------------------------------------------------------------------------------ operators
-struct OpArena {
-  unsigned char* base; size_t cap, top; bool bad;
-  OpArena(void* p, size_t c) : base((unsigned char*)p), cap(c), top(0), bad(false) {}
-  void* get(size_t bytes) {
-    size_t off = top;
-    top = (size_t)round_up((long)(top + bytes), 256);
-    if (top > cap) { bad = true; return base; }
-    return base + off;
-  }
-};
 
 size_t flair_conv2d_workspace_bytes(int dtype, int N, int H, int W, int C0, int C1, int up0, int Cout, int R, int stride,
                                     int pad) {
@@ -410,14 +400,14 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
   if (!x0 || !w_oihw || !dy || !workspace) return -1;
   hipStream_t s = (hipStream_t)stream;
   const int Ho = conv_out_extent(H, R, stride, pad), Wo = conv_out_extent(W, R, stride, pad);
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   int rc = 0;
   if (dx) {
     ConvArgs a;
     conv_dgrad_args(a, dtype, ConvInput{dy, nullptr, Cout, 0, 0, N, Ho, Wo}, R, stride, pad, H, W, Cin);
     const int rows_d = conv_weight_rows_pad(Cin);
     void* wd = ar.get((size_t)rows_d * a.Kpad * dtype_size(dtype));
-    if (ar.bad) return -100;
+    if (ar.err) return ar.err;
     rc = pack_weight(dtype, w_oihw, wd, Cout, Cin, R, R, Cout, rows_d, a.Kpad, 1, s);
     if (rc) return rc;
     a.w = wd; a.out = dx; a.out_ld = Cin;
@@ -428,7 +418,7 @@ int flair_conv2d_backward(int dtype, const void* x0, int N, int H, int W, int Ci
     WgradArgs w;
     wgrad_args(w, ConvInput{x0, nullptr, Cin, 0, 0, N, H, W}, R, stride, pad, dy, Cout, Cout, dw, Cin);
     w.partial = (float*)ar.get(wgrad_workspace_bytes(dtype, w));
-    if (ar.bad) return -100;
+    if (ar.err) return ar.err;
     rc = launch_wgrad(dtype, w, s);
   }
   return rc;
@@ -493,12 +483,12 @@ static size_t conv_ex_parity_packs(const flair_conv_ex_t* p, ConvArgs& a, unsign
   if (!a.ncls) {
     tb.d[tb.n++] = d;
     a.w = base;
-    return (size_t)round_up((long)((size_t)rows_d * a.Kpad * es), 256);
+    return Arena::rounded((size_t)rows_d * a.Kpad * es);
   }
   for (int cls = 0; cls < 4; ++cls) {
     tb.d[tb.n++] = parity_class_pack(d, cls, top, a.cls_kpad[cls]);
     a.cls_w[cls] = base + top;
-    top += (size_t)round_up((long)((size_t)rows_d * a.cls_kpad[cls] * es), 256);
+    top += Arena::rounded((size_t)rows_d * a.cls_kpad[cls] * es);
   }
   a.w = a.cls_w[3];
   return top;
@@ -514,8 +504,8 @@ size_t flair_conv2d_ex_workspace_bytes(const flair_conv_ex_t* p) {
     return conv_ex_parity_packs(p, a, nullptr, tb) + 256;
   }
   a.stats = p->stats;
-  size_t b = (size_t)round_up((long)((size_t)conv_weight_rows_pad(p->Cout) * a.Kpad * dtype_size(p->dtype)), 256);
-  if (p->stats) b += (size_t)round_up((long)conv_grid_rows(p->dtype, a) * 2 * p->Cout * 4, 256);
+  size_t b = Arena::rounded((size_t)conv_weight_rows_pad(p->Cout) * a.Kpad * dtype_size(p->dtype));
+  if (p->stats) b += Arena::rounded((size_t)conv_grid_rows(p->dtype, a) * 2 * p->Cout * 4);
   return b + 256;
 }
 
@@ -545,7 +535,7 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
   }
   // the epilogue reads bnr_y, bnr_scale and bnr_shift unconditionally, and a reduction without a partial has nowhere to go
   if (p->bnr_partial ? (!p->bnr_y || !p->bnr_scale || !p->bnr_shift) : (p->bnr_y != nullptr)) return -1;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   const int Cin = a.C0 + a.C1, rows_f = conv_weight_rows_pad(p->Cout);
   void* wp = ar.get((size_t)rows_f * a.Kpad * dtype_size(p->dtype));
   a.w = wp;
@@ -559,7 +549,7 @@ int flair_conv2d_ex(const flair_conv_ex_t* p, void* workspace, size_t wsb, void*
     partial = (float*)ar.get((size_t)nblk * 2 * p->Cout * 4);
     a.stats = partial;
   }
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   // mode 1: w_oihw is the forward layer's [C0][Cout][R][R]; the data gradient multiplies by its transposed, flipped pack
   rc = p->mode == 1 ? pack_weight(p->dtype, p->w_oihw, wp, Cin, p->Cout, p->R, p->R, Cin, rows_f, a.Kpad, 1, s)
                     : pack_weight(p->dtype, p->w_oihw, wp, p->Cout, Cin, p->R, p->R, Cin, rows_f, a.Kpad, 0, s);
@@ -583,8 +573,8 @@ static int wgrad_ex_fill(const flair_wgrad_ex_t* p, WgradArgs& w) {
 size_t flair_conv2d_wgrad_ex_workspace_bytes(const flair_wgrad_ex_t* p) {
   WgradArgs w;
   if (!p || wgrad_ex_fill(p, w)) return 0;
-  size_t b = (size_t)round_up((long)wgrad_workspace_bytes(p->dtype, w), 256);
-  if (p->dbias && wgrad_dbias_fusable(p->dtype, w)) b += (size_t)round_up((long)WGRAD_DBIAS_ROWS * w.dy_ld * 4, 256);
+  size_t b = Arena::rounded(wgrad_workspace_bytes(p->dtype, w));
+  if (p->dbias && wgrad_dbias_fusable(p->dtype, w)) b += Arena::rounded((size_t)WGRAD_DBIAS_ROWS * w.dy_ld * 4);
   return b + 256;
 }
 
@@ -593,19 +583,19 @@ int flair_conv2d_wgrad_ex(const flair_wgrad_ex_t* p, void* workspace, size_t wsb
   WgradArgs w;
   int rc = wgrad_ex_fill(p, w);
   if (rc) return rc;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   w.partial = (float*)ar.get(wgrad_workspace_bytes(p->dtype, w));
   if (p->dbias && wgrad_dbias_fusable(p->dtype, w)) w.dbias_partial = (float*)ar.get((size_t)WGRAD_DBIAS_ROWS * w.dy_ld * 4);
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   return launch_wgrad(p->dtype, w, (hipStream_t)stream);
 }
 
 // partial block sums + the per-channel coefficient rows of either direction (what the two calls below carve out of `workspace`)
 size_t flair_bn_workspace_bytes(int64_t rows, int C) {
   if (rows < 1 || C < 1) return 0;
-  const size_t partial = (size_t)round_up((long)bn_bwd_blocks(rows) * 2 * C * 4, 256);
-  const size_t fwd = 2 * (size_t)round_up((long)C * 4, 256) + partial + (size_t)round_up(2L * C * 4, 256);
-  const size_t bwd = partial + (size_t)round_up(3L * C * 4, 256);
+  const size_t partial = Arena::rounded((size_t)bn_bwd_blocks(rows) * 2 * C * 4);
+  const size_t fwd = 2 * Arena::rounded((size_t)C * 4) + partial + Arena::rounded((size_t)2 * C * 4);
+  const size_t bwd = partial + Arena::rounded((size_t)3 * C * 4);
   return (fwd > bwd ? fwd : bwd) + 256;
 }
 
@@ -614,7 +604,7 @@ int flair_bn_relu_forward(int dtype, const void* y, int64_t rows, int C, const f
                           void* out, float* save_mean, float* save_invstd, void* workspace, size_t wsb, void* stream) {
   if (!y || !out || !workspace) return -1;
   hipStream_t s = (hipStream_t)stream;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   float* scale = (float*)ar.get(C * 4);
   float* shift = (float*)ar.get(C * 4);
   int rc;
@@ -622,13 +612,13 @@ int flair_bn_relu_forward(int dtype, const void* y, int64_t rows, int C, const f
     const int nblk = bn_bwd_blocks(rows);
     float* partial = (float*)ar.get((size_t)nblk * 2 * C * 4);
     float* zo = (float*)ar.get(2 * C * 4);
-    if (ar.bad) return -100;
+    if (ar.err) return ar.err;
     rc = bn_stats_partial(dtype, y, rows, C, partial, zo, s);
     if (rc) return rc;
     rc = bn_finalize(partial, nblk, C, rows, gamma, beta, running_mean, running_var, 0.1f, 1e-5f, scale, shift,
                      save_mean, save_invstd, s);
   } else {
-    if (ar.bad) return -100;
+    if (ar.err) return ar.err;
     rc = bn_eval_coeffs(C, gamma, beta, running_mean, running_var, 1e-5f, scale, shift, s);
   }
   if (rc) return rc;
@@ -639,10 +629,10 @@ int flair_bn_relu_backward(int dtype, const void* dout, const void* out, const v
                            const float* gamma, const float* save_mean, const float* save_invstd, int relu, void* dy,
                            void* dres, float* dgamma, float* dbeta, void* workspace, size_t wsb, void* stream) {
   if (!dout || !y || !dy || !workspace) return -1;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   float* partial = (float*)ar.get((size_t)bn_bwd_blocks(rows) * 2 * C * 4);
   float* coef = (float*)ar.get(3 * C * 4);
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   return bn_backward(dtype, dout, relu ? out : nullptr, y, save_mean, save_invstd, gamma, rows, C, partial, coef, dgamma,
                      dbeta, 0, dy, dres, 0, nullptr, nullptr, 0, 0, (hipStream_t)stream);
 }
@@ -653,16 +643,16 @@ int flair_bn_backward_ex(const flair_bn_bwd_ex_t* p, void* workspace, size_t wsb
   if (p->dres && !p->dy) return -1;              // the apply pass always writes dy
   if (!p->dgamma != !p->dbeta) return -1;
   if (p->pre_nblk > 0 && !p->partial) return -1;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   float* partial = p->pre_nblk > 0 ? p->partial : (float*)ar.get((size_t)bn_bwd_blocks(p->rows) * 2 * p->C * 4);
   float* coef = p->coef ? p->coef : (float*)ar.get(3 * (size_t)p->C * 4);
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   return bn_backward(p->dtype, p->dout, p->out, p->y, p->mean, p->invstd, p->gamma, (long)p->rows, p->C, partial, coef, p->dgamma,
                      p->dbeta, p->accumulate_param, p->dy, p->dres, p->dres_accumulate, p->mscale, p->mshift, p->pre_nblk,
                      p->premasked, (hipStream_t)stream);
 }
 
-static size_t bwd16_ex_pack_bytes() { return (size_t)round_up(16L * conv_kpad(DT_BF16, 9 * 16) * 2, 256); }
+static size_t bwd16_ex_pack_bytes() { return Arena::rounded((size_t)16 * conv_kpad(DT_BF16, 9 * 16) * 2); }
 
 // the separate weight gradient of the same layer: its grid is the fused kernel's default
 static void bwd16_ex_wgrad(const flair_bwd16_ex_t* p, WgradArgs& w) {
@@ -674,8 +664,8 @@ size_t flair_bwd16_ex_workspace_bytes(const flair_bwd16_ex_t* p) {
   if (!p || p->N < 1 || p->H < 1 || p->W < 1 || (p->H % 8) || (p->W % 32)) return 0;
   WgradArgs w;
   bwd16_ex_wgrad(p, w);
-  return bwd16_ex_pack_bytes() + (size_t)round_up((long)bwd16_workspace_bytes(bwd16_grid(w)), 256) +
-         (size_t)round_up((long)WGRAD_DBIAS_ROWS * 16 * 4, 256) + 256;
+  return bwd16_ex_pack_bytes() + Arena::rounded(bwd16_workspace_bytes(bwd16_grid(w))) +
+         Arena::rounded((size_t)WGRAD_DBIAS_ROWS * 16 * 4) + 256;
 }
 
 int flair_bwd16_ex_grid_rows(const flair_bwd16_ex_t* p) {
@@ -697,7 +687,7 @@ int flair_bwd16_ex(const flair_bwd16_ex_t* p, void* workspace, size_t wsb, void*
   bwd16_ex_wgrad(p, w);
   const int grid = bwd16_grid(w);
   if (p->bnr_rows < grid) return -100;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   const int Kpad = conv_kpad(DT_BF16, 9 * 16);
   void* wp = ar.get((size_t)16 * Kpad * 2);
   Bwd16Args f;
@@ -705,7 +695,7 @@ int flair_bwd16_ex(const flair_bwd16_ex_t* p, void* workspace, size_t wsb, void*
   f.slabs = (float*)ar.get(bwd16_workspace_bytes(grid));
   f.grid = grid;
   if (p->dbias) f.dbias_partial = (float*)ar.get((size_t)WGRAD_DBIAS_ROWS * 16 * 4);
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   // the forward layer's [Cout][16][3][3] as the flipped / transposed data-gradient pack, 16 rows of 9 x 16 (padded) gradient channels
   const int rc = pack_weight(DT_BF16, p->w_oihw, wp, p->Cout, 16, 3, 3, 16, 16, Kpad, 1, s);
   if (rc) return rc;
@@ -749,9 +739,9 @@ int flair_ew_add(int dtype, void* dst, const void* src, int64_t n, void* stream)
 int flair_colsum(int dtype, const void* x, int64_t rows, int ld, int C, float* out, void* workspace, size_t wsb, void* stream) {
   if (!x || !out || !workspace || rows < 1 || ld < 1 || C < 1) return -1;
   if (dtype != DT_F32 && dtype != DT_BF16) return -2;
-  OpArena ar(workspace, wsb);
+  Arena ar(workspace, wsb);
   float* partial = (float*)ar.get((size_t)bn_bwd_blocks((long)rows) * ld * 4);
-  if (ar.bad) return -100;
+  if (ar.err) return ar.err;
   return colsum(dtype, x, (long)rows, ld, C, partial, out, (hipStream_t)stream);
 }
 int flair_pack_weights(int dtype, const float* params, const flair_pack_desc_t* descs, int n, void* base, void* stream) {

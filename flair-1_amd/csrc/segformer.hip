@@ -75,7 +75,7 @@ bool SegFormer::shape_ok(int H, int W) const {
 }
 
 void SegFormer::layernorm(const SfNorm& n, const void* x, void* y, long rows) {
-  TF_RUN(sf_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, 1e-6f, s_));
+  RUN(sf_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, 1e-6f, s_));
 }
 
 int SegFormer::run(const float* params, const float* x_nchw, float* logits_quarter, float* logits_full, int B, int H, int W, void* ws,
@@ -109,13 +109,13 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
       float* p = nullptr;
       if (dtype == DT_BF16 && (h == 64 || h == 128)) {
         p = (float*)alloc((size_t)4 * h * 10 * 4);
-        if (!fresh) TF_RUN(sf_ffn_dw_pack(params_ + K.dw_w, params_ + K.dw_b, p, 4 * h, s_));
+        if (!fresh) RUN(sf_ffn_dw_pack(params_ + K.dw_w, params_ + K.dw_b, p, 4 * h, s_));
       }
       ffn_dw_.push_back(p);
     }
   float* bn_scale = (float*)alloc((size_t)dec_hidden * 4);
   float* bn_shift = (float*)alloc((size_t)dec_hidden * 4);
-  if (!fresh) TF_RUN(bn_eval_coeffs(dec_hidden, params_ + bn_g, params_ + bn_b, params_ + bn_rm, params_ + bn_rv, 1e-5f, bn_scale, bn_shift, s_));
+  if (!fresh) RUN(bn_eval_coeffs(dec_hidden, params_ + bn_g, params_ + bn_b, params_ + bn_rm, params_ + bn_rv, 1e-5f, bn_scale, bn_shift, s_));
   // decode head by linearity (see below): W_i = F_i P_i per stage, shift2 = folded BatchNorm shift + the projected biases
   const int D = dec_hidden;
   const SfLin& Lf = lins[fuse];
@@ -125,14 +125,14 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
   if (head_mode) {
     shift2 = (float*)alloc((size_t)D * 4);
     if (!fresh)
-      TF_RUN(sf_fuse_bias(params_ + Lf.w_off, D, params_ + lins[dec_proj[3]].b_off, params_ + lins[dec_proj[2]].b_off,
+      RUN(sf_fuse_bias(params_ + Lf.w_off, D, params_ + lins[dec_proj[3]].b_off, params_ + lins[dec_proj[2]].b_off,
                           params_ + lins[dec_proj[1]].b_off, params_ + lins[dec_proj[0]].b_off, bn_scale, bn_shift, shift2, s_));
     for (int i = 0; i < 4; ++i) {
       const SfLin& Lp = lins[dec_proj[i]];
       const int Ci = Lp.cin;
       // P_i transposed, packed as the weight of a product over D: rows = the C_i input channels, K = D
       const SfLin Lt = make_lin(D, Ci, 1, 1, 0);
-      const size_t pt_off = top_;
+      const size_t pt_off = ar_.top;
       alloc((size_t)Lt.rows * Lt.Kpad * es);
       // F_i = columns [(3 - i) D, (4 - i) D) of the fuse weight, as a [D pixels][D channels] tensor
       void* fi = alloc((size_t)D * D * es);
@@ -145,9 +145,9 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
       tb.n = 1;
       PackDesc& d = tb.d[0];
       d.w_off = Lp.w_off; d.dst_off = pt_off; d.Cout = D; d.Cin = Ci; d.R = 1; d.S = 1; d.Cin_p = D; d.rows_pad = Lt.rows; d.Kpad = Lt.Kpad; d.tf = 1;
-      TF_RUN(pack_weights_all(dtype, params_, base_, tb, s_));
-      TF_RUN(sf_slice_cols(dtype, params_ + Lf.w_off, 4 * D, (3 - i) * D, D, D, fi, s_));
-      gemm(Lt, fi, 1, D, 1, wi[i], Lw[i].Kpad, nullptr, nullptr, nullptr, 0, nullptr, 0, base_ + pt_off);   // the D rows of F_i as pixels
+      RUN(pack_weights_all(dtype, params_, ar_.base, tb, s_));
+      RUN(sf_slice_cols(dtype, params_ + Lf.w_off, 4 * D, (3 - i) * D, D, D, fi, s_));
+      gemm(Lt, fi, 1, D, 1, wi[i], Lw[i].Kpad, nullptr, nullptr, nullptr, 0, nullptr, 0, ar_.base + pt_off);   // the D rows of F_i as pixels
     }
   }
   void* wint = nullptr;
@@ -156,15 +156,15 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
     wint = alloc((size_t)128 * 96 * es);
     wc32 = alloc((size_t)32 * D * es);
     if (!fresh) {
-      TF_RUN(sf_head_wint(wint, s_));
-      if (!dry_ && !err_ && hipMemsetAsync(wc32, 0, (size_t)32 * D * es, s_) != hipSuccess) err_ = -101;
-      TF_RUN(sf_slice_cols(dtype, params_ + lins[cls].w_off, D, 0, D, num_labels, wc32, s_));
+      RUN(sf_head_wint(wint, s_));
+      if (!ar_.dry && !ar_.err && hipMemsetAsync(wc32, 0, (size_t)32 * D * es, s_) != hipSuccess) ar_.err = -101;
+      RUN(sf_slice_cols(dtype, params_ + lins[cls].w_off, D, 0, D, num_labels, wc32, s_));
     }
   }
   // ---- input and the tensors that live to the decode head
   const int Cin_p = lins[stages[0].patch].cin_p;
   void* xin = alloc((size_t)B * H * W * Cin_p * es);
-  TF_RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
+  RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
   const int H4 = H / 4, W4 = W / 4;
   void* feat[4];
   int fh[4], fw[4];
@@ -180,7 +180,7 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
     const SfStage& S = stages[i];
     const int h = hidden[i], Hs = fh[i], Ws = fw[i];
     const long tokens = (long)B * Hs * Ws;
-    const size_t mark = top_;
+    const size_t mark = ar_.top;
     void* x = alloc((size_t)tokens * h * es);
     void* ln = alloc((size_t)tokens * h * es);
     void* qb = alloc((size_t)tokens * h * es);
@@ -213,9 +213,9 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
         layernorm(norms[K.sr_ln], red, redn, ktok);
         kv_in = redn;
       }
-      gemm(Lkv, kv_in, B, Hk, Wk, kvb, 2 * h, nullptr, nullptr, nullptr, 0, nullptr, 0, base_ + kv_w_[blk], kv_b_[blk]);
+      gemm(Lkv, kv_in, B, Hk, Wk, kvb, 2 * h, nullptr, nullptr, nullptr, 0, nullptr, 0, ar_.base + kv_w_[blk], kv_b_[blk]);
       ++blk;
-      TF_RUN(sf_attention(dtype, qb, kvb, (const unsigned char*)kvb + (size_t)h * es, ctx, B, Hs * Ws, Hk * Wk, h, 2 * h, s_));
+      RUN(sf_attention(dtype, qb, kvb, (const unsigned char*)kvb + (size_t)h * es, ctx, B, Hs * Ws, Hk * Wk, h, 2 * h, s_));
       gemm(lins[K.o], ctx, B, Hs, Ws, x, h, /*residual*/ x, nullptr, nullptr, 0, nullptr);   // x = o_proj(ctx) + x, element by element in place
       if (ffn_dw_[blk - 1] && sf_ffn_fused_ok(dtype, h, Hs, Ws) && tune("FLAIR_SF_FFN", 1)) {
         // LayerNorm, fc1, depth-wise 3x3 + GELU, fc2 and the residual in one kernel; the result lands in the other buffer
@@ -227,8 +227,8 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
         const bool emit = K.sr >= 0 && tune("FLAIR_SF_FFN_LN", 1);
         const SfNorm& nn = norms[last ? S.out_ln : S.blocks[bi + 1].ln1];
         void* lnout = emit ? (last ? feat[i] : ctx) : nullptr;
-        TF_RUN(sf_ffn_fused(x, params_ + n2.g_off, params_ + n2.b_off, base_ + lins[K.fc1].packed, params_ + lins[K.fc1].b_off, ffn_dw_[blk - 1],
-                            base_ + lins[K.fc2].packed, params_ + lins[K.fc2].b_off, ln, B, Hs, Ws, h, 1e-6f, params_ + nn.g_off,
+        RUN(sf_ffn_fused(x, params_ + n2.g_off, params_ + n2.b_off, ar_.base + lins[K.fc1].packed, params_ + lins[K.fc1].b_off, ffn_dw_[blk - 1],
+                            ar_.base + lins[K.fc2].packed, params_ + lins[K.fc2].b_off, ln, B, Hs, Ws, h, 1e-6f, params_ + nn.g_off,
                             params_ + nn.b_off, lnout, s_));
         std::swap(x, ln);
         if (emit && last) stage_norm_done = true;
@@ -236,12 +236,12 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
       } else {
         layernorm(norms[K.ln2], x, ln, tokens);
         gemm(lins[K.fc1], ln, B, Hs, Ws, f1, 4 * h, nullptr, nullptr, nullptr, 0, nullptr);
-        TF_RUN(sf_dwconv3x3_gelu(dtype, f1, params_ + K.dw_w, params_ + K.dw_b, f2, B, Hs, Ws, 4 * h, s_));
+        RUN(sf_dwconv3x3_gelu(dtype, f1, params_ + K.dw_w, params_ + K.dw_b, f2, B, Hs, Ws, 4 * h, s_));
         gemm(lins[K.fc2], f2, B, Hs, Ws, x, h, /*residual*/ x, nullptr, nullptr, 0, nullptr);
       }
     }
     if (!stage_norm_done) layernorm(norms[S.out_ln], x, feat[i], tokens);
-    top_ = mark;   // the stage's scratch is free again (one stream: later launches are ordered behind its readers)
+    ar_.release(mark);   // the stage's scratch is free again (one stream: later launches are ordered behind its readers)
     sin = feat[i]; sH = Hs; sW = Ws;
   }
   // ---- decode head.  The library's order (Linear to D per stage, upsample, concatenate stage 3 .. 0, 1x1 fuse over 4 D channels,
@@ -257,10 +257,10 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
       gemm(Lw[i], feat[i], B, fh[i], fw[i], g[i], D, nullptr, nullptr, nullptr, 0, nullptr, 0, wi[i]);
     }
     if (head_mode == 2)
-      TF_RUN(sf_head_fused(feat[0], wi[0], g[1], g[2], g[3], wint, bn_scale, shift2, wc32, params_ + lins[cls].b_off, lq, B, H4, W4, D,
+      RUN(sf_head_fused(feat[0], wi[0], g[1], g[2], g[3], wint, bn_scale, shift2, wc32, params_ + lins[cls].b_off, lq, B, H4, W4, D,
                            num_labels, s_));
     else
-      TF_RUN(sf_upsample_sum_bn_relu(dtype, g[0], g[1], g[2], g[3], bn_scale, shift2, z, B, H4, W4, D, s_));
+      RUN(sf_upsample_sum_bn_relu(dtype, g[0], g[1], g[2], g[3], bn_scale, shift2, z, B, H4, W4, D, s_));
   } else {
     const int cat_ld = 4 * dec_hidden;
     void* cat = alloc((size_t)B * H4 * W4 * cat_ld * es);
@@ -269,17 +269,17 @@ int SegFormer::run(const float* params, const float* x_nchw, float* logits_quart
       if (i == 0) {   // already at 1/4 resolution: straight into its channel slice
         gemm(lins[dec_proj[0]], feat[0], B, fh[0], fw[0], slot, cat_ld, nullptr, nullptr, nullptr, 0, nullptr);
       } else {
-        const size_t mark = top_;
+        const size_t mark = ar_.top;
         void* p = alloc((size_t)B * fh[i] * fw[i] * dec_hidden * es);
         gemm(lins[dec_proj[i]], feat[i], B, fh[i], fw[i], p, dec_hidden, nullptr, nullptr, nullptr, 0, nullptr);
-        TF_RUN(sf_bilinear_nhwc(dtype, p, slot, B, fh[i], fw[i], dec_hidden, H4, W4, cat_ld, s_));
-        top_ = mark;
+        RUN(sf_bilinear_nhwc(dtype, p, slot, B, fh[i], fw[i], dec_hidden, H4, W4, cat_ld, s_));
+        ar_.release(mark);
       }
     }
     gemm(lins[fuse], cat, B, H4, W4, z, dec_hidden, nullptr, bn_scale, bn_shift, 1, nullptr);   // 1x1 conv + folded BatchNorm + ReLU
   }
   if (head_mode != 2) gemm(lins[cls], z, B, H4, W4, nullptr, 0, nullptr, nullptr, nullptr, 0, lq);   // classifier: fp32 NCHW logits at 1/4 resolution
-  if (logits_full) TF_RUN(sf_bilinear_nchw_f32(lq, logits_full, (long)B * num_labels, H4, W4, H, W, s_));
+  if (logits_full) RUN(sf_bilinear_nchw_f32(lq, logits_full, (long)B * num_labels, H4, W4, H, W, s_));
   return end();
 }
 

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 
+#include "arena.h"
 #include "ops.h"
 
 namespace flair {
@@ -25,15 +26,6 @@ struct SfLin {   // Linear (k = 1) or Conv2d(k, stride, pad) as an implicit GEMM
 struct SfNorm { int C; long g_off, b_off; };
 struct SfPart { long w_off, b_off; };   // one projection of a row-stacked product (fuse_rows)
 
-// a launch inside run(): skipped in the dry run and after the first error, which it records
-#define TF_RUN(expr)                     \
-  do {                                   \
-    if (!dry_ && !err_) {                \
-      int rc__ = (expr);                 \
-      if (rc__) err_ = rc__;             \
-    }                                    \
-  } while (0)
-
 class TfExec {
  public:
   int dtype;
@@ -52,14 +44,11 @@ class TfExec {
   int add_lin(const std::string& name, int cin, int cout, int k, int stride, int pad, bool bias);   // "...#conv": a 4-d weight
   int add_ln(const std::string& name, int C);
 
-  // ---- the arena of one run(): a bump allocator over the workspace; scratch is released with top_ = mark
-  unsigned char* base_ = nullptr;
-  size_t top_ = 0;
-  bool dry_ = false;
-  int err_ = 0;
+  // ---- the arena of one run(); scratch is released with ar_.release(mark), and the plan is the high-water mark
+  Arena ar_;
   hipStream_t s_ = nullptr;
   const float* params_ = nullptr;
-  void* alloc(size_t bytes);
+  void* alloc(size_t bytes) { return ar_.get(bytes); }
   // Resets the arena.  True: the weight-only front of the arena (everything allocated before the first shape-dependent tensor)
   // is still valid from the last run — same parameter buffer, workspace and mode_key, no weights_changed() since.
   bool begin(const float* params, void* ws, size_t ws_bytes, hipStream_t s, bool dry, int mode_key);
@@ -78,7 +67,7 @@ class TfExec {
             const float* oshift, int relu, float* out_nchw, int gelu = 0, const void* wpacked = nullptr, const float* bias = nullptr);
 
  private:
-  size_t cap_ = 0, peak_ = 0, need_ = 0;
+  size_t need_ = 0;
   PackTable packs_;
   int mode_key_ = 0;
   bool cache_ok_ = false;

@@ -45,36 +45,28 @@ int TfExec::add_ln(const std::string& name, int C) {
   return (int)norms.size() - 1;
 }
 
-void* TfExec::alloc(size_t bytes) {
-  const size_t off = top_;
-  top_ = (size_t)round_up((long)(top_ + bytes), 256);
-  if (top_ > peak_) peak_ = top_;   // (scratch is released with top_ = mark: the plan is the high-water mark)
-  if (!dry_ && top_ > cap_) { if (!err_) err_ = -100; return base_; }
-  return base_ + off;
-}
-
 bool TfExec::begin(const float* params, void* ws, size_t ws_bytes, hipStream_t s, bool dry, int mode_key) {
-  base_ = dry ? (unsigned char*)0x100000 : (unsigned char*)ws;
-  cap_ = ws_bytes; top_ = 0; peak_ = 0; dry_ = dry; err_ = 0; s_ = s; params_ = params; mode_key_ = mode_key;
+  ar_.reset(ws, ws_bytes, dry);
+  s_ = s; params_ = params; mode_key_ = mode_key;
   packs_.n = 0;
   return !dry && cache_ok_ && cache_params_ == params && cache_ws_ == ws && cache_mode_ == mode_key;
 }
 
 int TfExec::end() {
-  need_ = peak_ + (1 << 20);
-  if (!dry_) { cache_ok_ = err_ == 0; cache_params_ = params_; cache_ws_ = base_; cache_mode_ = mode_key_; }
-  return err_;
+  need_ = ar_.peak + (1 << 20);
+  if (!ar_.dry) { cache_ok_ = ar_.err == 0; cache_params_ = params_; cache_ws_ = ar_.base; cache_mode_ = mode_key_; }
+  return ar_.err;
 }
 
 void TfExec::flush_packs() {
-  if (packs_.n) TF_RUN(pack_weights_all(dtype, params_, base_, packs_, s_));
+  if (packs_.n) RUN(pack_weights_all(dtype, params_, ar_.base, packs_, s_));
   packs_.n = 0;
 }
 
 void TfExec::pack_lins(bool fresh) {
   const size_t es = dtype_size(dtype);
-  for (auto& L : lins) { L.packed = top_; alloc((size_t)L.rows * L.Kpad * es); }
-  if (fresh || dry_) return;
+  for (auto& L : lins) { L.packed = ar_.top; alloc((size_t)L.rows * L.Kpad * es); }
+  if (fresh || ar_.dry) return;
   for (const SfLin& L : lins) {
     if (packs_.n == PackTable::MAX) flush_packs();
     packs_.d[packs_.n++] = pack_desc(L.w_off, L.packed, L.cout, L.cin, L.k, L.cin_p, L.rows, L.Kpad, 0);
@@ -83,16 +75,16 @@ void TfExec::pack_lins(bool fresh) {
 }
 
 size_t TfExec::fuse_rows(const SfLin& G, const SfPart* parts, int n, bool fresh, float** bias) {
-  const size_t es = dtype_size(dtype), off = top_;
+  const size_t es = dtype_size(dtype), off = ar_.top;
   const int C = G.cout / n;
   alloc((size_t)G.rows * G.Kpad * es);
   *bias = (float*)alloc((size_t)n * C * 4);
-  if (fresh || dry_) return off;
+  if (fresh || ar_.dry) return off;
   for (int part = 0; part < n; ++part) {
     packs_.d[packs_.n++] = pack_desc(parts[part].w_off, off + (size_t)part * C * G.Kpad * es, C, G.cin, 1, G.cin_p,
                                      part + 1 < n ? C : G.rows - (n - 1) * C, G.Kpad, 0);   // the last part carries the padding rows
-    if (!err_ && hipMemcpyAsync(*bias + part * C, params_ + parts[part].b_off, (size_t)C * 4, hipMemcpyDeviceToDevice, s_) != hipSuccess)
-      err_ = -101;
+    if (!ar_.err && hipMemcpyAsync(*bias + part * C, params_ + parts[part].b_off, (size_t)C * 4, hipMemcpyDeviceToDevice, s_) != hipSuccess)
+      ar_.err = -101;
   }
   if (packs_.n + n > PackTable::MAX) flush_packs();   // room for the next call's n
   return off;
@@ -102,11 +94,11 @@ void TfExec::gemm(const SfLin& L, const void* in, int B, int Hin, int Win, void*
                   const float* oshift, int relu, float* out_nchw, int gelu, const void* wpacked, const float* bias) {
   ConvArgs a;
   conv_fwd_args(a, dtype, ConvInput{in, nullptr, L.cin_p, 0, 0, B, Hin, Win}, L.k, L.stride, L.pad, L.cout);
-  a.w = wpacked ? wpacked : base_ + L.packed;
+  a.w = wpacked ? wpacked : ar_.base + L.packed;
   a.bias = bias ? bias : L.b_off >= 0 ? params_ + L.b_off : nullptr;
   a.out = out; a.out_ld = out_ld; a.out_nchw = out_nchw;
   a.ores = res; a.oscale = oscale; a.oshift = oshift; a.orelu = relu; a.ogelu = gelu;
-  TF_RUN(launch_conv(dtype, a, s_));
+  RUN(launch_conv(dtype, a, s_));
 }
 
 }  // namespace flair

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "arena.h"
 #include "bwd_halo16.h"
 #include "ops.h"
 
@@ -55,6 +56,17 @@ struct TensorInfo {
   int stage; // 0 stem, 1..4 encoder layers, 5 decoder, 6 head (gradient bucket id)
 };
 
+// Backward hand-off from the one consumer of a unit's `out` to that unit: the consumer's data-gradient kernel already reduced
+// sum(dz), sum(dz*y) per pixel tile in its epilogue (ConvArgs::bnr_*, UNet::attach_bn_reduce).  masked: it also stored the gradient
+// MASKED by the unit's ReLU (ConvArgs::bnr_mask), so the gradient buffer of `out` holds dz: what the identity branch of a BasicBlock
+// receives and what the fused BatchNorm-backward apply of the unit's own data gradient (ConvArgs::ap_*) expects.
+struct BnReduce {
+  float* partial = nullptr;
+  int nblk = 0;
+  bool masked = false;
+  BnReduce take() { const BnReduce r = *this; *this = BnReduce(); return r; }   // unit_backward consumes it
+};
+
 struct Unit {  // conv -> BN -> (+ residual) -> ReLU
   int conv = -1, bn = -1;
   Act in0, in1;
@@ -64,14 +76,31 @@ struct Unit {  // conv -> BN -> (+ residual) -> ReLU
   bool relu = true;
   int res_unit = -1;   // downsample unit whose BN output is the residual
   Act res;             // identity residual
-  // backward: set when the one consumer of `out` already reduced sum(dz), sum(dz*y) per pixel tile in the epilogue of
-  // its data-gradient kernel (ConvArgs::bnr_*); consumed (and cleared) by unit_backward
-  float* bnr_partial = nullptr;
-  int bnr_nblk = 0;
-  // backward: that consumer also stored the gradient MASKED by this unit's ReLU (ConvArgs::bnr_mask): the gradient buffer of
-  // `out` holds dz, which is what the identity branch of a BasicBlock receives and what the fused BatchNorm-backward apply of
-  // the unit's own data gradient (ConvArgs::ap_*) expects.  Consumed (and cleared) by unit_backward
-  bool bnr_masked = false;
+  BnReduce bnr;
+};
+
+// run_unit: what the unit's convolution reads, [up2(in0) if up0] ++ in1, and the ONE 3x3 convolution `cons` that reads its output,
+// as [up2(out) if up0] ++ skip: it may take the pre-BatchNorm tensor and apply BN + ReLU while it stages (UNet::lazy_into_hg)
+struct UnitIn { Act in0, in1; bool up0 = false; };
+struct LazyOut { int cons = -1; bool up0 = false; Act skip; };
+
+// unit_backward: dout = gradient w.r.t. the unit's `out`; a call site names what differs from the defaults
+struct UnitBwd {
+  const void* dout = nullptr;
+  void* dres = nullptr; bool dres_acc = false;   // the residual branch's gradient dz is written (dres_acc: added) here
+  bool dgrad = true;               // false: the stem, whose input needs no gradient
+  bool upcat = false;              // decoder conv1: the input was cat([up2(in0), in1])
+  const void* acc_src = nullptr;   // conv1 of a BasicBlock: the identity branch's share of dX as a tensor of its own (the masked
+                                   // gradient of the block's output), added by the data gradient instead of a copy written as dres
+};
+
+// The data gradient of one layer, described before anything is launched (UNet::describe_dgrad)
+struct DgradDesc {
+  enum Form { DG_NONE, DG_PLAIN, DG_UPCAT_TILE, DG_UPCAT_SPLIT, DG_PARITY } form = DG_NONE;
+  ConvArgs a;
+  void *dx0 = nullptr, *dsk = nullptr, *dcat = nullptr;   // the upcat forms: gradient of in0, of the skip partner, of the concat
+  bool acc0 = false, acc1 = false;
+  int producer = -1;   // the unit whose BatchNorm-backward reduction rides in this launch's epilogue (attach_bn_reduce), or -1
 };
 
 // What one forward() does besides the plain pass (flair_unet_fwd_opts_t, include/flair_hip.h): arguments of that call, read while
@@ -107,6 +136,7 @@ struct FwdOpts {
 class UNet {
  public:
   UNet(int in_channels, int classes, int dtype);
+  ~UNet();
   int in_channels, classes, dtype;
   std::vector<ConvDesc> convs;
   std::vector<BnDesc> bns;
@@ -141,18 +171,14 @@ class UNet {
   // every entry point other than forward() lays the arena out differently (the split path re-imports five feature tensors
   // in front of the decoder units) or overwrites it: the constants of the last eval forward are gone
   void invalidate_reuse() { last_valid_ = false; last_params_ = nullptr; last_buffers_ = nullptr; }
-  void* last_dlogits_nhwc() const { return dl_nhwc_; }
   const void* logits_nhwc() const { return logits_nhwc_; }
   int head_ld() const { return convs.back().Cout_p; }
 
  private:
-  // ---- arena
-  unsigned char* base_ = nullptr;
-  size_t cap_ = 0, top_ = 0;
-  bool dry_ = false;
-  int err_ = 0;
+  // ---- arena (and the error of the call that runs on it)
+  Arena ar_;
   hipStream_t s_ = nullptr;
-  void* alloc(size_t bytes);
+  void* alloc(size_t bytes) { return ar_.get(bytes); }
   Act alloc_act(int N, int H, int W, int C);
   float* alloc_f(long n) { return (float*)alloc((size_t)n * 4); }
 
@@ -165,6 +191,7 @@ class UNet {
   Act xin_, f_[6], dec_in_[6], pool_, dec_out_;
   unsigned char* pool_idx_ = nullptr;
   int enc_units_end_ = 0, dec_units_begin_ = 0;
+  int dec_conv0_ = 0, dec_bn0_ = 0;   // the first decoder convolution / BatchNorm of the table (build_table)
   size_t fwd_top_ = 0;      // arena top after forward (backward scratch starts here)
   bool packed_d_ = false;
   bool reuse_ = false, last_valid_ = false;
@@ -188,10 +215,6 @@ class UNet {
   hipStream_t wgrad_stream();     // forks the side stream behind everything queued on s_ so far
   int side_cus() const;           // WgradArgs::cus of a launch on the side stream
   void side_join();
- public:
-  ~UNet();
- private:   // whole-model training forward only: small-channel decoder units hand out lazy activations
-  void* dl_nhwc_ = nullptr;
   void* logits_nhwc_ = nullptr;   // head output kept in NHWC T when forward() was called without an NCHW logits buffer
   void* const* stage_events_ = nullptr;
   void stage_done(int stage);
@@ -200,14 +223,14 @@ class UNet {
   // unit whose ReLU output is `a`, if `a` has exactly one consumer and the unit's mask comes from y; else -1
   int sole_producer(const Act& a) const;
   int residual_producer(const Act& a) const;
-  void attach_bn_reduce(ConvArgs& a, const Act& target);
-  // the fused backward of a 16 -> 16 layer (bwd16_fusable): `a` / `w` as the separate path would launch them, x the layer input
-  bool bwd16_ok(int flavour, const ConvArgs& a, const WgradArgs& w, const Act& x) const;
-  void bwd16_run(Bwd16Args& f, const ConvArgs& a, const WgradArgs& w, const Act& x);
+  // asks the data gradient `a`, which completes the gradient of `target`, to run the first pass of the BatchNorm backward of the
+  // unit that produced `target` in its epilogue; returns that unit (its Unit::bnr is set), or -1 when nothing was attached
+  int attach_bn_reduce(ConvArgs& a, const Act& target);
+  // the fused backward of a 16 -> 16 layer (bwd16_fusable): `a` / `w` as the separate path would launch them, x the layer input,
+  // producer the unit attach_bn_reduce(a, x) returned
+  bool bwd16_ok(int flavour, const ConvArgs& a, const WgradArgs& w, int producer) const;
+  void bwd16_run(Bwd16Args& f, const ConvArgs& a, const WgradArgs& w, const Act& x, int producer);
   std::vector<GradBuf> gbufs_;
-  // set by the BasicBlock walk just before the backward of a block's conv1: its data gradient adds this tensor (the masked
-  // gradient of the block's output = the identity branch's share) instead of reading a copy of it from its own output buffer
-  const void* acc_src_next_ = nullptr;
   // FLAIR_BWD_FUSE (0 / 1, default on): the halo-GEMM data gradients store their result masked by the consumer unit's ReLU, the
   // BatchNorm-backward apply pass then reads no mask source, and the identity branch takes the masked gradient without a copy
   bool bwd_fuse() const;
@@ -220,16 +243,26 @@ class UNet {
   int add_conv(const std::string& name, int cin, int cout, int k, int stride, int pad, bool bias, int stage);
   int add_bn(const std::string& name, int c, int stage);
   void begin(void* ws, size_t ws_bytes, hipStream_t s, bool dry);
+  void set_lazy_policy();   // FLAIR_LAZY_BN -> lazy_ok_, lazy_max_c_
+  size_t plan_end();        // closes a dry run: the plan, and a handle with no arena
+  // backward-side entry points: -11 unless `ws` holds a training forward, else per-call state and the data-gradient packs
+  int bwd_begin(const float* params, float* grads, void* ws, hipStream_t s);
+  // decoder_forward / head_forward: -11 unless they resume the split forward on the same arena and shape
+  int fwd_resume(const float* params, int B, int H, int W, int training, void* ws, hipStream_t s);
   void pack_forward_weights();
   void pack_dgrad_weights();
-  int run_unit(int conv, int bn, const Act& in0, const Act& in1, bool up0, bool relu, int res_unit, const Act& res,
-               bool materialize, int lazy_cons = -1, bool lazy_up0 = false, const Act* lazy_skip = nullptr);
-  bool lazy_into_hg(const Act& y, int cons, bool up0, const Act& skip) const;
+  int run_unit(int conv, int bn, const UnitIn& in, bool relu, int res_unit, const Act& res, bool materialize,
+               const LazyOut& lazy = LazyOut());
+  bool lazy_into_hg(const Act& y, const LazyOut& lazy) const;
   void encoder_fwd_impl(const float* x_nchw);
-  void decoder_fwd_impl();
+  void decoder_fwd_impl(const Act* f);   // over the features f[1..5]: f_, or what the split path re-imported (dec_in_)
   void head_fwd_impl(float* logits_nchw, const FwdOpts& o);
-  void unit_backward(int ui, const void* dout, void* dres, bool dres_acc, bool need_dgrad, void* dx_override,
-                     bool upcat = false);
+  // data gradient of layer `c` from dy (the gradient of its output, with that tensor's geometry) to the layer's input
+  // [up2(in0)] ++ in1 of extent Hin x Win; takes the gradient buffers (grad_of) and attaches the upstream reduction
+  DgradDesc describe_dgrad(const ConvDesc& c, const Act& dy, const Act& in0, const Act& in1, int Hin, int Win, bool upcat,
+                           const void* acc_src);
+  void unit_backward(int ui, const UnitBwd& g);
+  const void* import_dlogits(const float* dlogits_nchw);
   void head_bwd_impl(const void* dl);
   void decoder_bwd_impl();
   void encoder_bwd_impl();

@@ -98,7 +98,7 @@ void UperNet::conv_bn_relu(int i, const void* in, int B, int Hin, int Win, void*
 }
 
 void UperNet::layernorm(const SfNorm& n, const void* x, void* y, long rows, int ld) {
-  TF_RUN(swin_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, ld, 1e-5f, s_));
+  RUN(swin_layernorm(dtype, x, params_ + n.g_off, params_ + n.b_off, y, rows, n.C, ld, 1e-5f, s_));
 }
 
 int UperNet::run(const float* params, const float* x_nchw, float* logits, int B, int H, int W, void* ws, size_t ws_bytes, hipStream_t s,
@@ -125,12 +125,12 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     float* sc = (float*)alloc((size_t)n * 4);
     float* sh = (float*)alloc((size_t)n * 4);
     bn_sc_.push_back(sc); bn_sh_.push_back(sh);
-    if (!fresh) TF_RUN(bn_eval_coeffs(n, params_ + c.g, params_ + c.b, params_ + c.rm, params_ + c.rv, 1e-5f, sc, sh, s_));
+    if (!fresh) RUN(bn_eval_coeffs(n, params_ + c.g, params_ + c.b, params_ + c.rm, params_ + c.rv, 1e-5f, sc, sh, s_));
   }
   // ---- input, the backbone's outputs, the pyramid-pooling concatenation (stage 4's output is its first dims[3] channels)
   const int Cin_p = lins[patch].cin_p;
   void* xin = alloc((size_t)B * H * W * Cin_p * es);
-  TF_RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
+  RUN(nchw_f32_to_nhwc(dtype, x_nchw, xin, B, in_channels, H, W, Cin_p, s_));
   int fh[4], fw[4];
   for (int i = 0; i < 4; ++i) { fh[i] = H >> (i + 2); fw[i] = W >> (i + 2); }
   void* feat[3];
@@ -140,11 +140,11 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
   // ---- backbone
   void* x = alloc((size_t)B * fh[0] * fw[0] * dims[0] * es);
   {
-    const size_t mark = top_;
+    const size_t mark = ar_.top;
     void* t = alloc((size_t)B * fh[0] * fw[0] * dims[0] * es);
     gemm(lins[patch], xin, B, H, W, t, dims[0], nullptr, nullptr, nullptr, 0, nullptr);   // 4x4 stride-4 conv + bias
     layernorm(norms[patch_ln], t, x, (long)B * fh[0] * fw[0], dims[0]);
-    top_ = mark;
+    ar_.release(mark);
   }
   size_t blk = 0;
   for (int i = 0; i < 4; ++i) {
@@ -152,7 +152,7 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     const int C = dims[i], h = fh[i], w = fw[i];
     const long tokens = (long)B * h * w;
     void* xn = i < 3 ? alloc((size_t)tokens / 4 * 2 * C * es) : nullptr;
-    const size_t mark = top_;
+    const size_t mark = ar_.top;
     void* ln = alloc((size_t)tokens * C * es);
     void* qkv = alloc((size_t)tokens * 3 * C * es);
     void* ctx = alloc((size_t)tokens * C * es);
@@ -161,8 +161,8 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     for (size_t bi = 0; bi < S.blocks.size(); ++bi, ++blk) {
       const SwBlock& K = S.blocks[bi];
       layernorm(norms[K.ln1], x, ln, tokens, C);
-      gemm(Lq, ln, B, h, w, qkv, 3 * C, nullptr, nullptr, nullptr, 0, nullptr, 0, base_ + qkv_w_[blk], qkv_b_[blk]);
-      TF_RUN(swin_window_attention(dtype, qkv, qkv_b_[blk], params_ + K.table, ctx, B, h, w, C, heads[i], (bi & 1) ? 3 : 0, s_));
+      gemm(Lq, ln, B, h, w, qkv, 3 * C, nullptr, nullptr, nullptr, 0, nullptr, 0, ar_.base + qkv_w_[blk], qkv_b_[blk]);
+      RUN(swin_window_attention(dtype, qkv, qkv_b_[blk], params_ + K.table, ctx, B, h, w, C, heads[i], (bi & 1) ? 3 : 0, s_));
       gemm(lins[K.o], ctx, B, h, w, x, C, /*residual*/ x, nullptr, nullptr, 0, nullptr);   // x = o_proj(ctx) + x in place
       layernorm(norms[K.ln2], x, ln, tokens, C);
       gemm(lins[K.fc1], ln, B, h, w, f1, 4 * C, nullptr, nullptr, nullptr, 0, nullptr, /*gelu*/ 1);
@@ -171,10 +171,10 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
     if (i < 3) layernorm(norms[hs_norm[i]], x, feat[i], tokens, C);
     else layernorm(norms[hs_norm[3]], x, ppm_cat, tokens, pc_ld);
     if (i < 3) {   // patch merging: gather + LayerNorm(4C) into `ln` (tokens / 4 rows of 4C), reduction 4C -> 2C
-      TF_RUN(swin_patch_merge_ln(dtype, x, params_ + norms[S.merge_ln].g_off, params_ + norms[S.merge_ln].b_off, ln, B, h, w, C, 1e-5f, s_));
+      RUN(swin_patch_merge_ln(dtype, x, params_ + norms[S.merge_ln].g_off, params_ + norms[S.merge_ln].b_off, ln, B, h, w, C, 1e-5f, s_));
       gemm(lins[S.reduction], ln, B, h / 2, w / 2, xn, 2 * C, nullptr, nullptr, nullptr, 0, nullptr);
     }
-    top_ = mark;   // the stage's scratch is free again (one stream: later launches are ordered behind its readers)
+    ar_.release(mark);   // the stage's scratch is free again (one stream: later launches are ordered behind its readers)
     x = xn;
   }
   // ---- head: laterals, pyramid pooling + bottleneck
@@ -182,37 +182,37 @@ int UperNet::run(const float* params, const float* x_nchw, float* logits, int B,
   for (int i = 0; i < 4; ++i) lat[i] = alloc((size_t)B * fh[i] * fw[i] * D * es);
   for (int i = 0; i < 3; ++i) conv_bn_relu(lateral[i], feat[i], B, fh[i], fw[i], lat[i], D);
   {
-    const size_t mark = top_;
+    const size_t mark = ar_.top;
     for (int j = 0; j < 4; ++j) {
       const int Sc = pool_scales[j];
       void* pooled = alloc((size_t)B * Sc * Sc * dims[3] * es);
       void* pp = alloc((size_t)B * Sc * Sc * D * es);
-      TF_RUN(swin_adaptive_avgpool(dtype, ppm_cat, pc_ld, pooled, B, fh[3], fw[3], dims[3], Sc, s_));
+      RUN(swin_adaptive_avgpool(dtype, ppm_cat, pc_ld, pooled, B, fh[3], fw[3], dims[3], Sc, s_));
       conv_bn_relu(psp[j], pooled, B, Sc, Sc, pp, D);
-      TF_RUN(sf_bilinear_nhwc(dtype, pp, ppm_cat + (size_t)(dims[3] + j * D) * es, B, Sc, Sc, D, fh[3], fw[3], pc_ld, s_));
+      RUN(sf_bilinear_nhwc(dtype, pp, ppm_cat + (size_t)(dims[3] + j * D) * es, B, Sc, Sc, D, fh[3], fw[3], pc_ld, s_));
     }
     conv_bn_relu(bottleneck, ppm_cat, B, fh[3], fw[3], lat[3], D);
-    top_ = mark;
+    ar_.release(mark);
   }
   // ---- top-down path: each step reads the level the previous step updated
-  for (int i = 3; i > 0; --i) TF_RUN(swin_bilinear_add(dtype, lat[i], lat[i - 1], B, fh[i], fw[i], D, fh[i - 1], fw[i - 1], s_));
+  for (int i = 3; i > 0; --i) RUN(swin_bilinear_add(dtype, lat[i], lat[i - 1], B, fh[i], fw[i], D, fh[i - 1], fw[i - 1], s_));
   // ---- FPN convs, every level at level 0's size in its channel slice of the concatenation, fpn_bottleneck, classifier
   unsigned char* fcat = (unsigned char*)alloc((size_t)B * fh[0] * fw[0] * 4 * D * es);
   conv_bn_relu(fpn[0], lat[0], B, fh[0], fw[0], fcat, 4 * D);
   for (int i = 1; i < 3; ++i) {
-    const size_t mark = top_;
+    const size_t mark = ar_.top;
     void* t = alloc((size_t)B * fh[i] * fw[i] * D * es);
     conv_bn_relu(fpn[i], lat[i], B, fh[i], fw[i], t, D);
-    TF_RUN(sf_bilinear_nhwc(dtype, t, fcat + (size_t)i * D * es, B, fh[i], fw[i], D, fh[0], fw[0], 4 * D, s_));
-    top_ = mark;
+    RUN(sf_bilinear_nhwc(dtype, t, fcat + (size_t)i * D * es, B, fh[i], fw[i], D, fh[0], fw[0], 4 * D, s_));
+    ar_.release(mark);
   }
-  TF_RUN(sf_bilinear_nhwc(dtype, lat[3], fcat + (size_t)3 * D * es, B, fh[3], fw[3], D, fh[0], fw[0], 4 * D, s_));
+  RUN(sf_bilinear_nhwc(dtype, lat[3], fcat + (size_t)3 * D * es, B, fh[3], fw[3], D, fh[0], fw[0], 4 * D, s_));
   void* z = alloc((size_t)B * fh[0] * fw[0] * D * es);
   conv_bn_relu(fpn_bottleneck, fcat, B, fh[0], fw[0], z, D);
   float* lq = (float*)alloc((size_t)B * num_labels * fh[0] * fw[0] * 4);
   // 1x1 conv + bias: fp32 NCHW at 1/4, for a quarter-resolution caller straight into its tensor (the workspace plan is the same)
   gemm(lins[cls], z, B, fh[0], fw[0], nullptr, 0, nullptr, nullptr, nullptr, 0, quarter ? logits : lq);
-  if (!quarter) TF_RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
+  if (!quarter) RUN(sf_bilinear_nchw_f32(lq, logits, (long)B * num_labels, fh[0], fw[0], H, W, s_));
   return end();
 }
 

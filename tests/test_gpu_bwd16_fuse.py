@@ -22,7 +22,7 @@ upstream unit + weight gradient (+ bias gradient) in one kernel; tune key FLAIR_
    per CU: walks of two and three tiles, the BatchNorm-backward partials carried across a walk, one column per workgroup), no pins:
    the fused kernels are in the step — a fallback on disagreeing occupancy answers would fail here — and fused = separate bit for
    bit."""
-import ctypes as C
+import functools
 import os
 import re
 
@@ -30,6 +30,7 @@ import pytest
 import torch
 
 import exact_cases as E
+import launch_helpers as LH
 
 pytestmark = pytest.mark.gpu
 
@@ -39,37 +40,11 @@ DEFAULTS = {"FLAIR_BWD16_FUSE": FUSE_DEFAULT, "FLAIR_BWD16_WGS": 0, "FLAIR_WGH_W
 FUSED = ("bwd16_fused_head_bf16", "bwd16_fused_unit_bf16")
 
 
-class _tuned:
-    def __init__(self, **pairs):
-        self.pairs = pairs
-
-    def __enter__(self):
-        from flair_amd import _lib as L
-        for k, v in self.pairs.items():
-            L.check(L.lib().flair_tune_set(k.encode(), v), "flair_tune_set")
-
-    def __exit__(self, *exc):
-        from flair_amd import _lib as L
-        for k, v in DEFAULTS.items():
-            L.lib().flair_tune_set(k.encode(), v)
+def _tuned(**pairs):
+    return LH.tuned(pairs.items(), DEFAULTS)
 
 
-def _profiled(fn):
-    """(result, {kernel name: launches}) of fn under the library's launch profile"""
-    from flair_amd import _lib as L
-    L.check(L.lib().flair_profile_start(2048))
-    try:
-        res = fn()
-    finally:
-        n = L.lib().flair_profile_stop()
-    assert n >= 0, n
-    out = {}
-    for i in range(n):
-        name = C.create_string_buffer(96)
-        ms, cnt, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
-        L.check(L.lib().flair_profile_kernel(i, name, 96, C.byref(ms), C.byref(cnt), C.byref(fl), C.byref(by)))
-        out[name.value.decode()] = cnt.value
-    return res, out
+_profiled = functools.partial(LH.profiled, slots=2048)   # every kernel of whole training steps
 
 
 @pytest.fixture(scope="module")

@@ -38,8 +38,7 @@ Not covered here:
 
 Both dtypes of a case share one reference (the case modules cache the last two), so the dtype parameter varies fastest.  One
 process, well under 1 GB of device memory; the 120 tests of this file take 7 s on an MI355X (the slowest 0.7 s)."""
-import contextlib
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -48,6 +47,7 @@ import torch.nn.functional as F
 
 import bwd_fused_cases as B
 import exact_cases as E
+import launch_helpers as LH
 
 pytestmark = pytest.mark.gpu
 
@@ -84,40 +84,9 @@ def _same(got, ref, what):
                              f"expected {float(ref[i])}; last at {tuple(int(v) for v in bad[-1])}")
 
 
-@contextlib.contextmanager
-def _tuned(pairs):
-    from flair_amd import _lib as L
-    try:
-        for k, v in pairs:
-            L.check(L.lib().flair_tune_set(k.encode(), v))
-        yield
-    finally:
-        for k, v in E.TUNE_DEFAULTS.items():
-            L.lib().flair_tune_set(k.encode(), v)
-
-
-_PROFILED = ("conv", "wgrad", "bn_bwd_", "bn_act", "maxpool_", "upcat_bwd", "pack_weights_all")
-
-
-def _profiled(fn):
-    """Run fn under the library's launch profile: (result, {kernel name: launches}) of the convolution, weight-gradient,
-    BatchNorm-backward, pooling, upcat and pack launches."""
-    from flair_amd import _lib as L
-    L.check(L.lib().flair_profile_start(256))
-    try:
-        res = fn()
-    finally:
-        n = L.lib().flair_profile_stop()
-    assert n >= 0, n
-    out = {}
-    for i in range(n):
-        name = C.create_string_buffer(96)
-        ms, cnt, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
-        L.check(L.lib().flair_profile_kernel(i, name, 96, C.byref(ms), C.byref(cnt), C.byref(fl), C.byref(by)))
-        k = name.value.decode()
-        if k.startswith(_PROFILED) and k != "wgrad_reduce":
-            out[k] = cnt.value
-    return res, out
+_tuned = functools.partial(LH.tuned, defaults=E.TUNE_DEFAULTS)
+# the convolution, weight-gradient, BatchNorm-backward, pooling, upcat and pack launches
+_profiled = functools.partial(LH.profiled, keep=("conv", "wgrad", "bn_bwd_", "bn_act", "maxpool_", "upcat_bwd", "pack_weights_all"))
 
 
 def _backed(t, dt, dev, numel):

@@ -8,8 +8,6 @@ a quotient and a remainder; each case asserts through the profile that the kerne
 
 Both dtypes of a case share one reference (exact_cases caches the last two), so the dtype parameter varies fastest.  Nothing here
 needs more than one process or 1 GB of device memory; the whole file takes well under a minute on an MI355X."""
-import contextlib
-import ctypes as C
 import functools
 
 import numpy as np
@@ -18,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import exact_cases as E
+import launch_helpers as LH
 
 pytestmark = pytest.mark.gpu
 
@@ -49,36 +48,8 @@ def _same(got, ref, what):
                              f"expected {float(ref[i])}; last at {tuple(int(v) for v in bad[-1])}")
 
 
-@contextlib.contextmanager
-def _tuned(pairs):
-    from flair_amd import _lib as L
-    try:
-        for k, v in pairs:
-            L.check(L.lib().flair_tune_set(k.encode(), v))
-        yield
-    finally:
-        for k, v in E.TUNE_DEFAULTS.items():
-            L.lib().flair_tune_set(k.encode(), v)
-
-
-def _profiled(fn):
-    """Run fn under the library's launch profile: (result, {conv / weight-gradient kernel name: launches})."""
-    from flair_amd import _lib as L
-    L.check(L.lib().flair_profile_start(256))
-    try:
-        res = fn()
-    finally:
-        n = L.lib().flair_profile_stop()
-    assert n >= 0, n
-    out = {}
-    for i in range(n):
-        name = C.create_string_buffer(96)
-        ms, cnt, fl, by = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
-        L.check(L.lib().flair_profile_kernel(i, name, 96, C.byref(ms), C.byref(cnt), C.byref(fl), C.byref(by)))
-        k = name.value.decode()
-        if (k.startswith("conv") or k.startswith("wgrad")) and k != "wgrad_reduce":
-            out[k] = cnt.value
-    return res, out
+_tuned = functools.partial(LH.tuned, defaults=E.TUNE_DEFAULTS)
+_profiled = functools.partial(LH.profiled, keep=("conv", "wgrad"))   # the convolution and weight-gradient launches
 
 
 # ------------------------------------------------------------------------------------------------ convolutions, plain entry points
