@@ -78,6 +78,7 @@ const char* flair_strerror(int code) {
     case -16: return "flair_unet_fwd_opts_t: rows_f32 in a training forward needs drows_f32 (the in-place add is for eval-mode forwards)";
     case -17: return "flair_unet_fwd_opts_t: drows_f32 is for a training forward (an eval-mode forward takes rows_f32 alone)";
     case -18: return "flair_unet_fwd_opts_t: the gradient that reaches the bottleneck tensor was stored masked, its sums into drows_f32 would be wrong";
+    case -19: return "D4 transform code with an odd rot90 count needs a square tile (H == W)";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -335,6 +336,20 @@ int flair_gather_tiles(const uint8_t* raster_u8, int bands, int raster_h, int ra
     a.stdv[c] = norm_type == 2 ? stds[c] : 1.0;
   }
   return gather_tiles(a, tiles, raster_h, raster_w, (hipStream_t)stream);
+}
+int flair_d4_nchw_f32(const float* in_nchw, float* out_nchw, int B, int C, int H, int W, int code, void* stream) {
+  if (!in_nchw || !out_nchw || in_nchw == out_nchw) return -1;
+  return d4_nchw_f32(in_nchw, out_nchw, B, C, H, W, code, (hipStream_t)stream);
+}
+int flair_tta_accum(const float* logits_nchw, int B, int C, int H, int W, int code, int first, float* acc_nchw, uint8_t* preds_u8,
+                    float* prob_f32, int n, void* stream) {
+  if (!logits_nchw) return -1;
+  return tta_accum(logits_nchw, 1, B, C, H, W, code, first, acc_nchw, preds_u8, prob_f32, n, (hipStream_t)stream);
+}
+int flair_tta_accum_q4(const float* logits_nchw, int B, int C, int H, int W, int code, int first, float* acc_nchw, uint8_t* preds_u8,
+                       float* prob_f32, int n, void* stream) {
+  if (!logits_nchw) return -1;
+  return tta_accum(logits_nchw, 4, B, C, H, W, code, first, acc_nchw, preds_u8, prob_f32, n, (hipStream_t)stream);
 }
 int flair_confmat_masks(const uint8_t* truth_raw, const uint8_t* pred, int64_t n, int C, int truth_offset, int64_t* confmat,
                         void* stream) {

@@ -9,6 +9,7 @@
 //                   src/zone_detect/compare.py:35,71-76; src/zone_detect/dataset.py:11-34.
 //   confmat_masks   offline evaluation: confusion matrix of (truth raster - 1) against a prediction raster.
 //                   src/flair/metrics.py:60-75.
+#include "d4.h"
 #include "logit_source.h"
 #include "ops.h"
 #include "prof.h"
@@ -18,18 +19,6 @@ namespace flair {
 namespace {
 
 constexpr int MAXC = 32;
-
-// where output pixel (i, j) of rot90^k(hflip(vflip(a))) comes from (numpy: rot90 is counter-clockwise,
-// r[i][j] = m[j][N-1-i]); flags: bit0 V-flip, bit1 H-flip, bits 2-3 k
-__device__ __forceinline__ void d4_source(int flags, int i, int j, int H, int W, int& si, int& sj) {
-  const int k = (flags >> 2) & 3;
-  if (k == 0) { si = i; sj = j; }
-  else if (k == 1) { si = j; sj = W - 1 - i; }
-  else if (k == 2) { si = H - 1 - i; sj = W - 1 - j; }
-  else { si = H - 1 - j; sj = i; }
-  if (flags & 2) sj = W - 1 - sj;
-  if (flags & 1) si = H - 1 - si;
-}
 
 __device__ __forceinline__ float norm_byte(int mode, unsigned char v, double mean, double stdv) {
   if (mode == 2) return (float)(((double)v - mean) / stdv);  // numpy: float64 subtract, float64 divide, then float32

@@ -1,4 +1,4 @@
-// Where a zone_detect kernel (feed.hip detect_convert, zone_stitch.hip, zone_metrics.hip) reads the logits of ONE window pixel:
+// Where a zone_detect kernel (feed.hip detect_convert, zone_stitch.hip, zone_metrics.hip) or tta.hip's accumulate reads the logits of ONE window pixel:
 // the kernels are templated on one of these and call src(c) once per class, everything after that load is shared text.
 //   FullLogits     fp32 NCHW (B, C, S, S): the value stored at the pixel
 //   QuarterLogits  fp32 NCHW (B, C, S/4, S/4), what the HuggingFace-provider models' classifiers write: the value

@@ -140,6 +140,11 @@ int detect_stitch_max(const float* logits, int up, const unsigned char* preds, c
                       const int* tiles, int x_lo, int x_hi, int y_lo, int y_hi, float* out, int Hr, int Wr, hipStream_t s);
 int confmat_masks(const unsigned char* truth, const unsigned char* pred, long n, int C, int truth_offset, long long* confmat,
                   hipStream_t s);
+// test-time augmentation (csrc/tta.hip); code: the D4 packing of csrc/d4.h, -19 for an odd rot90 count with H != W
+int d4_nchw_f32(const float* in, float* out, int B, int C, int H, int W, int code, hipStream_t s);
+// one pass: acc (B, C, H, W) (+)= softmax of the transformed-frame logits, moved back to the original frame; `up` as above
+int tta_accum(const float* logits, int up, int B, int C, int H, int W, int code, int first, float* acc, unsigned char* preds, float* prob,
+              int n, hipStream_t s);
 // zone_detect metrics (csrc/zone_metrics.hip); source 0: u8 class tiles (B, S, S), 1: fp32 logits (B, C, S, S), 2: fp32 raster,
 // 3: fp32 quarter-resolution logits (B, C, S/4, S/4)
 int zone_window_confmat(int source, const void* pred, int B, int C, int S, int margin, const int* tiles, const unsigned char* truth,

@@ -126,6 +126,9 @@ PROTOTYPES = {
     "flair_detect_blend_accum_q4": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_detect_stitch_max_q4": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp]),
     "flair_zone_window_confmat_logits_q4": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
+    "flair_d4_nchw_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "flair_tta_accum": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+    "flair_tta_accum_q4": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
     "flair_zone_window_confmat_raster": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "flair_zone_raster_confmat": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "flair_zone_error_map": (i32, [vp, vp, i32, i32, i32, vp, i32, vp, i32, C.c_double, i32, vp, vp, vp, vp, vp, vp]),

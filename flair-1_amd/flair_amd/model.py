@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .tta import tta_codes, tta_predict
 from .unet import create_model
 
 
@@ -178,20 +179,26 @@ class FLAIR_ModelFactory(nn.Module):
         return output
 
     @torch.no_grad()
-    def predict_classes(self, x, met=None, want_prob=False):
+    def predict_classes(self, x, met=None, want_prob=False, tta=None):
         """argmax(softmax(forward(x, met))) as uint8 (B,H,W) and, with ``want_prob``, the winner's fp32 probability — what
         ``predict_step`` (task_module.py:206-213) and zone_detect's 'argmax' output compute.  The U-Net takes both out of its head
         convolution's epilogue (``Unet.predict_classes``), with metadata through the same single native call; the MetadataMLP
         runs without dropout, as Lightning's ``model.eval()`` makes the reference's.  Other models: the separate kernel over
-        the logits."""
+        the logits.
+        ``tta`` ("flips", "d4" or a list of D4 transform codes, ``flair_amd.tta``): the mean probability over those transforms of
+        ``x`` instead, at the resolution of this model's logits (a SegFormer's stay quarter-size, quirk Q11); the metadata vectors go
+        unchanged to every pass."""
+        codes = tta_codes(tta)
         if self.model_provider == "SegmentationModelsPytorch":
             if self.use_metadata != True:  # noqa: E712
-                return self.seg_model.predict_classes(x, want_prob=want_prob)
+                return self.seg_model.predict_classes(x, want_prob=want_prob, tta=codes)
             if met is None:
                 raise ValueError("this model was built with use_metadata: predict_classes needs the (B,45) metadata vectors")
             if os.environ.get("FLAIR_META_FUSE", "1") != "0":
                 x_enc = self.enc(met, masks=None)
                 check_metadata_tile(x)
-                return self.seg_model.predict_classes(x, want_prob=want_prob, bottleneck_rows=x_enc)
+                return self.seg_model.predict_classes(x, want_prob=want_prob, bottleneck_rows=x_enc, tta=codes)
+        if codes is not None:
+            return tta_predict(lambda t: self.forward(t, met), x, codes, want_prob=want_prob)
         logits = self.forward(x, met)
         return ops.softmax_argmax(logits.detach().float().contiguous(), want="u8", want_maxprob=want_prob)

@@ -364,6 +364,57 @@ def softmax_argmax(logits, want="i64", want_maxprob=False):
     return (p, mp) if want_maxprob else p
 
 
+def _check_d4(code, H, W):
+    code = int(code)
+    if not 0 <= code <= 15:
+        raise ValueError(f"D4 transform code {code} is outside 0..15 (bit 0 V-flip, bit 1 H-flip, bits 2-3 rot90 count)")
+    if code & 4 and H != W:
+        raise ValueError(f"D4 transform code {code} has an odd rot90 count: it needs a square tile, not {H} x {W}")
+    return code
+
+
+def d4_transform(x, code):
+    """rot90^k(hflip(vflip(x))) of an fp32 (B, C, H, W) tensor for the packed ``code`` (data_feed.pack_d4), out of place"""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("d4_transform takes an fp32 (B, C, H, W) tensor")
+    B, Cc, H, W = x.shape
+    code = _check_d4(code, H, W)
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    L.check(L.lib().flair_d4_nchw_f32(L.ptr(x), L.ptr(out), B, Cc, H, W, code, L.stream()), "flair_d4_nchw_f32")
+    return out
+
+
+def tta_accumulate(logits, code, acc=None, first=False, preds=None, prob=None, n=1, quarter=False):
+    """One pass of the test-time-augmentation ensemble (flair_tta_accum / _q4 of include/flair_hip.h): the softmax of ``logits``
+    (fp32 (B, C, H, W), or (B, C, H/4, W/4) with ``quarter``), taken in the frame of transform ``code``, goes into ``acc`` (fp32
+    (B, C, H, W), stored when ``first`` else added) at the original-frame pixel; with ``preds`` (uint8 (B, H, W)) this is the last
+    of ``n`` passes and writes the class and, into ``prob`` (fp32 (B, H, W)), the largest sum / n instead of ``acc``."""
+    if logits.dim() != 4 or logits.dtype != torch.float32:
+        raise ValueError("tta_accumulate takes fp32 (B, C, h, w) logits")
+    B, Cc, h, w = logits.shape
+    up = 4 if quarter else 1
+    H, W = h * up, w * up
+    code = _check_d4(code, H, W)
+    if not 1 <= Cc <= 32:
+        raise ValueError(f"tta_accumulate takes 1 to 32 classes, not {Cc}")
+    if not 1 <= int(n) <= 16:
+        raise ValueError(f"tta_accumulate takes 1 to 16 passes, not {n}")
+    if quarter and H != W:
+        raise ValueError("quarter-resolution logits need a square tile")
+    if prob is not None and preds is None:
+        raise ValueError("prob needs preds (the last pass writes both)")
+    if acc is None and not (first and preds is not None):
+        raise ValueError("only a pass that is both first and last runs without acc")
+    for t, shape, dt, name in ((acc, (B, Cc, H, W), torch.float32, "acc"), (preds, (B, H, W), torch.uint8, "preds"),
+                               (prob, (B, H, W), torch.float32, "prob")):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt):
+            raise ValueError(f"{name} must be {dt} {shape}, got {t.dtype} {tuple(t.shape)}")
+    fn = "flair_tta_accum_q4" if quarter else "flair_tta_accum"
+    L.check(getattr(L.lib(), fn)(L.ptr(logits), B, Cc, H, W, code, int(bool(first)), L.ptr(acc), L.ptr(preds), L.ptr(prob), int(n),
+                                 L.stream()), fn)
+
+
 def confmat_update(confmat, target, pred):
     Cc = confmat.shape[0]
     L.check(L.lib().flair_confmat_update(L.ptr(target), _LABEL_KIND[target.dtype], L.ptr(pred), _LABEL_KIND[pred.dtype],

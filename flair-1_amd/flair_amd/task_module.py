@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import ops
 from .head import MeanMetric, MulticlassJaccardIndex
+from .tta import tta_codes, tta_predict
 
 try:  # pragma: no cover - lightning is absent in the build image
     import pytorch_lightning as pl
@@ -158,11 +159,12 @@ class segmentation_task_training(_Base):
 
 
 class segmentation_task_predict(_Base):
-    def __init__(self, model, num_classes: int, use_metadata: bool = False):
+    def __init__(self, model, num_classes: int, use_metadata: bool = False, tta=None):
         super().__init__()
         self.model = model
         self.num_classes = num_classes
         self.use_metadata = use_metadata
+        self.tta = tta_codes(tta)   # D4 transform codes of the test-time augmentation (flair_amd.tta), None: off
 
     def forward(self, input_im, input_met):
         return self.model(input_im, input_met)
@@ -183,9 +185,14 @@ class segmentation_task_predict(_Base):
         if fast is not None and not getattr(self.model, "training", True):
             # an eval-mode model that hands out argmax(softmax(logits)) itself (the U-Net: from its head convolution's epilogue,
             # the logits are never written; with metadata in the same native call)
+            kw = {} if self.tta is None else {"tta": self.tta}
             with torch.no_grad():
-                preds = fast(batch["img"], batch["mtd"]) if self.use_metadata == True else fast(batch["img"])  # noqa: E712
+                preds = fast(batch["img"], batch["mtd"], **kw) if self.use_metadata == True else fast(batch["img"], **kw)  # noqa: E712
             batch["preds"] = preds.to(torch.int64)
+            return batch
+        if self.tta is not None:
+            met = batch["mtd"] if self.use_metadata == True else ""  # noqa: E712
+            batch["preds"] = tta_predict(lambda t: self.forward(t, met), batch["img"], self.tta).to(torch.int64)
             return batch
         if self.use_metadata == True:  # noqa: E712
             logits = self.forward(batch["img"], batch["mtd"])

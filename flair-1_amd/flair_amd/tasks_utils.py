@@ -48,7 +48,8 @@ def get_segmentation_module(config, stage: str = "train", compute_dtype=None):
         scheduler = ReduceLROnPlateau(optimizer=optimizer, mode="min", factor=0.5, patience=10, cooldown=4, min_lr=1e-7)
         return segmentation_task_training(model=model, class_infos=config["classes"], criterion=criterion,
                                           optimizer=optimizer, scheduler=scheduler, use_metadata=config["use_metadata"])
-    return segmentation_task_predict(model=model, num_classes=len(config["classes"]), use_metadata=config["use_metadata"])
+    return segmentation_task_predict(model=model, num_classes=len(config["classes"]), use_metadata=config["use_metadata"],
+                                     tta=config.get("tta"))
 
 
 _YEARS = ("2018", "2019", "2020", "2021")

@@ -23,6 +23,7 @@ import torch.distributed as dist
 from . import _lib as L
 from . import ops
 from .model import check_metadata_tile
+from .tta import tta_codes
 
 
 def bucket_ranges(stage_ranges, min_elems=0):
@@ -253,13 +254,18 @@ class SegTrainer:
         return self.metadata_encoder(mtd.to(self.grads.device), masks=None).detach()
 
     @torch.no_grad()
-    def predict(self, img, mtd=None):
+    def predict(self, img, mtd=None, tta=None):
         """predict_step of the reference (task_module.py:206-213): (B,H,W) uint8 argmax(softmax(logits)); with ``mtd`` ((B,45)
-        metadata vectors) the logits of the metadata branch (model.py:57-62)."""
+        metadata vectors) the logits of the metadata branch (model.py:57-62).  ``tta`` ("flips", "d4" or a list of D4 transform
+        codes, ``flair_amd.tta``): the class of the largest mean probability over those transforms of ``img`` instead."""
         m = self.model
         B, _, H, W = img.shape
+        codes = tta_codes(tta)
         with torch.cuda.device(self.grads.device):
-            return self._predict(m, img, B, H, W, self._meta_rows(img, mtd))
+            rows = self._meta_rows(img, mtd)
+            if codes is not None:
+                return m.predict_classes(img, bottleneck_rows=rows, tta=codes)
+            return self._predict(m, img, B, H, W, rows)
 
     def _predict(self, m, img, B, H, W, rows=None):
         preds = torch.empty(B, H, W, dtype=torch.uint8, device=img.device)

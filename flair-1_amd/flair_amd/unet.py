@@ -30,6 +30,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from ._native_model import query_layout, tensor_of
+from .tta import tta_codes, tta_predict
 
 
 def _on_model_device(fn):
@@ -750,14 +751,19 @@ class Unet(nn.Module):
 
     @torch.no_grad()
     @_on_model_device
-    def predict_classes(self, x, want_prob=False, bottleneck_rows=None):
+    def predict_classes(self, x, want_prob=False, bottleneck_rows=None, tta=None):
         """Eval-mode forward whose head convolution returns the argmax class per pixel (uint8 (B,H,W)) and, with ``want_prob``,
         that class's softmax probability (fp32 (B,H,W)) from its epilogue — what ``convert(softmax(model(x)), 'argmax')`` of
         zone_detect (dataset.py:23-30) and ``predict_step`` (task_module.py:206-213) compute — without writing the logits.
         ``bottleneck_rows``: fp32 (B, H/32), added to the bottleneck feature as ``feats[-1][b,c,h,w] += rows[b,h]`` (the
-        metadata fusion of model.py:57-62) inside the same native call."""
+        metadata fusion of model.py:57-62) inside the same native call.
+        ``tta`` (``flair_amd.tta.tta_codes``: "flips", "d4" or a list of transform codes): the mean probability over those D4
+        transforms of ``x`` instead, from the fp32 logits of ``eval_logits`` (the rows go unchanged to every pass)."""
         if not x.is_cuda:
             raise L.FlairHipError("flair_amd.Unet needs HIP tensors (no CPU fallback)")
+        codes = tta_codes(tta)
+        if codes is not None:
+            return tta_predict(lambda t: self.eval_logits(t, bottleneck_rows=bottleneck_rows), x, codes, want_prob=want_prob)
         B, H, W = x.shape[0], x.shape[-2], x.shape[-1]   # (_c_forward checks and prepares the input: once per call, it is host time)
         preds = torch.empty(B, H, W, dtype=torch.uint8, device=x.device)
         prob = torch.empty(B, H, W, dtype=torch.float32, device=x.device) if want_prob else None

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .tta import tta_codes, tta_predict
 
 OUTPUT_TYPES = {"argmax": 0, "class_prob": 1}   # the values config["output_type"] may take (compare.py:69-82)
 _MODE_PROBS = 2                                   # private: every fp32 softmax probability, no convert (compare.py:35)
@@ -325,6 +326,16 @@ class ZoneDetector:
         # quarter-resolution logits straight into the _q4 kernels (no x4 pass, no tile-sized logits); FLAIR_ZD_QUARTER=0: the x4 path
         want = os.environ.get("FLAIR_ZD_QUARTER", "1" if QUARTER_DEFAULT else "0") != "0"
         self.quarter = want and hasattr(model, "forward_quarter") and self.S % 4 == 0
+        # test-time augmentation (flair_amd.tta): every batch of windows becomes a (class, mean probability) pair, which
+        # the _preds kernels stitch whatever the model
+        self.tta = tta_codes(config.get("tta"))
+        if self.tta is not None:
+            if self.output_type != "argmax":
+                raise ValueError("tta needs output_type 'argmax': 'class_prob' writes every class's probability, and the ensemble keeps "
+                                 "only the winner's")
+            if self.blend not in (None, "max"):
+                raise ValueError(f"tta with stitching {self.stitching!r} is not implemented: 'average' and 'average_weights' blend "
+                                 "per-class probabilities, and the ensemble keeps only the winner's (use 'exact-clipping' or 'max')")
         self.window_confmats = None   # run(raster, truth): (n, C, C) int64 on the device, one per window in job order
         self.window_rects = None      # and their (col_off, row_off, width, height) core rectangles, numpy int32 (n, 4)
 
@@ -349,6 +360,14 @@ class ZoneDetector:
         if getattr(self.model, "classes", self.n_classes) != self.n_classes:
             raise RuntimeError(f"model has {self.model.classes} classes, config says {self.n_classes}")
         return True
+
+    def _tta_preds(self, imgs: torch.Tensor):
+        """(class u8, mean probability f32), both (B, S, S), of the ensemble over ``self.tta`` for a batch of gathered windows"""
+        if self._fast_preds(0):
+            return self.model.predict_classes(imgs, want_prob=True, tta=self.tta)
+        if self.quarter:
+            return tta_predict(self._logits_quarter, imgs, self.tta, want_prob=True, quarter=True)
+        return tta_predict(self._logits, imgs, self.tta, want_prob=True)
 
     def _logits(self, imgs: torch.Tensor) -> torch.Tensor:
         if hasattr(self.model, "forward_full"):
@@ -406,7 +425,10 @@ class ZoneDetector:
                                                len(self.channels), NORM_CODES[self.norm_type], self._means, self._stds,
                                                L.ptr(imgs), L.stream()), "flair_gather_tiles")
             if blend is not None:
-                if self.blend == "max" and self._fast_preds(mode):
+                if self.tta is not None:
+                    preds, prob = self._tta_preds(imgs)
+                    blend.add(b0, tiles, preds=preds, prob=prob)
+                elif self.blend == "max" and self._fast_preds(mode):
                     preds, prob = self.model.predict_classes(imgs, want_prob=True)
                     blend.add(b0, tiles, preds=preds, prob=prob)
                 elif self.quarter:
@@ -414,8 +436,8 @@ class ZoneDetector:
                 else:
                     blend.add(b0, tiles, logits=self._logits(imgs))
                 continue
-            if self._fast_preds(mode):
-                preds, prob = self.model.predict_classes(imgs, want_prob=True)
+            if self.tta is not None or self._fast_preds(mode):
+                preds, prob = self._tta_preds(imgs) if self.tta is not None else self.model.predict_classes(imgs, want_prob=True)
                 L.check(L.lib().flair_detect_stitch_preds(L.ptr(preds), L.ptr(prob), B, self.S, self.margin, L.ptr(tiles), L.ptr(out),
                                                           Hr, Wr, L.stream()), "flair_detect_stitch_preds")
                 if confmats is not None:

@@ -259,6 +259,25 @@ int flair_detect_blend_accum_q4(const float* logits_nchw, int B, int C, int S, i
 int flair_detect_stitch_max_q4(const float* logits_nchw, int B, int C, int S, int margin, const int32_t* tiles, int x_lo, int x_hi,
                                int y_lo, int y_hi, float* raster_out, int raster_h, int raster_w, void* stream);
 
+/* Test-time augmentation over the D4 group of the training augmentation (csrc/tta.hip).  `code` is the packing of
+ * d4_flags above: bit 0 V-flip, bit 1 H-flip, bits 2-3 the rot90 count k; T = rot90^k(hflip(vflip(.))), numpy's counter-clockwise
+ * rot90.  Codes outside 0..15 return -2, an odd k with H != W returns -19, null tensors -1; nothing is launched then.
+ * flair_d4_nchw_f32: out = T(in) for fp32 (B, C, H, W), out of place (in == out returns -1): a pure permutation.
+ * flair_tta_accum: one pass of the ensemble S = sum over codes of T^-1(softmax(f(T(x)))).  logits_nchw (B, C, H, W) are the
+ *   model's logits of T(x); their per-pixel softmax (flair_softmax_argmax's arithmetic) is added into acc_nchw fp32 (B, C, H, W)
+ *   at the pixel of x it belongs to.  first != 0: stored instead of added (acc may hold anything).  preds_u8 != NULL marks the
+ *   last of n passes (n in 1..16): the sum is finished in registers, preds_u8 (B, H, W) = the lowest class of the largest sum,
+ *   the optional prob_f32 (B, H, W) = that sum / n (fp32 division), and acc is not written.  A pass that is first and last never
+ *   touches acc (which may be NULL then and only then).  prob_f32 without preds_u8 returns -1; C outside 1..32 or n outside
+ *   1..16 returns -2.  No atomics: the sum at a pixel is the same fp32 additions in pass order on every run.
+ * flair_tta_accum_q4: the same over QUARTER-resolution logits (B, C, H/4, W/4), resized x4 per pixel as the _q4 family above
+ *   does (H == W, H % 4 == 0, else -2); acc, preds and prob stay (B, ., H, W). */
+int flair_d4_nchw_f32(const float* in_nchw, float* out_nchw, int B, int C, int H, int W, int code, void* stream);
+int flair_tta_accum(const float* logits_nchw, int B, int C, int H, int W, int code, int first, float* acc_nchw, uint8_t* preds_u8,
+                    float* prob_f32, int n, void* stream);
+int flair_tta_accum_q4(const float* logits_nchw, int B, int C, int H, int W, int code, int first, float* acc_nchw, uint8_t* preds_u8,
+                       float* prob_f32, int n, void* stream);
+
 /* zone_detect's comparison metrics against a ground-truth raster (src/zone_detect/test/metrics.py; csrc/zone_metrics.hip).
  * truth_u8 (raster_h, raster_w): the stored label raster; its class is (truth - 1) in uint8 arithmetic, so a 0 becomes 255.
  * Every count is sklearn's confusion_matrix(truth - 1, pred, labels=range(C)): rows truth, columns prediction, pairs with a
