@@ -360,6 +360,23 @@ int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void*
   if (!params || !grads) return -1;
   return sgd_step(params, grads, n, lr, (hipStream_t)stream);
 }
+int flair_optim_sgd(float* params, const float* grads, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                    float weight_decay, int nesterov, int first, float grad_scale, const float* coef, void* stream) {
+  return optim_sgd(params, grads, momentum_buf, n, lr, momentum, dampening, weight_decay, nesterov, first, grad_scale, coef,
+                   (hipStream_t)stream);
+}
+int flair_optim_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float bc1, float bc2, int first, float grad_scale, const float* coef, void* stream) {
+  return optim_adamw(params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2, first, grad_scale, coef,
+                     (hipStream_t)stream);
+}
+int flair_grad_sqnorm_partials(void) { return grad_sqnorm_partials(); }
+int flair_grad_sqnorm(const float* grads, int64_t n, double* partials, double* sum, int accumulate, void* stream) {
+  return grad_sqnorm(grads, n, partials, sum, accumulate, (hipStream_t)stream);
+}
+int flair_clip_coef(const double* sum, float grad_scale, float max_norm, float* norm, float* coef, void* stream) {
+  return clip_coef(sum, grad_scale, max_norm, norm, coef, (hipStream_t)stream);
+}
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream) {
   if (!x || !v) return -1;
   return add_rowvec_nchw(x, v, N, C, H, W, (hipStream_t)stream);

@@ -73,6 +73,15 @@ int ew_add(int dtype, void* dst, const void* src, long n, hipStream_t s);
 int fill_zero(void* p, size_t bytes, hipStream_t s);
 int fill_f32(float* p, long n, float v, hipStream_t s);
 
+// ---- optim.hip: update rules over a flat fp32 buffer.  g' = g * grad_scale * coef (coef: optional device float)
+int optim_sgd(float* params, const float* grads, float* buf, long n, float lr, float momentum, float dampening, float weight_decay,
+              int nesterov, int first, float grad_scale, const float* coef, hipStream_t s);
+int optim_adamw(float* params, const float* grads, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                float weight_decay, float bc1, float bc2, int first, float grad_scale, const float* coef, hipStream_t s);
+int grad_sqnorm_partials();   // fp64 elements of grad_sqnorm's workspace
+int grad_sqnorm(const float* grads, long n, double* partials, double* sum, int accumulate, hipStream_t s);
+int clip_coef(const double* sum, float grad_scale, float max_norm, float* norm, float* coef, hipStream_t s);
+
 // ---- ce_head.hip
 struct CeArgs {
   const float* logits;        // NCHW fp32 [B][C][H][W]   (or null with logits_nhwc set)

@@ -57,6 +57,11 @@ PROTOTYPES = {
                                  C.POINTER(C.c_double), vp, vp]),
     "flair_detect_stitch": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
     "flair_sgd_step": (i32, [vp, vp, i64, f32, vp]),
+    "flair_optim_sgd": (i32, [vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, f32, vp, vp]),
+    "flair_optim_adamw": (i32, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, i32, f32, vp, vp]),
+    "flair_grad_sqnorm_partials": (i32, []),
+    "flair_grad_sqnorm": (i32, [vp, i64, vp, vp, i32, vp]),
+    "flair_clip_coef": (i32, [vp, f32, f32, vp, vp, vp]),
     "flair_add_rowvec_nchw": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "flair_add_rowvec_nhwc": (i32, [i32, vp, vp, i32, i32, i32, i32, vp]),
     "flair_add_rowvec_nhwc_to": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -662,6 +662,91 @@ def sgd_step_(params_flat, grads_flat, lr):
     L.check(L.lib().flair_sgd_step(L.ptr(params_flat), L.ptr(grads_flat), params_flat.numel(), float(lr), L.stream()), "sgd_step")
 
 
+# ---- update rules over flat fp32 buffers (flair_optim_* / flair_grad_sqnorm / flair_clip_coef of include/flair_hip.h)
+def _check_flat_f32(n, **tensors):
+    for name, t in tensors.items():
+        if t is not None and (t.dim() != 1 or t.dtype != torch.float32 or t.numel() != n):
+            raise ValueError(f"{name} must be fp32 ({n},), got {t.dtype} {tuple(t.shape)}")
+
+
+def _check_coef(coef):
+    if coef is not None and (coef.dtype != torch.float32 or coef.numel() != 1):
+        raise ValueError("coef must be one fp32 device value")
+
+
+def optim_sgd_(params, grads, buf, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, first=False, grad_scale=1.0,
+               coef=None):
+    """torch.optim.SGD's rule on flat buffers, in place on ``params`` and ``buf`` (the momentum buffer; None without momentum):
+    g' = grads * grad_scale * coef, then weight decay, momentum (``first``: buf = g', its content unread), nesterov, p -= lr g'."""
+    if params.dim() != 1 or params.dtype != torch.float32:
+        raise ValueError("optim_sgd_ takes flat fp32 buffers")
+    n = params.numel()
+    _check_flat_f32(n, grads=grads, buf=buf)
+    _check_coef(coef)
+    if momentum != 0 and buf is None:
+        raise ValueError("momentum needs its buffer")
+    if nesterov and (momentum <= 0 or dampening != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+    L.check(L.lib().flair_optim_sgd(L.ptr(params), L.ptr(grads), L.ptr(buf), n, float(lr), float(momentum), float(dampening),
+                                    float(weight_decay), int(bool(nesterov)), int(bool(first)), float(grad_scale), L.ptr(coef),
+                                    L.stream()), "optim_sgd")
+
+
+def adamw_bias_corrections(betas, step):
+    """(1 - beta1^t, 1 - beta2^t) in fp64, as the host hands them to flair_optim_adamw"""
+    return 1.0 - float(betas[0]) ** int(step), 1.0 - float(betas[1]) ** int(step)
+
+
+def optim_adamw_(params, grads, exp_avg, exp_avg_sq, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, step=1, first=False,
+                 grad_scale=1.0, coef=None):
+    """torch.optim.AdamW's rule on flat buffers, in place on ``params``, ``exp_avg`` and ``exp_avg_sq``; ``step`` is t of the bias
+    corrections (1-based), ``first`` takes both moments as zero whatever the buffers hold."""
+    if params.dim() != 1 or params.dtype != torch.float32:
+        raise ValueError("optim_adamw_ takes flat fp32 buffers")
+    n = params.numel()
+    _check_flat_f32(n, grads=grads, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+    _check_coef(coef)
+    if exp_avg is None or exp_avg_sq is None:
+        raise ValueError("AdamW needs both moment buffers")
+    if int(step) < 1:
+        raise ValueError(f"step counts from 1, got {step}")
+    bc1, bc2 = adamw_bias_corrections(betas, step)
+    L.check(L.lib().flair_optim_adamw(L.ptr(params), L.ptr(grads), L.ptr(exp_avg), L.ptr(exp_avg_sq), n, float(lr), float(betas[0]),
+                                      float(betas[1]), float(eps), float(weight_decay), bc1, bc2, int(bool(first)), float(grad_scale),
+                                      L.ptr(coef), L.stream()), "optim_adamw")
+
+
+def grad_sqnorm_partials():
+    return int(L.lib().flair_grad_sqnorm_partials())
+
+
+def grad_sqnorm_(grads, sq_sum, partials, accumulate=False):
+    """sq_sum (one fp64 device value) = (its content if ``accumulate`` else 0) + sum of grads^2; ``partials``: fp64 workspace of
+    grad_sqnorm_partials() elements.  Fixed summation order: the same bits on every run."""
+    if grads.dim() != 1 or grads.dtype != torch.float32:
+        raise ValueError("grad_sqnorm_ takes a flat fp32 buffer")
+    if sq_sum.dtype != torch.float64 or sq_sum.numel() != 1:
+        raise ValueError("sq_sum must be one fp64 device value")
+    if partials.dtype != torch.float64 or partials.numel() < grad_sqnorm_partials():
+        raise ValueError(f"partials must hold {grad_sqnorm_partials()} fp64 values")
+    L.check(L.lib().flair_grad_sqnorm(L.ptr(grads), grads.numel(), L.ptr(partials), L.ptr(sq_sum), int(bool(accumulate)), L.stream()),
+            "grad_sqnorm")
+    return sq_sum
+
+
+def clip_coef_(sq_sum, max_norm, norm, coef, grad_scale=1.0):
+    """clip_grad_norm_'s rule from the fp64 sum of squares: norm = sqrt(sq_sum) * grad_scale, coef = min(1, max_norm / (norm + 1e-6)),
+    both written as fp32 device values; nothing comes back to the host."""
+    if sq_sum.dtype != torch.float64 or sq_sum.numel() != 1:
+        raise ValueError("sq_sum must be one fp64 device value")
+    for name, t in (("norm", norm), ("coef", coef)):
+        if t.dtype != torch.float32 or t.numel() != 1:
+            raise ValueError(f"{name} must be one fp32 device value")
+    if not float(max_norm) > 0:
+        raise ValueError(f"max_norm must be positive, got {max_norm}")
+    L.check(L.lib().flair_clip_coef(L.ptr(sq_sum), float(grad_scale), float(max_norm), L.ptr(norm), L.ptr(coef), L.stream()), "clip_coef")
+
+
 # ---- the SegFormer / UperNet-Swin kernels one at a time (the launchers the two executors call).  `rc=True` returns the
 # launcher's return code instead of raising, so that a refusal (-2) can be asserted.
 def _ret(rc, what, out, want_rc):

@@ -22,6 +22,7 @@ from torch.optim.lr_scheduler import ReduceLROnPlateau
 from .data_feed import TileFeed
 from .head import FusedCrossEntropyLoss
 from .model import FLAIR_ModelFactory
+from .optim import torch_optimizer_from_config
 from .task_module import segmentation_task_predict, segmentation_task_training
 
 
@@ -44,7 +45,8 @@ def get_segmentation_module(config, stage: str = "train", compute_dtype=None):
             criterion = FusedCrossEntropyLoss(weight=class_weights)
         else:
             criterion = FusedCrossEntropyLoss()
-        optimizer = torch.optim.SGD(model.parameters(), lr=config["learning_rate"])
+        # optional config key ``optimizer: {name: sgd|adamw, ...}``; without it the reference's torch.optim.SGD(lr)
+        optimizer = torch_optimizer_from_config(config, model.parameters())
         scheduler = ReduceLROnPlateau(optimizer=optimizer, mode="min", factor=0.5, patience=10, cooldown=4, min_lr=1e-7)
         return segmentation_task_training(model=model, class_infos=config["classes"], criterion=criterion,
                                           optimizer=optimizer, scheduler=scheduler, use_metadata=config["use_metadata"])

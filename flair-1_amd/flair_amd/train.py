@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import ops
+from . import optim as _optim
 from .model import check_metadata_tile
 from .tta import tta_codes
 
@@ -85,7 +86,12 @@ class SegTrainer:
     """Owns the flat gradient buffer, the fused head outputs and the RCCL exchange for one rank."""
 
     def __init__(self, model, lr, class_weight=None, group=None, overlap=True, min_bucket_elems=1 << 18,
-                 force_exchange=False, broadcast_buffers=True, class_names=None, metadata_encoder=None):
+                 force_exchange=False, broadcast_buffers=True, class_names=None, metadata_encoder=None,
+                 optimizer=None, clip_grad_norm=None, params=None):
+        """``optimizer``: a ``flair_amd.optim.SGD`` / ``AdamW`` specification; ``clip_grad_norm``: clip_grad_norm_'s max_norm over
+        the U-Net's and the MetadataMLP's gradients together; ``params``: the parameter order of ``optimizer_state_dict()``
+        (default ``list(model.parameters()) + list(metadata_encoder.parameters())``).  With neither of the first two the step is
+        the reference's plain SGD (tasks_utils.py:95), call for call what it was before they existed."""
         self.model = model
         # a MetadataMLP (BASELINE config 4): train_step / validate_step / predict add its encoding to the bottleneck inside their one
         # native call; train_step(..., mtd) also trains it
@@ -134,6 +140,134 @@ class SegTrainer:
             self._bucket_stage = [min(s for s, (b, e) in enumerate(sr) if b >= bb and e <= be and e > b) for bb, be in self.buckets]
             dist.broadcast(p, src=self._src0, group=group)  # DDP's initial parameter broadcast
             dist.broadcast(model.flat_buffers(), src=self._src0, group=group)
+        self.optimizer = None
+        self.grad_norm = None
+        if optimizer is not None or clip_grad_norm is not None:
+            self._init_optimizer(_optim.SGD() if optimizer is None else optimizer, clip_grad_norm, params)
+
+    # ------------------------------------------------------------------------------ optimizer path (flair_amd.optim)
+    def _init_optimizer(self, spec, clip_grad_norm, params):
+        if not isinstance(spec, (_optim.SGD, _optim.AdamW)):
+            raise TypeError("optimizer must be a flair_amd.optim.SGD or AdamW specification (torch.optim objects drive the "
+                            "LightningModule surface, not the fused trainer)")
+        if clip_grad_norm is not None and not float(clip_grad_norm) > 0:
+            raise ValueError(f"clip_grad_norm must be positive, got {clip_grad_norm}")
+        m = self.model
+        dev = self.grads.device
+        self._spec = spec
+        self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
+        self._opt = _optim.FlatOptimizer(spec, m.flat_parameters(), list(m.parameters()))
+        self._mlp_opt = None
+        # the norm leaves out the padding between stages of the flat buffer (every stage starts on 4 floats): maximal runs of
+        # tensors, each starting on a 16-byte boundary
+        spans = sorted((self._opt.offset(p), self._opt.offset(p) + p.numel()) for p in m.parameters())
+        runs = []
+        for b, e in spans:
+            if runs and runs[-1][1] == b:
+                runs[-1][1] = e
+            else:
+                runs.append([b, e])
+        self._norm_runs = [(b, e) for b, e in runs]
+        if self.clip_grad_norm is not None:
+            self._sq = torch.zeros(1, dtype=torch.float64, device=dev)
+            self._sq_partials = torch.empty(ops.grad_sqnorm_partials(), dtype=torch.float64, device=dev)
+            self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
+            self.grad_norm = self._clip[0]
+            self._coef = self._clip[1:2]
+        else:
+            self._coef = None
+        enc = self.metadata_encoder
+        plist = list(params) if params is not None else list(m.parameters()) + ([] if enc is None else list(enc.parameters()))
+        self.optimizer = _optim.TrainerOptimizer(spec, self._flat_optimizers, plist, lambda: self.lr,
+                                                 lambda v: setattr(self, "lr", v))
+        if enc is not None and all(p.device == dev for p in enc.parameters()):
+            self._bind_mlp()
+
+    def _flat_optimizers(self):
+        return [o for o in (self._opt, self._mlp_opt) if o is not None]
+
+    def _bind_mlp(self):
+        """Make the MetadataMLP's trainable tensors views of one flat buffer (as Unet.flatten_ does for the U-Net) and bind the
+        second flat optimizer over it; state already held survives a rebind after the module was moved."""
+        ps = [p for p in self.metadata_encoder.parameters() if p.requires_grad]
+        old = self._mlp_opt
+        if old is not None and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps)):
+            try:
+                offs = [old.offset(p) for p in ps]
+                if offs == self._mlp_offs:
+                    return ps
+            except ValueError:
+                pass
+        if any(p.numel() % 4 for p in ps):
+            raise ValueError("the flat optimizer takes tensors of whole 16-byte chunks (numel % 4 == 0)")
+        dev = self.grads.device
+        flat = torch.zeros(sum(p.numel() for p in ps), dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            o = 0
+            for p in ps:
+                v = flat[o:o + p.numel()].view(p.shape)
+                v.copy_(p.detach().to(device=dev, dtype=torch.float32))
+                p.data = v
+                o += p.numel()
+        new = _optim.FlatOptimizer(self._spec, flat, ps)
+        if old is not None and len(old.params) == len(ps):   # same tensors at new addresses: the state moves along
+            for a, b in zip(new.state, old.state):
+                a.copy_(b)
+            new.steps = old.steps
+        self._mlp_opt = new
+        self._mlp_offs = [new.offset(p) for p in ps]
+        return ps
+
+    def optimizer_state_dict(self):
+        """torch.optim's format (``state``: momentum_buffer, or step / exp_avg / exp_avg_sq, clones shaped like their parameter;
+        ``param_groups`` with torch's keys) over the ``params`` order: loads into torch.optim.SGD / AdamW over the same parameters."""
+        if self.optimizer is None:
+            raise ValueError("SegTrainer was built without optimizer= / clip_grad_norm=: plain SGD has no state")
+        return self.optimizer.state_dict()
+
+    def load_optimizer_state_dict(self, sd):
+        if self.optimizer is None:
+            raise ValueError("SegTrainer was built without optimizer= / clip_grad_norm=: plain SGD has no state")
+        if self.metadata_encoder is not None:
+            if any(p.device != self.grads.device for p in self.metadata_encoder.parameters()):
+                raise ValueError("move the metadata_encoder to the trainer's device before loading optimizer state")
+            self._bind_mlp()
+        self.optimizer.load_state_dict(sd)
+
+    def _optim_step(self, rows):
+        """The update on the optimizer path, behind the waited-for all-reduces: the MetadataMLP's backward and exchange, one norm
+        over both gradients (when clipping), then one kernel per flat buffer.  DDP's average is grad_scale = 1 / world on the
+        gradient -- folding it into lr, as the plain step does, is wrong under weight decay or Adam."""
+        m = self.model
+        if m._flat_p is not self._opt.flat:
+            raise RuntimeError("the model's flat parameter buffer was rebuilt (moved or re-flattened) behind the optimizer: "
+                               "build a new SegTrainer and load optimizer_state_dict() into it")
+        gs = 1.0 / self.world
+        mlp = None
+        if rows is not None:
+            ps = self._bind_mlp()
+            if ps:
+                for p in ps:
+                    p.grad = None
+                rows.backward(self._drows)
+                flat = torch.cat([p.grad.reshape(-1) for p in ps])
+                if self.exchange and not self._no_collective:
+                    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
+                self.mlp_grads = flat
+                for p in ps:
+                    p.grad = None
+                mlp = flat
+        if self.clip_grad_norm is not None:
+            acc = False
+            for b, e in self._norm_runs:
+                ops.grad_sqnorm_(self.grads[b:e], self._sq, self._sq_partials, accumulate=acc)
+                acc = True
+            if mlp is not None:
+                ops.grad_sqnorm_(mlp, self._sq, self._sq_partials, accumulate=True)
+            ops.clip_coef_(self._sq, self.clip_grad_norm, self._clip[0:1], self._coef, grad_scale=gs)
+        self._opt.step(self.grads, self.lr, grad_scale=gs, coef=self._coef)
+        if mlp is not None:
+            self._mlp_opt.step(mlp, self.lr, grad_scale=gs, coef=self._coef)
 
     def _buffers(self, B, H, W):
         m = self.model
@@ -236,6 +370,10 @@ class SegTrainer:
                 allreduce_buckets(self.grads, self.buckets, self.group)
                 if self.sync_buffers:
                     dist.broadcast(m.flat_buffers(), src=self._src0, group=self.group)
+        if self.optimizer is not None:
+            self._optim_step(rows)
+            m._eval.note_native_write()
+            return self.loss
         if rows is not None:
             self._mlp_step(rows)
         # DDP averages: fold 1/world into the step size

@@ -417,6 +417,31 @@ int flair_tiff_chunks_to_batch(const uint8_t* scratch, long slot_bytes, const in
                                int max_rows, uint8_t* planes, int n_planes, int H, int W, void* stream);
 
 int flair_sgd_step(float* params, const float* grads, int64_t n, float lr, void* stream);
+
+/* Update rules of the fused trainer over one flat fp32 buffer of n elements (csrc/optim.hip, DESIGN §10 "Optimizers").  One pass
+ * each, no atomics, no host sync.  In both rules the gradient enters as g' = g * grad_scale * coef; coef is read from a device float
+ * when the pointer is non-NULL (flair_clip_coef writes one), else it is 1.  grads is never written; params and the state buffers are
+ * updated in place.  All tensor pointers 16-byte aligned.
+ * flair_optim_sgd: torch.optim.SGD's single-tensor rule.  weight_decay != 0: g' += weight_decay * p.  momentum != 0: buf = g' on a
+ *   first step (first != 0; the buffer's content is not read), else buf = momentum * buf + (1 - dampening) * g'; then
+ *   g' = nesterov ? g' + momentum * buf : buf.  p -= lr * g'.  momentum_buf may be NULL when momentum == 0.  With momentum ==
+ *   weight_decay == 0, grad_scale == 1 and coef == NULL the result is flair_sgd_step's to the bit.
+ * flair_optim_adamw: torch.optim.AdamW's single-tensor rule (decoupled decay, no amsgrad, no maximize): m += (g' - m)(1 - beta1),
+ *   v = beta2 v + (1 - beta2) g'^2, p = p (1 - lr weight_decay) - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).  bc1 = 1 - beta1^t and
+ *   bc2 = 1 - beta2^t come from the host.  first != 0 takes m and v as zero whatever the buffers hold.
+ * flair_grad_sqnorm: *sum = (accumulate ? *sum : 0) + sum of g^2, in fp64.  A grid that depends on n alone writes one fp64 partial
+ *   per block into `partials` (flair_grad_sqnorm_partials() doubles), one block adds them in index order: the same bits every run.
+ * flair_clip_coef: *norm = (float)(sqrt(*sum) * grad_scale), *coef = min(1, max_norm / (*norm + 1e-6)) -- clip_grad_norm_'s rule.
+ * Returns -1 for a NULL required pointer or n < 0; -2 for a misaligned pointer, nesterov with momentum == 0 or dampening != 0, a
+ * negative lr / momentum / weight_decay / eps, a beta outside [0, 1), bc1 or bc2 <= 0, max_norm or grad_scale <= 0.  Nothing is
+ * launched then. */
+int flair_optim_sgd(float* params, const float* grads, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                    float weight_decay, int nesterov, int first, float grad_scale, const float* coef, void* stream);
+int flair_optim_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                      float eps, float weight_decay, float bc1, float bc2, int first, float grad_scale, const float* coef, void* stream);
+int flair_grad_sqnorm_partials(void);
+int flair_grad_sqnorm(const float* grads, int64_t n, double* partials, double* sum, int accumulate, void* stream);
+int flair_clip_coef(const double* sum, float grad_scale, float max_norm, float* norm, float* coef, void* stream);
 /* feats[-1] += x_enc.unsqueeze(1).unsqueeze(-1).repeat(1,512,1,16) — model.py:59-60: x (N,C,H,W) += v (N,H). */
 int flair_add_rowvec_nchw(float* x, const float* v, int N, int C, int H, int W, void* stream);
 /* The same add, in place, on an NHWC tensor of the compute dtype (the layout the executor keeps its features in):
