@@ -8,12 +8,12 @@ native handle, and allocates the outputs of its own forward.
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import flat as _flat
 
 
 def tensor_of(root, name):
@@ -98,32 +98,17 @@ class NativeModel(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise L.FlairHipError(f"flair_amd.{type(self).__name__} runs on a HIP device only: call .cuda() first")
-        ok = self._flat is not None and self._flat.device == dev
-        if ok:
-            base = self._flat.data_ptr()
-            version = 0
-            for name, (shape, off, _) in self._layout.items():
-                t = getattr(*tensor_of(self, name))
-                if t.data_ptr() != base + 4 * off or t.dtype != torch.float32:
-                    ok = False
-                    break
-                version += t._version
-        if ok:
+        items = [(getattr(*tensor_of(self, name)), off, shape) for name, (shape, off, _) in self._layout.items()]
+        if _flat.aliased(self._flat, (i[:2] for i in items)):
+            version = sum(t._version for t, _, _ in items)
             if version != self._seen_version:   # an in-place update (load_state_dict, copy_, ...) since the last forward:
                 self.weights_changed()          # the library re-packs its cached weight layouts
                 self._seen_version = version
             return self._flat
-        flat = torch.zeros(self._n, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for name, (shape, off, _) in self._layout.items():
-                t = getattr(*tensor_of(self, name))
-                view = flat[off:off + math.prod(shape)].view(shape)
-                view.copy_(t.detach().to(device=dev, dtype=torch.float32))
-                t.data = view
-        self._flat = flat
-        self._seen_version = sum(getattr(*tensor_of(self, name))._version for name in self._layout)
+        self._flat = _flat.bind(items, self._n, dev)
+        self._seen_version = sum(t._version for t, _, _ in items)
         self.weights_changed()
-        return flat
+        return self._flat
 
     def weights_changed(self):
         """The library keeps packed copies of the weights between forwards; in-place updates through the module's parameters are

@@ -1,9 +1,10 @@
-"""Update rules of the fused trainer (``SegTrainer(..., optimizer=...)``): momentum SGD and AdamW over flat buffers.
+"""Update rules of the fused trainer: plain and momentum SGD and AdamW over flat buffers.  Every ``SegTrainer`` steps through a
+``FlatOptimizer``; without ``optimizer=`` its specification is ``SGD()``, the reference's rule, which has no state buffers.
 
 ``SGD`` and ``AdamW`` are specifications: hyper-parameters without tensors, validated by torch.optim's own rules and messages.
 ``FlatOptimizer`` binds one to a flat fp32 parameter buffer, to state buffers of the same length allocated beside it and to the
 ordered ``nn.Parameter`` views of that buffer; its ``step`` is one HIP kernel over the whole buffer (csrc/optim.hip: no per-tensor
-launches, no host sync).  ``TrainerOptimizer`` is what ``SegTrainer.optimizer`` exposes: ``state_dict()`` /
+launches, no host sync).  ``TrainerOptimizer`` is what ``SegTrainer.optimizer`` exposes when a rule was asked for: ``state_dict()`` /
 ``load_state_dict()`` in torch.optim's format over a chosen parameter order, so ``checkpoint.save_checkpoint`` / ``resume`` and
 ``torch.optim.SGD`` / ``AdamW`` exchange state with the fused trainer.
 

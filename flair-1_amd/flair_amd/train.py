@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from . import flat as _flat
 from . import ops
 from . import optim as _optim
 from .model import check_metadata_tile
@@ -82,6 +83,16 @@ def shard_indices(n_items, rank, world, epoch_seed=0, shuffle=True, drop_last=Fa
     return idx[rank::world]
 
 
+def update_scales(lr, world, fold):
+    """(lr, grad_scale) of one update from the gradient summed over ``world`` ranks."""
+    # DDP's average is grad_scale = 1 / world on the gradient.  Folding it into lr instead -- p -= (lr / world) * sum of g, one
+    # rounding fewer, what a trainer built with neither optimizer= nor clip_grad_norm= computes -- is only right for the rule without
+    # weight decay and without momentum: decay would be scaled down with the step, a momentum buffer would hold (and save) sums
+    # for averages, and Adam's step does not scale with its gradient at all.  The two differ in the last bit when world is no
+    # power of two, so neither replaces the other.
+    return (lr / world, 1.0) if fold else (lr, 1.0 / world)
+
+
 class SegTrainer:
     """Owns the flat gradient buffer, the fused head outputs and the RCCL exchange for one rank."""
 
@@ -91,7 +102,8 @@ class SegTrainer:
         """``optimizer``: a ``flair_amd.optim.SGD`` / ``AdamW`` specification; ``clip_grad_norm``: clip_grad_norm_'s max_norm over
         the U-Net's and the MetadataMLP's gradients together; ``params``: the parameter order of ``optimizer_state_dict()``
         (default ``list(model.parameters()) + list(metadata_encoder.parameters())``).  With neither of the first two the step is
-        the reference's plain SGD (tasks_utils.py:95), call for call what it was before they existed."""
+        the reference's plain SGD (tasks_utils.py:95), ``optim.SGD()`` through the same kernel, with ``optimizer`` left None and
+        DDP's average folded into the step size (``update_scales``)."""
         self.model = model
         # a MetadataMLP (BASELINE config 4): train_step / validate_step / predict add its encoding to the bottleneck inside their one
         # native call; train_step(..., mtd) also trains it
@@ -140,12 +152,10 @@ class SegTrainer:
             self._bucket_stage = [min(s for s, (b, e) in enumerate(sr) if b >= bb and e <= be and e > b) for bb, be in self.buckets]
             dist.broadcast(p, src=self._src0, group=group)  # DDP's initial parameter broadcast
             dist.broadcast(model.flat_buffers(), src=self._src0, group=group)
-        self.optimizer = None
-        self.grad_norm = None
-        if optimizer is not None or clip_grad_norm is not None:
-            self._init_optimizer(_optim.SGD() if optimizer is None else optimizer, clip_grad_norm, params)
+        self._fold = optimizer is None and clip_grad_norm is None   # the plain trainer: see update_scales
+        self._init_optimizer(_optim.SGD() if optimizer is None else optimizer, clip_grad_norm, params)
 
-    # ------------------------------------------------------------------------------ optimizer path (flair_amd.optim)
+    # ------------------------------------------------------------------------------ the update (flair_amd.optim)
     def _init_optimizer(self, spec, clip_grad_norm, params):
         if not isinstance(spec, (_optim.SGD, _optim.AdamW)):
             raise TypeError("optimizer must be a flair_amd.optim.SGD or AdamW specification (torch.optim objects drive the "
@@ -158,28 +168,29 @@ class SegTrainer:
         self.clip_grad_norm = None if clip_grad_norm is None else float(clip_grad_norm)
         self._opt = _optim.FlatOptimizer(spec, m.flat_parameters(), list(m.parameters()))
         self._mlp_opt = None
-        # the norm leaves out the padding between stages of the flat buffer (every stage starts on 4 floats): maximal runs of
-        # tensors, each starting on a 16-byte boundary
-        spans = sorted((self._opt.offset(p), self._opt.offset(p) + p.numel()) for p in m.parameters())
-        runs = []
-        for b, e in spans:
-            if runs and runs[-1][1] == b:
-                runs[-1][1] = e
-            else:
-                runs.append([b, e])
-        self._norm_runs = [(b, e) for b, e in runs]
+        self.grad_norm = self._coef = None
         if self.clip_grad_norm is not None:
+            # the norm leaves out the padding between stages of the flat buffer (every stage starts on 4 floats): maximal runs of
+            # tensors, each starting on a 16-byte boundary
+            spans = sorted((self._opt.offset(p), self._opt.offset(p) + p.numel()) for p in m.parameters())
+            runs = []
+            for b, e in spans:
+                if runs and runs[-1][1] == b:
+                    runs[-1][1] = e
+                else:
+                    runs.append([b, e])
+            self._norm_runs = [(b, e) for b, e in runs]
             self._sq = torch.zeros(1, dtype=torch.float64, device=dev)
             self._sq_partials = torch.empty(ops.grad_sqnorm_partials(), dtype=torch.float64, device=dev)
             self._clip = torch.zeros(2, dtype=torch.float32, device=dev)
             self.grad_norm = self._clip[0]
             self._coef = self._clip[1:2]
-        else:
-            self._coef = None
         enc = self.metadata_encoder
-        plist = list(params) if params is not None else list(m.parameters()) + ([] if enc is None else list(enc.parameters()))
-        self.optimizer = _optim.TrainerOptimizer(spec, self._flat_optimizers, plist, lambda: self.lr,
-                                                 lambda v: setattr(self, "lr", v))
+        self.optimizer = None   # the plain trainer shows none: its rule has no state to save
+        if not self._fold:
+            plist = list(params) if params is not None else list(m.parameters()) + ([] if enc is None else list(enc.parameters()))
+            self.optimizer = _optim.TrainerOptimizer(spec, self._flat_optimizers, plist, lambda: self.lr,
+                                                     lambda v: setattr(self, "lr", v))
         if enc is not None and all(p.device == dev for p in enc.parameters()):
             self._bind_mlp()
 
@@ -187,36 +198,24 @@ class SegTrainer:
         return [o for o in (self._opt, self._mlp_opt) if o is not None]
 
     def _bind_mlp(self):
-        """Make the MetadataMLP's trainable tensors views of one flat buffer (as Unet.flatten_ does for the U-Net) and bind the
-        second flat optimizer over it; state already held survives a rebind after the module was moved."""
+        """Make the MetadataMLP's trainable tensors views of one flat buffer, in parameters() order, and bind the second flat
+        optimizer over it; state already held survives a rebind after the module was moved."""
         ps = [p for p in self.metadata_encoder.parameters() if p.requires_grad]
+        offs = [0]
+        for p in ps:
+            offs.append(offs[-1] + p.numel())
         old = self._mlp_opt
-        if old is not None and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps)):
-            try:
-                offs = [old.offset(p) for p in ps]
-                if offs == self._mlp_offs:
-                    return ps
-            except ValueError:
-                pass
+        same = old is not None and len(old.params) == len(ps) and all(a is b for a, b in zip(old.params, ps))
+        if same and _flat.aliased(old.flat, zip(ps, offs)):
+            return
         if any(p.numel() % 4 for p in ps):
             raise ValueError("the flat optimizer takes tensors of whole 16-byte chunks (numel % 4 == 0)")
-        dev = self.grads.device
-        flat = torch.zeros(sum(p.numel() for p in ps), dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            o = 0
-            for p in ps:
-                v = flat[o:o + p.numel()].view(p.shape)
-                v.copy_(p.detach().to(device=dev, dtype=torch.float32))
-                p.data = v
-                o += p.numel()
-        new = _optim.FlatOptimizer(self._spec, flat, ps)
+        new = _optim.FlatOptimizer(self._spec, _flat.bind([(p, o, p.shape) for p, o in zip(ps, offs)], offs[-1], self.grads.device), ps)
         if old is not None and len(old.params) == len(ps):   # same tensors at new addresses: the state moves along
             for a, b in zip(new.state, old.state):
                 a.copy_(b)
             new.steps = old.steps
         self._mlp_opt = new
-        self._mlp_offs = [new.offset(p) for p in ps]
-        return ps
 
     def optimizer_state_dict(self):
         """torch.optim's format (``state``: momentum_buffer, or step / exp_avg / exp_avg_sq, clones shaped like their parameter;
@@ -234,29 +233,32 @@ class SegTrainer:
             self._bind_mlp()
         self.optimizer.load_state_dict(sd)
 
-    def _optim_step(self, rows):
-        """The update on the optimizer path, behind the waited-for all-reduces: the MetadataMLP's backward and exchange, one norm
-        over both gradients (when clipping), then one kernel per flat buffer.  DDP's average is grad_scale = 1 / world on the
-        gradient -- folding it into lr, as the plain step does, is wrong under weight decay or Adam."""
+    def _step(self, rows):
+        """The update, behind the waited-for all-reduces: the MetadataMLP's backward from the row gradient the native backward left
+        in ``_drows`` and the exchange of its gradients, one norm over both gradients (when clipping), then one kernel per flat buffer."""
         m = self.model
         if m._flat_p is not self._opt.flat:
-            raise RuntimeError("the model's flat parameter buffer was rebuilt (moved or re-flattened) behind the optimizer: "
-                               "build a new SegTrainer and load optimizer_state_dict() into it")
-        gs = 1.0 / self.world
+            if self._spec.n_state:
+                raise RuntimeError("the model's flat parameter buffer was rebuilt (moved or re-flattened) behind the optimizer: "
+                                   "build a new SegTrainer and load optimizer_state_dict() into it")
+            steps = self._opt.steps   # a rule without state follows the buffer
+            self._opt = _optim.FlatOptimizer(self._spec, m._flat_p, list(m.parameters()))
+            self._opt.steps = steps
+        lr, gs = update_scales(self.lr, self.world, self._fold)
         mlp = None
-        if rows is not None:
-            ps = self._bind_mlp()
-            if ps:
-                for p in ps:
-                    p.grad = None
-                rows.backward(self._drows)
-                flat = torch.cat([p.grad.reshape(-1) for p in ps])
-                if self.exchange and not self._no_collective:
-                    dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
-                self.mlp_grads = flat
-                for p in ps:
-                    p.grad = None
-                mlp = flat
+        if rows is not None and self._mlp_opt.params:
+            ps = self._mlp_opt.params
+            for p in ps:
+                p.grad = None
+            rows.backward(self._drows)
+            # one flat buffer (every tensor's size is a multiple of 4 floats: whole 16-byte chunks for the kernel)
+            mlp = torch.cat([p.grad.reshape(-1) for p in ps])
+            if self.exchange and not self._no_collective:
+                # after the backward, outside the overlapped buckets: some 22 KB, nothing to overlap
+                dist.all_reduce(mlp, op=dist.ReduceOp.SUM, group=self.group)
+            self.mlp_grads = mlp   # like ``grads``: the (summed) gradient of the last step, in parameters() order
+            for p in ps:
+                p.grad = None
         if self.clip_grad_norm is not None:
             acc = False
             for b, e in self._norm_runs:
@@ -265,9 +267,9 @@ class SegTrainer:
             if mlp is not None:
                 ops.grad_sqnorm_(mlp, self._sq, self._sq_partials, accumulate=True)
             ops.clip_coef_(self._sq, self.clip_grad_norm, self._clip[0:1], self._coef, grad_scale=gs)
-        self._opt.step(self.grads, self.lr, grad_scale=gs, coef=self._coef)
+        self._opt.step(self.grads, lr, grad_scale=gs, coef=self._coef)
         if mlp is not None:
-            self._mlp_opt.step(mlp, self.lr, grad_scale=gs, coef=self._coef)
+            self._mlp_opt.step(mlp, lr, grad_scale=gs, coef=self._coef)
 
     def _buffers(self, B, H, W):
         m = self.model
@@ -287,12 +289,12 @@ class SegTrainer:
         ``mtd``: (B,45) metadata vectors (BASELINE config 4, model.py:57-62).  ``metadata_encoder`` encodes them in whatever mode it
         is in — the trainer never switches it — and the encoding is added to the bottleneck inside the one native training forward
         (rows_f32 + drows_f32 of flair_unet_fwd_opts_t); the native backward returns its gradient, which goes through the MetadataMLP's own backward
-        kernel, and the MLP's six tensors take the same SGD step as the U-Net's (tasks_utils.py:95 hands the optimizer
-        ``model.parameters()``, the MLP included); their ``.grad`` is None afterwards.  ``mtd_masks``: the three dropout masks of
-        MetadataMLP.forward — "auto" draws them from torch's generator when the encoder is in training mode (none in eval mode),
-        a list is taken as it is, None means no dropout.  With a process group rank 0's MLP parameters are broadcast once, at the
-        first such step, and each step sums the MLP's gradients over the ranks in one flat all-reduce behind the backward.
-        Without ``mtd`` the step is the plain one, whether an encoder was given or not."""
+        kernel, and the MLP's trainable tensors, views of one flat buffer, take the U-Net's update rule in one launch of the same
+        kernel (tasks_utils.py:95 hands the optimizer ``model.parameters()``, the MLP included); their ``.grad`` is None afterwards.
+        ``mtd_masks``: the three dropout masks of MetadataMLP.forward — "auto" draws them from torch's generator when the encoder is
+        in training mode (none in eval mode), a list is taken as it is, None means no dropout.  With a process group rank 0's MLP
+        parameters are broadcast once, at the first such step, and each step sums the MLP's gradients over the ranks in one flat
+        all-reduce behind the backward.  Without ``mtd`` the step leaves the encoder alone, whether one was given or not."""
         with torch.cuda.device(self.grads.device):   # every native call below launches on the current device's stream
             return self._train_step(img, labels, mtd, mtd_masks)
 
@@ -311,31 +313,13 @@ class SegTrainer:
             for p, v in zip(ps, flat.split([p.numel() for p in ps])):
                 p.copy_(v.view_as(p))
         self._mlp_synced = True
+        self._bind_mlp()   # before the forward: it and the backward see one storage
         with torch.enable_grad():
             rows = enc(mtd.to(dev), masks=masks)
         B = img.shape[0]
         if self._drows is None or self._drows.shape != (B, 16):
             self._drows = torch.empty(B, 16, dtype=torch.float32, device=dev)
         return rows
-
-    def _mlp_step(self, rows):
-        """Backward of the MetadataMLP from the row gradient the native backward left in ``_drows``, the exchange of its
-        gradients and its SGD step (the U-Net's rule and kernel: p -= (lr / world) * sum over ranks of g)."""
-        ps = [p for p in self.metadata_encoder.parameters() if p.requires_grad]
-        if not ps:
-            return
-        for p in ps:
-            p.grad = None
-        rows.backward(self._drows)
-        # one flat buffer (every tensor's size is a multiple of 4 floats: whole 16-byte chunks for the SGD kernel)
-        flat = torch.cat([p.grad.reshape(-1) for p in ps])
-        if self.exchange and not self._no_collective:
-            # after the backward, outside the overlapped buckets: some 22 KB, nothing to overlap
-            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=self.group)
-        self.mlp_grads = flat   # like ``grads``: the (summed) gradient of the last step, in parameters() order
-        for p, g in zip(ps, flat.split([p.numel() for p in ps])):
-            ops.sgd_step_(p.data, g, self.lr / self.world)
-            p.grad = None
 
     def _train_step(self, img, labels, mtd=None, mtd_masks="auto"):
         m = self.model
@@ -370,14 +354,7 @@ class SegTrainer:
                 allreduce_buckets(self.grads, self.buckets, self.group)
                 if self.sync_buffers:
                     dist.broadcast(m.flat_buffers(), src=self._src0, group=self.group)
-        if self.optimizer is not None:
-            self._optim_step(rows)
-            m._eval.note_native_write()
-            return self.loss
-        if rows is not None:
-            self._mlp_step(rows)
-        # DDP averages: fold 1/world into the step size
-        ops.sgd_step_(m._flat_p, self.grads, self.lr / self.world)
+        self._step(rows)
         m._eval.note_native_write()   # parameters changed behind torch's version counter
         return self.loss
 

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import flat as _flat
 from ._native_model import query_layout, tensor_of
 from .tta import tta_codes, tta_predict
 
@@ -376,27 +377,14 @@ class Unet(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise L.FlairHipError("flair_amd.Unet runs on a HIP device only: call .cuda() first (no CPU fallback)")
-        ok = self._flat_p is not None and self._flat_p.device == dev
-        if ok:
-            base_p, base_b = self._flat_p.data_ptr(), self._flat_b.data_ptr()
-            for name in self._param_names + self._buffer_names:
-                t = getattr(*tensor_of(self, name))
-                _, off, kind, _ = self._layout[name]
-                if t.data_ptr() != (base_p if kind == 0 else base_b) + 4 * off or t.dtype != torch.float32:
-                    ok = False
-                    break
-        if ok:
+        # (tensor, float offset, shape) of the parameters and of the running statistics
+        params, buffers = ([(getattr(*tensor_of(self, name)), self._layout[name][1], self._layout[name][0]) for name in names]
+                           for names in (self._param_names, self._buffer_names))
+        if _flat.aliased(self._flat_p, (i[:2] for i in params)) and _flat.aliased(self._flat_b, (i[:2] for i in buffers)):
             return
-        flat_p = torch.zeros(self._n_params, dtype=torch.float32, device=dev)
-        flat_b = torch.zeros(max(self._n_buffers, 1), dtype=torch.float32, device=dev)
+        flat_p = _flat.bind(params, self._n_params, dev)
+        flat_b = _flat.bind(buffers, max(self._n_buffers, 1), dev)
         with torch.no_grad():
-            for name in self._param_names + self._buffer_names:
-                t = getattr(*tensor_of(self, name))
-                shape, off, kind, _ = self._layout[name]
-                n = math.prod(shape)
-                view = (flat_p if kind == 0 else flat_b)[off:off + n].view(shape)
-                view.copy_(t.detach().to(device=dev, dtype=torch.float32))
-                t.data = view
             bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
             flat_n = torch.zeros(len(bns), dtype=torch.int64, device=dev)
             for i, m in enumerate(bns):

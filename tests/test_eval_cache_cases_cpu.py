@@ -1,7 +1,7 @@
 """CPU preconditions of test_gpu_eval_cache.py (no device needed).
 
 (a) The torch semantics the eval key of ``flair_amd.Unet`` leans on, and the collision the key had while it held version counters
-    only: ``flatten_()``'s copy-and-rebind is replayed on a Conv2d and a BatchNorm2d.
+    only: ``flatten_()``'s copy-and-rebind (``flair_amd.flat``) runs on a Conv2d and a BatchNorm2d.
 (b) Every writer of eval_cache_cases really changes the answer — judged on the CPU oracle alone, so that a GPU case cannot pass
     because the stale and the fresh result happen to coincide.
 """
@@ -12,12 +12,13 @@ import torch
 import torch.nn as nn
 
 import eval_cache_cases as ec
+from flair_amd import flat
 
 
 # ------------------------------------------------------------------------------------------------ (a) what the key can see
 class _Flat:
-    """``Unet.flatten_`` without the native library: parameters -> one flat buffer, running statistics -> another, every tensor
-    rebound as a ``.data`` view; rebuilt when a tensor no longer aliases its slot."""
+    """``Unet.flatten_`` without the native library, over the binder it uses: parameters -> one flat buffer, running statistics ->
+    another, every tensor rebound as a ``.data`` view; both rebuilt when a tensor no longer aliases its slot."""
 
     def __init__(self):
         self.mods = nn.ModuleList([nn.Conv2d(3, 4, 3), nn.BatchNorm2d(4)])
@@ -42,23 +43,10 @@ class _Flat:
         return getattr(mod, leaf)
 
     def flatten_(self):
-        ok = self.flat_p is not None
-        if ok:
-            for name, kind, off, _ in self.layout:
-                t = self.tensor(name)
-                if t.data_ptr() != (self.flat_p, self.flat_b)[kind].data_ptr() + 4 * off or t.dtype != torch.float32:
-                    ok = False
-                    break
-        if ok:
+        items = [[(self.tensor(name), off, shape) for name, kind, off, shape in self.layout if kind == k] for k in (0, 1)]
+        if all(flat.aliased(f, (i[:2] for i in its)) for f, its in zip((self.flat_p, self.flat_b), items)):
             return False
-        flat = [torch.zeros(self.n[0]), torch.zeros(self.n[1])]
-        with torch.no_grad():
-            for name, kind, off, shape in self.layout:
-                t = self.tensor(name)
-                view = flat[kind][off:off + t.numel()].view(shape)
-                view.copy_(t.detach().to(torch.float32))
-                t.data = view
-        self.flat_p, self.flat_b = flat
+        self.flat_p, self.flat_b = (flat.bind(its, n, "cpu") for its, n in zip(items, self.n))
         return True
 
     def versions(self):
@@ -113,6 +101,39 @@ def test_a_key_of_versions_alone_collides_where_one_with_addresses_does_not(writ
     assert (f.versions() + f.addresses()) != (versions + addresses)   # the key with addresses tells them apart
     if writer is _rebind_all:
         assert not torch.equal(f.flat_p, before)                      # and so did the values
+
+
+def test_bind_copies_every_tensor_to_its_offset_and_aliased_tells_when_one_left():
+    mods = nn.ModuleList([nn.Conv2d(3, 4, 3), nn.BatchNorm2d(4)])
+    ts = list(mods.parameters())
+    offs, o = [], 5                                   # a gap in front, and one of 3 floats behind every tensor
+    for t in ts:
+        offs.append(o)
+        o += t.numel() + 3
+    want = [t.detach().clone() for t in ts]
+    items = lambda: list(zip(ts, offs))
+    buf = flat.bind([(t, off, t.shape) for t, off in items()], o, "cpu")
+    assert buf.dtype == torch.float32 and tuple(buf.shape) == (o,) and buf._version == len(ts)   # one copy_ per tensor
+    used = torch.zeros(o, dtype=torch.bool)
+    for t, off, w in zip(ts, offs, want):
+        assert torch.equal(t.detach(), w) and t.data_ptr() == buf.data_ptr() + 4 * off
+        assert torch.equal(buf[off:off + t.numel()].view(t.shape), w)
+        used[off:off + t.numel()] = True
+    assert int((~used).sum()) == 5 + 3 * len(ts) and not bool(buf[~used].any())    # the gaps stay zero
+    assert flat.aliased(buf, items())
+    with torch.no_grad():
+        for t in ts:
+            t.mul_(2)                                 # in-place writes go through the views
+    assert flat.aliased(buf, items()) and torch.equal(buf[offs[0]:offs[0] + ts[0].numel()].view(ts[0].shape), 2 * want[0])
+    assert not flat.aliased(None, items())
+    assert not flat.aliased(buf, [(t, off + (i == 1)) for i, (t, off) in enumerate(items())])     # an offset off by one
+    keep = ts[2].data
+    ts[2].data = keep.clone()                         # one tensor rebound
+    assert not flat.aliased(buf, items())
+    ts[2].data = keep
+    assert flat.aliased(buf, items())
+    mods.double()                                     # (parameters keep their identity: Module._apply rebinds .data)
+    assert not flat.aliased(buf, items())
 
 
 # ------------------------------------------------------------------------------------------------ (b) every writer matters

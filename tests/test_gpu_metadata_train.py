@@ -416,6 +416,26 @@ def test_train_step_with_metadata_is_the_documented_sequence_bit_for_bit(dev):
     assert tuple(ta.mlp_grads.shape) == (sum(p.numel() for p in enc_a.parameters()),)
 
 
+def test_plain_metadata_step_updates_two_flat_buffers_in_two_launches(dev):
+    """(the bits are pinned by the test above)"""
+    import flair_amd
+    import launch_helpers as LH
+    from flair_amd import flat
+    C = 13
+    _, m = _pair(5, C, 5, dev)
+    enc = _seeded_mlp(9).to(dev).train()
+    x, mtd, lab = _batch512(1, C, 14)
+    x, mtd, lab = x.to(dev), mtd.to(dev), lab.to(torch.uint8).to(dev)
+    tr = flair_amd.SegTrainer(m.train(), lr=0.02, metadata_encoder=enc)
+    _, ran = LH.profiled(lambda: tr.train_step(x, lab, mtd), keep=("sgd", "optim_"), slots=2048)
+    assert ran == {"optim_sgd": 2}, ran                      # the U-Net's buffer and the MLP's: not one launch per MLP tensor
+    ps = [p for p in enc.parameters() if p.requires_grad]
+    offs = [sum(p.numel() for p in ps[:i]) for i in range(len(ps))]
+    assert len(ps) == 6 and tr._mlp_opt.flat.numel() == sum(p.numel() for p in ps)
+    assert flat.aliased(tr._mlp_opt.flat, zip(ps, offs))
+    assert tr.optimizer is None
+
+
 def test_auto_masks_follow_the_encoders_mode_and_torchs_generator(dev):
     import flair_amd
     C = 13

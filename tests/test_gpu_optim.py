@@ -1,5 +1,6 @@
 """The fused trainer's update rules on the device: the kernels of csrc/optim.hip through the raw C ABI on guarded buffers, then
-``SegTrainer(..., optimizer=, clip_grad_norm=)``: rules, metadata, state dicts / checkpoints, two data-parallel ranks.
+``SegTrainer(..., optimizer=, clip_grad_norm=)`` and the plain trainer, which takes the same path: rules, metadata, state dicts /
+checkpoints, two data-parallel ranks.
 
 Every comparison is one step of the fp64 restatement of tests/optim_cases.py from the device's own pre-step fp32 state, within the
 bound derived there (roundings of the expression x 2^-24 x the magnitudes they act on); bit-equalities are bit-equalities."""
@@ -440,6 +441,57 @@ def test_trainer_default_rule_is_the_plain_trainer_bit_for_bit(dev):
         tb.optimizer_state_dict()
     with pytest.raises(TypeError):
         flair_amd.SegTrainer(b, lr=0.02, optimizer=torch.optim.SGD(b.parameters(), lr=0.02))
+
+
+def _plain_step_by_hand(model, tr, img, lab, lr):
+    """The plain step call by call, its update by the reference kernel flair_sgd_step (tr lends its head buffers and gradient)"""
+    from flair_amd import _lib as L
+    from flair_amd import ops
+    l = L.lib()
+    B, _, H, W = img.shape
+    ld = tr._buffers(B, H, W)
+    model._c_forward(img, training=True, want_logits=False)
+    L.check(l.flair_ce_head_nhwc(l.flair_unet_logits_nhwc(model._h), model._dt, ld, L.ptr(lab), ops._LABEL_KIND[lab.dtype],
+                                 L.ptr(tr.class_weight), B, model.classes, H, W, L.ptr(tr.loss), L.ptr(tr._dl), L.ptr(tr._preds), None,
+                                 L.ptr(tr.confmat), L.ptr(tr._ce_ws), L.stream()), "ce_head_nhwc")
+    model._c_backward(dlogits_nhwc=tr._dl, grads=tr.grads)
+    ops.sgd_step_(model._flat_p, tr.grads, lr)
+    model._eval.note_native_write()
+    return tr.loss.clone()
+
+
+def _rebind_head_bias(model):
+    b = model.segmentation_head[0].bias
+    b.data = b.data * 2 + 1          # a new tensor behind the parameter: the next forward rebuilds both flat buffers
+
+
+def test_plain_trainer_is_the_reference_kernel_and_follows_a_rebuilt_flat_buffer(dev):
+    import flair_amd
+    lr = 0.02
+    a, b = _model(dev), _model(dev)
+    ta, lender = flair_amd.SegTrainer(a, lr=lr), flair_amd.SegTrainer(b, lr=lr)
+    x, lab = _batch(seed=3, B=1)
+    x, lab = x.to(dev), lab.to(dev)
+    flats = []
+    for step in range(2):
+        la = ta.train_step(x, lab).clone()
+        lb = _plain_step_by_hand(b, lender, x, lab, lr)
+        assert torch.equal(_bits(la), _bits(lb)), (step, float(la), float(lb))
+        assert torch.equal(_bits(a.flat_parameters()), _bits(b.flat_parameters())), step
+        assert torch.equal(_bits(a.flat_buffers()), _bits(b.flat_buffers())) and torch.equal(a._flat_n, b._flat_n), step
+        assert ta._opt.flat is a._flat_p and ta._opt.state == [] and ta._opt.steps == step + 1
+        flats.append(a._flat_p)
+        _rebind_head_bias(a)
+        _rebind_head_bias(b)
+    assert flats[0] is not flats[1]                              # the second step did run on a rebuilt buffer
+    assert ta.optimizer is None
+    # a rule with state cannot follow: its buffers are indexed like the flat parameters they were allocated beside
+    c = _model(dev)
+    tc = flair_amd.SegTrainer(c, lr=lr, optimizer=FO.SGD(momentum=0.9))
+    tc.train_step(x, lab)
+    _rebind_head_bias(c)
+    with pytest.raises(RuntimeError, match="rebuilt"):
+        tc.train_step(x, lab)
 
 
 def test_trainer_metadata_takes_the_same_rule_and_one_norm(dev):

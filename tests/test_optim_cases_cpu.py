@@ -211,3 +211,14 @@ def test_get_segmentation_module_reads_the_optimizer_key():
     task = get_segmentation_module(dict(cfg, optimizer={"name": "sgd", "momentum": 0.9, "nesterov": True}), "train")
     g = task.optimizer.param_groups[0]
     assert type(task.optimizer) is torch.optim.SGD and (g["momentum"], g["nesterov"], g["lr"]) == (0.9, True, 0.02)
+
+
+@pytest.mark.parametrize("world", [1, 2, 3, 8])
+def test_update_scales_keeps_both_ways_of_averaging_over_the_ranks(world):
+    """The plain trainer's p -= f32(lr / world) * sum g and the other rules' p -= f32(lr) * (sum g * f32(1 / world)) differ in the last
+    bit when world is no power of two: each keeps its own pair, as Python floats, and a scale of exactly 1.0 selects the unscaled kernel."""
+    from flair_amd.train import update_scales
+    lr = 0.05
+    assert update_scales(lr, world, True) == (lr / world, 1.0)
+    assert update_scales(lr, world, False) == (lr, 1.0 / world)
+    assert all(type(v) is float for fold in (True, False) for v in update_scales(lr, world, fold))
