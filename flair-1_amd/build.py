@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "flair_amd")
 OBJ_DIR = os.path.join(HERE, "build")
 LIB = os.path.join(OUT_DIR, "libflair_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_hg.hip", "wgrad.hip", "wgrad_halo.hip", "bwd_halo16.hip", "wgrad_hg.hip", "stem.hip", "batchnorm.hip", "misc.hip", "ce_head.hip", "feed.hip", "zone_stitch.hip", "zone_metrics.hip", "tta.hip", "optim.hip", "tiff_lzw.hip", "tiff_read.hip", "unet.hip", "capi.hip", "prof.hip", "tune.hip", "metadata_mlp.hip", "tf_exec.hip", "segformer_ops.hip", "segformer.hip", "swin_ops.hip", "upernet.hip"]
+SOURCES = ["conv_igemm.hip", "conv_halo.hip", "conv_hg.hip", "wgrad.hip", "wgrad_halo.hip", "bwd_halo16.hip", "wgrad_hg.hip", "stem.hip", "batchnorm.hip", "misc.hip", "ce_head.hip", "seg_loss.hip", "feed.hip", "zone_stitch.hip", "zone_metrics.hip", "tta.hip", "optim.hip", "tiff_lzw.hip", "tiff_read.hip", "unet.hip", "capi.hip", "prof.hip", "tune.hip", "metadata_mlp.hip", "tf_exec.hip", "segformer_ops.hip", "segformer.hip", "swin_ops.hip", "upernet.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # The zone_detect consumers and the test-time-augmentation accumulate (tta.hip), templated on their logit source (csrc/logit_source.h).  In the quarter-resolution instantiations the
 # SLP vectorizer turns the per-class array of the unrolled softmax loops into whole-array register copies (254 VGPRs + AGPR copies,

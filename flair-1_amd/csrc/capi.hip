@@ -79,6 +79,8 @@ const char* flair_strerror(int code) {
     case -17: return "flair_unet_fwd_opts_t: drows_f32 is for a training forward (an eval-mode forward takes rows_f32 alone)";
     case -18: return "flair_unet_fwd_opts_t: the gradient that reaches the bottleneck tensor was stored masked, its sums into drows_f32 would be wrong";
     case -19: return "D4 transform code with an odd rot90 count needs a square tile (H == W)";
+    case -20: return "flair_seg_loss_t: invalid specification (ce / dice negative or both 0, label_smoothing outside [0, 1), focal_gamma neither "
+                     "0 nor >= 1, label_smoothing with focal_gamma, either without ce, dice_smooth < 0, dice_eps <= 0)";
     case -100: return "workspace too small";
     default: return "invalid argument";
   }
@@ -191,6 +193,35 @@ int flair_ce_head_nhwc(const void* logits_nhwc, int dtype, int ld, const void* l
   a.dlogits_dtype = dtype; a.dlogits_ld = ld; a.preds_u8 = preds_u8; a.preds_i64 = nullptr;
   a.targets_i32 = targets_i32; a.confmat = (long long*)confmat; a.workspace = (float*)workspace;
   return ce_head(a, (hipStream_t)stream);
+}
+size_t flair_seg_loss_workspace_bytes(int B, int C, int H, int W) { return seg_loss_workspace_bytes(B, C, H, W); }
+
+static void seg_loss_common(SegLossArgs& a, const void* labels, int label_kind, const float* weight, int B, int C, int H, int W,
+                            const flair_seg_loss_t* spec, float* loss3, void* dl, uint8_t* preds_u8, int32_t* targets_i32, int64_t* confmat,
+                            void* workspace) {
+  a.labels = labels; a.label_kind = label_kind; a.weight = weight; a.B = B; a.C = C; a.H = H; a.W = W;
+  a.spec = SegLossSpec{spec->ce, spec->label_smoothing, spec->focal_gamma, spec->dice, spec->dice_smooth, spec->dice_eps};
+  a.loss3 = loss3; a.dl = dl; a.preds_u8 = preds_u8; a.targets_i32 = targets_i32; a.confmat = (long long*)confmat;
+  a.workspace = (float*)workspace;
+}
+int flair_seg_loss(const float* logits, const void* labels, int label_kind, const float* weight, int B, int C, int H, int W,
+                   const flair_seg_loss_t* spec, float* loss3, float* dl_nchw, uint8_t* preds_u8, int64_t* preds_i64,
+                   int32_t* targets_i32, int64_t* confmat, void* workspace, void* stream) {
+  if (!logits || !labels || !spec || !loss3 || !workspace || label_kind < 0 || label_kind > 3) return -1;
+  SegLossArgs a;
+  seg_loss_common(a, labels, label_kind, weight, B, C, H, W, spec, loss3, dl_nchw, preds_u8, targets_i32, confmat, workspace);
+  a.logits = logits; a.preds_i64 = (long long*)preds_i64;
+  return seg_loss(a, (hipStream_t)stream);
+}
+int flair_seg_loss_nhwc(const void* logits_nhwc, int dtype, int ld, const void* labels, int label_kind, const float* weight, int B,
+                        int C, int H, int W, const flair_seg_loss_t* spec, float* loss3, void* dl_nhwc, uint8_t* preds_u8,
+                        int32_t* targets_i32, int64_t* confmat, void* workspace, void* stream) {
+  if (!logits_nhwc || !labels || !spec || !loss3 || !workspace || label_kind < 0 || label_kind > 3) return -1;
+  if (dtype != DT_F32 && dtype != DT_BF16) return -2;
+  SegLossArgs a;
+  seg_loss_common(a, labels, label_kind, weight, B, C, H, W, spec, loss3, dl_nhwc, preds_u8, targets_i32, confmat, workspace);
+  a.logits_nhwc = logits_nhwc; a.dtype = dtype; a.ld = ld;
+  return seg_loss(a, (hipStream_t)stream);
 }
 int flair_softmax_argmax_nhwc(const void* logits_nhwc, int dtype, int ld, int B, int C, int H, int W, uint8_t* preds_u8,
                               int64_t* preds_i64, float* maxprob, void* stream) {

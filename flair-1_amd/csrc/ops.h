@@ -118,6 +118,29 @@ int confmat_update(const void* target, int target_kind, const void* pred, int pr
                    long long* confmat, hipStream_t s);
 int jaccard_from_confmat(const long long* confmat, int C, float* per_class, float* weighted, float* macro, hipStream_t s);
 
+// ---- seg_loss.hip: the head with a configurable objective (label-smoothed / focal CE, soft Dice); the field order of
+// flair_seg_loss_t (include/flair_hip.h)
+struct SegLossSpec { float ce, label_smoothing, focal_gamma, dice, dice_smooth, dice_eps; };
+struct SegLossArgs {
+  const float* logits = nullptr;       // NCHW fp32 [B][C][H][W]   (or null with logits_nhwc set)
+  const void* logits_nhwc = nullptr;   // NHWC T [B*H*W][ld], ld 16 or 32
+  int dtype = 0, ld = 0;               // of logits_nhwc and of dl when the source is NHWC
+  const void* labels = nullptr;
+  int label_kind = 0;                  // as CeArgs::label_kind
+  const float* weight = nullptr;       // optional class weights [C]
+  int B = 0, C = 0, H = 0, W = 0;
+  SegLossSpec spec = {};
+  float* loss3 = nullptr;              // out: [loss, CE term, Dice term]
+  void* dl = nullptr;                  // optional out: fp32 NCHW for the NCHW source, else NHWC T rows of stride ld, padding zeroed
+  unsigned char* preds_u8 = nullptr;   // optional out [B][H][W]
+  long long* preds_i64 = nullptr;      // optional out [B][H][W] (NCHW source only)
+  int* targets_i32 = nullptr;          // optional out [B][H][W]
+  long long* confmat = nullptr;        // optional in/out [C][C]
+  float* workspace = nullptr;          // >= seg_loss_workspace_bytes() bytes
+};
+size_t seg_loss_workspace_bytes(int B, int C, int H, int W);
+int seg_loss(const SegLossArgs& a, hipStream_t s);
+
 // ---- feed.hip (rows either side of the hot path)
 struct FeedArgs {
   static constexpr int MAXCH = 16;

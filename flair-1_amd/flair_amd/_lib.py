@@ -43,6 +43,9 @@ PROTOTYPES = {
     "flair_ce_head": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
     "flair_unet_logits_nhwc": (vp, [vp]),
     "flair_ce_head_nhwc": (i32, [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "flair_seg_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "flair_seg_loss": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "flair_seg_loss_nhwc": (i32, [vp, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "flair_softmax_argmax_nhwc": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
     "flair_softmax_argmax": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, vp]),
     "flair_confmat_update": (i32, [vp, i32, vp, i32, i64, i32, vp, vp]),
@@ -177,6 +180,11 @@ class UnetFwdOpts(C.Structure):
                 ("ce_labels", vp), ("ce_label_kind", i32), ("ce_class_weight", vp), ("ce_loss", vp),
                 ("ce_preds_u8", vp), ("ce_confmat", vp), ("ce_workspace", vp),
                 ("rows_f32", vp), ("drows_f32", vp)]
+
+
+class SegLossSpec(C.Structure):
+    """flair_seg_loss_t (flair_amd.losses.SegLoss.astuple() in its order)"""
+    _fields_ = [("ce", f32), ("label_smoothing", f32), ("focal_gamma", f32), ("dice", f32), ("dice_smooth", f32), ("dice_eps", f32)]
 
 
 class ConvEx(C.Structure):

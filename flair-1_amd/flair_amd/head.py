@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .losses import SegLoss
 
 
 class _CEFn(torch.autograd.Function):
@@ -54,6 +55,50 @@ class FusedCrossEntropyLoss(nn.Module):
                 labels = labels.long()
         w = None if self.weight is None else self.weight.to(logits.device)
         return _CEFn.apply(logits, labels, w, self)
+
+
+class _SegLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, weight, owner):
+        terms, dl, preds, _ = ops.seg_loss(logits.detach().float().contiguous(), labels, owner.spec, weight, want_dlogits=True,
+                                           want_preds="i64", confmat=owner._confmat_sink)
+        owner.last_preds = preds
+        owner.last_terms = terms
+        ctx.save_for_backward(dl)
+        return terms[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None
+
+
+class FusedSegLoss(nn.Module):
+    """A ``flair_amd.losses.SegLoss`` objective (label-smoothed or focal CE, soft Dice) with ``nn.CrossEntropyLoss``'s call
+    signature for (B,C,H,W) logits and integer or one-hot targets, one fused HIP head (csrc/seg_loss.hip).
+
+    After each call ``last_preds`` holds argmax(softmax(logits)) (B,H,W) int64 and ``last_terms`` the device tensor
+    [loss, CE term, Dice term]."""
+
+    def __init__(self, spec, weight=None):
+        super().__init__()
+        if not isinstance(spec, SegLoss):
+            raise TypeError("FusedSegLoss takes a flair_amd.losses.SegLoss specification")
+        self.spec = spec
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32))
+        self.last_preds = None
+        self.last_terms = None
+        self._confmat_sink = None
+
+    def forward(self, logits, target):
+        labels = target.contiguous()
+        if not (labels.dtype == torch.float32 and labels.dim() == 4) and labels.dtype not in (torch.uint8, torch.int32, torch.int64):
+            labels = labels.long()
+        w = None if self.weight is None else self.weight.to(logits.device)
+        return _SegLossFn.apply(logits, labels, w, self)
+
+    def extra_repr(self):
+        return repr(self.spec)
 
 
 class MulticlassJaccardIndex(nn.Module):

@@ -353,6 +353,33 @@ def ce_head(logits, labels, weight=None, want_dlogits=True, want_preds="u8", con
     return loss, dl, (pu8 if pu8 is not None else pi64), tg
 
 
+def seg_loss_spec(spec):
+    """The flair_seg_loss_t of a ``flair_amd.losses.SegLoss`` (or of six floats in its field order: the operator tests)."""
+    vals = spec.astuple() if hasattr(spec, "astuple") else tuple(spec)
+    return L.SegLossSpec(*[float(v) for v in vals])
+
+
+def seg_loss(logits, labels, spec, weight=None, want_dlogits=True, want_preds="u8", confmat=None, want_targets=False):
+    """The head with a configurable objective (flair_seg_loss; ``spec``: a flair_amd.losses.SegLoss): loss = ce * CE + dice * Dice,
+    its gradient, argmax(softmax) and the confusion matrix.  logits fp32 (B,C,H,W); labels as for ce_head.  Returns
+    (terms, dlogits, preds, targets): terms a 3-float device tensor [loss, CE, Dice]."""
+    import ctypes as C
+    B, Cc, H, W = logits.shape
+    kind = 3 if labels.dtype == torch.float32 else _LABEL_KIND[labels.dtype]
+    dev = logits.device
+    terms = torch.empty(3, dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if want_dlogits else None
+    pu8 = torch.empty(B, H, W, dtype=torch.uint8, device=dev) if want_preds == "u8" else None
+    pi64 = torch.empty(B, H, W, dtype=torch.int64, device=dev) if want_preds == "i64" else None
+    tg = torch.empty(B, H, W, dtype=torch.int32, device=dev) if want_targets else None
+    l = L.lib()
+    ws = _ws(l.flair_seg_loss_workspace_bytes(B, Cc, H, W), dev)
+    sp = seg_loss_spec(spec)
+    L.check(l.flair_seg_loss(L.ptr(logits), L.ptr(labels), kind, L.ptr(weight), B, Cc, H, W, C.byref(sp), L.ptr(terms), L.ptr(dl),
+                             L.ptr(pu8), L.ptr(pi64), L.ptr(tg), L.ptr(confmat), L.ptr(ws), L.stream()), "seg_loss")
+    return terms, dl, (pu8 if pu8 is not None else pi64), tg
+
+
 def softmax_argmax(logits, want="i64", want_maxprob=False):
     B, Cc, H, W = logits.shape
     dev = logits.device

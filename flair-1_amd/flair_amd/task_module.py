@@ -16,6 +16,7 @@ import torch.nn as nn
 
 from . import ops
 from .head import MeanMetric, MulticlassJaccardIndex
+from .losses import SegLoss
 from .tta import tta_codes, tta_predict
 
 try:  # pragma: no cover - lightning is absent in the build image
@@ -40,11 +41,32 @@ class _StepFn(torch.autograd.Function):
         return dl * g, None, None
 
 
+class _SegLossStepFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, msk, weight, spec):
+        terms, dl, preds, targets = ops.seg_loss(logits.detach().float().contiguous(), msk.contiguous(), spec, weight,
+                                                 want_dlogits=True, want_preds="i64", want_targets=True)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(preds, targets)
+        return terms[0].clone(), preds, targets
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gt):
+        (dl,) = ctx.saved_tensors
+        return dl * g, None, None, None
+
+
 def fused_step(logits, msk, criterion):
-    """task_module.py:71-79 in one launch.  msk: fp32 one-hot (B,C,H,W) (reference layout) or (B,H,W) ints."""
+    """task_module.py:71-79 in one launch.  msk: fp32 one-hot (B,C,H,W) (reference layout) or (B,H,W) ints.  A criterion that
+    carries a ``flair_amd.losses.SegLoss`` (``head.FusedSegLoss``: its ``spec``) is computed as that objective, any other as the
+    weighted cross entropy of its ``weight``."""
     w = getattr(criterion, "weight", None)
     w = None if w is None else w.to(device=logits.device, dtype=torch.float32)
-    loss, preds, targets = _StepFn.apply(logits, msk, w)
+    spec = getattr(criterion, "spec", None)
+    if isinstance(spec, SegLoss):
+        loss, preds, targets = _SegLossStepFn.apply(logits, msk, w, spec)
+    else:
+        loss, preds, targets = _StepFn.apply(logits, msk, w)
     return loss, preds.flatten(start_dim=1), targets.flatten(start_dim=1)
 
 

@@ -20,7 +20,8 @@ from torch import nn
 from torch.optim.lr_scheduler import ReduceLROnPlateau
 
 from .data_feed import TileFeed
-from .head import FusedCrossEntropyLoss
+from . import losses
+from .head import FusedCrossEntropyLoss, FusedSegLoss
 from .model import FLAIR_ModelFactory
 from .optim import torch_optimizer_from_config
 from .task_module import segmentation_task_predict, segmentation_task_training
@@ -45,6 +46,11 @@ def get_segmentation_module(config, stage: str = "train", compute_dtype=None):
             criterion = FusedCrossEntropyLoss(weight=class_weights)
         else:
             criterion = FusedCrossEntropyLoss()
+        # optional config key ``loss: {ce:, label_smoothing:, focal_gamma:, dice:, ...}`` (flair_amd.losses); without it the
+        # reference's criterion as built above
+        spec = losses.from_config(config)
+        if spec is not None:
+            criterion = FusedSegLoss(spec, weight=criterion.weight)
         # optional config key ``optimizer: {name: sgd|adamw, ...}``; without it the reference's torch.optim.SGD(lr)
         optimizer = torch_optimizer_from_config(config, model.parameters())
         scheduler = ReduceLROnPlateau(optimizer=optimizer, mode="min", factor=0.5, patience=10, cooldown=4, min_lr=1e-7)

@@ -15,6 +15,7 @@ checkpoints see rank 0's statistics on every rank without a collective of their 
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -22,6 +23,7 @@ import torch.distributed as dist
 
 from . import _lib as L
 from . import flat as _flat
+from . import losses as _losses
 from . import ops
 from . import optim as _optim
 from .model import check_metadata_tile
@@ -98,13 +100,19 @@ class SegTrainer:
 
     def __init__(self, model, lr, class_weight=None, group=None, overlap=True, min_bucket_elems=1 << 18,
                  force_exchange=False, broadcast_buffers=True, class_names=None, metadata_encoder=None,
-                 optimizer=None, clip_grad_norm=None, params=None):
+                 optimizer=None, clip_grad_norm=None, params=None, loss=None):
         """``optimizer``: a ``flair_amd.optim.SGD`` / ``AdamW`` specification; ``clip_grad_norm``: clip_grad_norm_'s max_norm over
         the U-Net's and the MetadataMLP's gradients together; ``params``: the parameter order of ``optimizer_state_dict()``
         (default ``list(model.parameters()) + list(metadata_encoder.parameters())``).  With neither of the first two the step is
         the reference's plain SGD (tasks_utils.py:95), ``optim.SGD()`` through the same kernel, with ``optimizer`` left None and
-        DDP's average folded into the step size (``update_scales``)."""
+        DDP's average folded into the step size (``update_scales``).
+        ``loss``: a ``flair_amd.losses.SegLoss`` -- train_step and validate_step compute that objective (flair_seg_loss_nhwc /
+        flair_seg_loss) in place of the reference's weighted cross entropy, and ``loss_terms`` holds [loss, CE, Dice] of the last
+        train_step; None: the reference's criterion through flair_ce_head_nhwc, every line as before."""
         self.model = model
+        if loss is not None and not isinstance(loss, _losses.SegLoss):
+            raise TypeError("loss must be a flair_amd.losses.SegLoss specification (or None: the reference's cross entropy)")
+        self.loss_spec = loss
         # a MetadataMLP (BASELINE config 4): train_step / validate_step / predict add its encoding to the bottleneck inside their one
         # native call; train_step(..., mtd) also trains it
         self.metadata_encoder = metadata_encoder
@@ -128,6 +136,11 @@ class SegTrainer:
         self.class_weight = None if class_weight is None else torch.as_tensor(class_weight, dtype=torch.float32, device=dev)
         self.confmat = torch.zeros(model.classes, model.classes, dtype=torch.int64, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.loss_terms = None
+        if loss is not None:
+            self.loss_terms = torch.zeros(3, dtype=torch.float32, device=dev)
+            self.loss = self.loss_terms[0]   # the device scalar stays the loss
+            self._loss_c = ops.seg_loss_spec(loss)
         self.buckets = bucket_ranges(model.stage_ranges(), min_bucket_elems)
         self._dl = None
         self._preds = None
@@ -279,7 +292,10 @@ class SegTrainer:
             dev = self.grads.device
             self._dl = torch.empty(B * H * W, ld, dtype=dt, device=dev)
             self._preds = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
-            self._ce_ws = torch.empty(L.lib().flair_ce_workspace_bytes(B, H, W) + 256, dtype=torch.uint8, device=dev)
+            wsb = L.lib().flair_ce_workspace_bytes(B, H, W)
+            if self.loss_spec is not None:
+                wsb = L.lib().flair_seg_loss_workspace_bytes(B, m.classes, H, W)
+            self._ce_ws = torch.empty(wsb + 256, dtype=torch.uint8, device=dev)
         return ld
 
     def train_step(self, img, labels, mtd=None, mtd_masks="auto"):
@@ -330,10 +346,16 @@ class SegTrainer:
         m._c_forward(img, training=True, want_logits=False, train_rows=None if rows is None else (rows.detach(), self._drows))
         kind = 3 if labels.dtype == torch.float32 else ops._LABEL_KIND[labels.dtype]
         l = L.lib()
-        L.check(l.flair_ce_head_nhwc(l.flair_unet_logits_nhwc(m._h), m._dt, ld, L.ptr(labels.contiguous()), kind,
-                                     L.ptr(self.class_weight), B, m.classes, H, W, L.ptr(self.loss), L.ptr(self._dl),
-                                     L.ptr(self._preds), None, L.ptr(self.confmat), L.ptr(self._ce_ws), L.stream()),
-                "ce_head_nhwc")
+        if self.loss_spec is None:
+            L.check(l.flair_ce_head_nhwc(l.flair_unet_logits_nhwc(m._h), m._dt, ld, L.ptr(labels.contiguous()), kind,
+                                         L.ptr(self.class_weight), B, m.classes, H, W, L.ptr(self.loss), L.ptr(self._dl),
+                                         L.ptr(self._preds), None, L.ptr(self.confmat), L.ptr(self._ce_ws), L.stream()),
+                    "ce_head_nhwc")
+        else:
+            L.check(l.flair_seg_loss_nhwc(l.flair_unet_logits_nhwc(m._h), m._dt, ld, L.ptr(labels.contiguous()), kind,
+                                          L.ptr(self.class_weight), B, m.classes, H, W, ctypes.byref(self._loss_c), L.ptr(self.loss_terms),
+                                          L.ptr(self._dl), L.ptr(self._preds), None, L.ptr(self.confmat), L.ptr(self._ce_ws),
+                                          L.stream()), "seg_loss_nhwc")
         if self.exchange and self.overlap:
             m._c_backward(dlogits_nhwc=self._dl, grads=self.grads, stage_events=self.events)
             works = []
@@ -410,6 +432,16 @@ class SegTrainer:
             self._val_ws = torch.empty(L.lib().flair_ce_workspace_bytes(B, H, W) + 256, dtype=torch.uint8, device=dev)
         kind = 3 if labels.dtype == torch.float32 else ops._LABEL_KIND[labels.dtype]
         labels = labels.contiguous()
+        if self.loss_spec is not None:
+            # the objective of train_step on the eval forward's fp32 NCHW logits (Unet.eval_logits: the route that hands the logits
+            # out whether the eval forward ran eagerly or as a replayed graph)
+            terms, _, preds, _ = ops.seg_loss(m.eval_logits(img, bottleneck_rows=rows), labels, self.loss_spec, self.class_weight,
+                                              want_dlogits=False, want_preds="u8", confmat=self.val_confmat)
+            self._val_preds = preds
+            loss = terms[0].clone()
+            self.val_loss_sum += loss
+            self.val_count += 1
+            return loss
         loss = torch.empty((), dtype=torch.float32, device=dev)   # (a tensor of its own: the caller may keep every batch's)
         m._c_forward(img, training=False, want_logits=False,
                      ce=(L.ptr(labels), kind, L.ptr(self.class_weight), L.ptr(loss), L.ptr(self._val_preds),

@@ -153,6 +153,28 @@ const void* flair_unet_logits_nhwc(const flair_unet_t* h);
 int flair_ce_head_nhwc(const void* logits_nhwc, int dtype, int ld, const void* labels, int label_kind,
                        const float* class_weight, int B, int C, int H, int W, float* loss, void* dlogits_nhwc,
                        uint8_t* preds_u8, int32_t* targets_i32, int64_t* confmat, void* workspace, void* stream);
+/* The same head with a configurable objective in place of the weighted cross entropy (the criteria the reference's model library
+ * ships as smp.losses; the reference's own criterion stays flair_ce_head):
+ *   loss = ce * CE + dice * Dice
+ *   CE, focal_gamma == 0:  F.cross_entropy(logits, y, weight, ignore_index, label_smoothing) with mean reduction
+ *   CE, focal_gamma >= 1:  (1/D) sum_i w[y_i] q_i^gamma (-log p_{i,y_i}),  q_i = sum over c != y_i of p_ic,  D = sum_i w[y_i]
+ *   Dice: soft multiclass Dice over the pixels with a valid label of non-zero weight, averaged over the C classes, the classes
+ *         without such a pixel counting 0:  1 - (2 I_c + dice_smooth) / max(P_c + T_c + dice_smooth, dice_eps)
+ * Labels, label kinds, ignored labels, preds, targets and confmat as for flair_ce_head; preds and confmat are bit-identical to its.
+ * loss3: three floats [loss, CE, Dice].  dlogits: the gradient of loss, fp32 NCHW (flair_seg_loss) or NHWC rows of `dtype` with
+ * stride ld and zeroed padding columns (flair_seg_loss_nhwc, ld 16 or 32).  workspace: flair_seg_loss_workspace_bytes(), 4-byte
+ * aligned.  No floating-point atomics: two calls on the same input give the same bits.
+ * A spec is invalid (-20) when: ce < 0 or dice < 0 or both 0; label_smoothing outside [0, 1); focal_gamma neither 0 nor >= 1;
+ * label_smoothing > 0 with focal_gamma > 0; either of them with ce == 0; dice_smooth < 0; dice_eps <= 0; any field not finite.
+ * Other codes as for flair_ce_head(_nhwc), all returned before anything is enqueued. */
+typedef struct flair_seg_loss { float ce, label_smoothing, focal_gamma, dice, dice_smooth, dice_eps; } flair_seg_loss_t;
+size_t flair_seg_loss_workspace_bytes(int B, int C, int H, int W);
+int flair_seg_loss(const float* logits_nchw, const void* labels, int label_kind, const float* class_weight, int B, int C, int H,
+                   int W, const flair_seg_loss_t* spec, float* loss3, float* dlogits_nchw, uint8_t* preds_u8, int64_t* preds_i64,
+                   int32_t* targets_i32, int64_t* confmat, void* workspace, void* stream);
+int flair_seg_loss_nhwc(const void* logits_nhwc, int dtype, int ld, const void* labels, int label_kind, const float* class_weight,
+                        int B, int C, int H, int W, const flair_seg_loss_t* spec, float* loss3, void* dlogits_nhwc,
+                        uint8_t* preds_u8, int32_t* targets_i32, int64_t* confmat, void* workspace, void* stream);
 /* predict_step over NHWC logits left in the workspace (flair_unet_forward with logits_nchw == NULL, flair_unet_logits_nhwc). */
 int flair_softmax_argmax_nhwc(const void* logits_nhwc, int dtype, int ld, int B, int C, int H, int W, uint8_t* preds_u8,
                               int64_t* preds_i64, float* maxprob, void* stream);
